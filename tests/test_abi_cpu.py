@@ -127,9 +127,13 @@ def test_tuning_table_hooks_and_no_stray_getenv(lib):
     kernel source reads an environment variable of its own (the developer-build ablation switches excepted)."""
     from coivo_amd import _lib
     assert _lib.tune_get("bn64_min_wgs") == 4096 and _lib.tune_get("wgrad_atomic_mb") == 3
-    _lib.tune_set("quad_min_wgs", 7)
-    assert _lib.tune_get("quad_min_wgs") == 7
-    _lib.tune_set("quad_min_wgs", 2048)
+    saved = _lib.tune_get("quad_min_wgs")
+    try:
+        _lib.tune_set("quad_min_wgs", 7)
+        assert _lib.tune_get("quad_min_wgs") == 7
+    finally:
+        _lib.tune_set("quad_min_wgs", saved)      # the tests share one process: later ones must see the library's default
+    assert _lib.tune_get("quad_min_wgs") == saved
     assert lib.colvo_tune_set(b"no_such_entry", 1.0) != 0 and b"no tuning entry" in lib.colvo_last_error()
     csrc = os.path.join(ROOT, "coivo_amd", "csrc")
     for f in os.listdir(csrc):

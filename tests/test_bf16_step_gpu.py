@@ -9,7 +9,9 @@ decisions, and the bar is DERIVED in the same step: the distance between that or
 of the HIP networks emulated (tests/gpu_util.py oracle_step_bf16) is the size of the bf16 data path's own noise -- 0.5-1.5 % of a
 gradient tensor's norm at B=2 64x96 (first run on the GPU: HIP 0.5-1.2e-2, emulated 0.3-1.6e-2) -- and a HIP gradient may be at
 most 3 x that far from the oracle.  A dropped tile, a lost
-atomic flush or a fork that lets a weight gradient read its dy early moves a layer's gradient by >= 10 %."""
+atomic flush or a fork that lets a weight gradient read its dy early moves a layer's gradient by >= 10 %.
+(bench.py times its networks with deterministic weight gradients, so that two runs compute the same thing; the form held here is
+the library's default, the one a train loop runs.)"""
 import pytest
 import torch
 
@@ -39,7 +41,7 @@ def test_benchmarked_bf16_backward_against_the_oracle_at_the_bf16_noise_level(B,
     dn, pn = hnn.DepthNet(compute_dtype=torch.bfloat16), hnn.PoseNet(compute_dtype=torch.bfloat16)
     dn.load_state_dict(bf16_rounded_state(dn_o))
     pn.load_state_dict(bf16_rounded_state(pn_o))
-    dn.deterministic = pn.deterministic = False            # the benchmarked form, whatever COLVO_DETERMINISTIC says
+    dn.deterministic = pn.deterministic = False            # the default form (float atomics), whatever COLVO_DETERMINISTIC says
     dn.zero_grad(); pn.zero_grad()
     _lib.form_counts(reset=True)
     loss, d_t, d_r, pose, a, bb = hnn.dcdp_forward(dn, pn, d["tgt"], d["ref"], d["K"])     # the fast path of bench.py

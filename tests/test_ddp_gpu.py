@@ -99,7 +99,7 @@ def test_rccl_path_with_one_rank():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_PORT="29533", COLVO_DETERMINISTIC="1")
     common = [sys.executable, os.path.join(root, "bench.py"), "--no-cpu-baseline", "--no-roofline-cfg2", "--no-side-measurements",
               "--steps", "30", "--warmup", "5",
-              "--graph", "off"]        # (the one-GPU default `best` runs 23 more steps before the warm-up: different final loss)
+              "--graph", "off"]        # (the one-GPU default `best` may time the replayed graph; the RCCL runs here are eager)
     out = {}
     # rccl: RCCL called natively on the group's communicator (ddp._NativeRccl, the default since round 5); rccl_torch: the same step
     # through ProcessGroup.allreduce (COLVO_DDP_TORCH_COLLECTIVES=1), the fallback

@@ -12,6 +12,7 @@ prints, per matching kernel: MFMA count and how many of them directly follow "ds
 import os
 import re
 import sys
+import tempfile
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from coivo_amd import build  # noqa: E402
@@ -19,9 +20,10 @@ from coivo_amd import build  # noqa: E402
 
 def count(src: str, pat: str = "."):
     """[(mangled kernel name, MFMAs, MFMAs right behind a full LDS drain)] for the kernels of coivo_amd/csrc/<src> matching `pat`."""
-    out = f"/tmp/{src[:-4]}.s"
-    build.emit_asm(src, out)
-    t = open(out).read()
+    with tempfile.TemporaryDirectory() as d:          # (a fixed path under /tmp may belong to another user)
+        out = os.path.join(d, src[:-4] + ".s")
+        build.emit_asm(src, out)
+        t = open(out).read()
     res = []
     for m in re.finditer(r"^(_Z\S+):\s*; @", t, flags=re.M):
         name = m.group(1)
