@@ -666,6 +666,7 @@ int colvo::launch_dgrad_planes_s2_mfma(const void* g, const float* w, int Cin, i
     k.groups_per_wave = std::max((int)TUNE(planes_groups), (k.ngroups + 4 * 2048 - 1) / (4 * 2048));
     const int wgs = (k.ngroups + 4 * k.groups_per_wave - 1) / (4 * k.groups_per_wave);
     colvo::launch(k_dgrad_planes_s2_mfma, dim3((unsigned)wgs), dim3(NT), 0, stream, k);
+    COLVO_CHECK_LAUNCH("k_dgrad_planes_s2_mfma");
     return 0;
 }
 

@@ -6,6 +6,9 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <atomic>
+#include <mutex>
+
 #include "../../include/colvo.h"
 
 namespace colvo {
@@ -51,6 +54,22 @@ inline void launch(void (*kernel)(P...), dim3 grid, dim3 block, unsigned lds, hi
     } else {
         hipLaunchKernelGGL(kernel, grid, block, lds, s, static_cast<P>(a)...);
     }
+}
+
+// Dynamic-LDS opt-in: a launch of `Kernel` asks for `lds` bytes; above the default 48 KB the kernel must first be allowed `limit`
+// bytes (its MaxDynamicSharedMemorySize attribute), once per kernel and process.  Safe under concurrent callers; once the
+// attribute is set, a call is one atomic load.
+template <auto Kernel>
+inline int allow_dynamic_lds(size_t lds, int limit, const char* who) {
+    static std::atomic<bool> done{false};
+    if (lds <= 48 * 1024 || done.load(std::memory_order_acquire)) return 0;
+    static std::mutex mu;
+    std::lock_guard<std::mutex> lock(mu);
+    if (done.load(std::memory_order_relaxed)) return 0;
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, limit);
+    if (e != hipSuccess) { set_error("%s: dynamic LDS opt-in failed: %s", who, hipGetErrorString(e)); return (int)e; }
+    done.store(true, std::memory_order_release);
+    return 0;
 }
 
 // Which kernel FORM a dispatcher chose, counted per process (colvo_form_counts: the tests of the grid-size-selected forms read it --

@@ -1384,6 +1384,16 @@ __global__ __launch_bounds__(NT) void k_conv3x3_res(const ConvK a, int ntiles, u
 // --------------------------------------------------------------------------------------------- //
 // host side                                                                                      //
 // --------------------------------------------------------------------------------------------- //
+// one launch of a one-tile kernel over the grid of tile_grid
+template <auto Kernel>
+int launch_tiles(ConvK k, int BN, int B, int nthreads, size_t lds, hipStream_t s, const char* name) {
+    const long long nwg = tile_grid(k, BN, B);
+    COLVO_CHECK_ARG(nwg < (1ll << 30), "%s: too many workgroups", name);
+    colvo::launch(Kernel, dim3((unsigned)nwg), dim3(nthreads), lds, s, k);
+    COLVO_CHECK_LAUNCH(name);
+    return 0;
+}
+
 template <typename T, int BN, int NG, int DEPTH, bool TAIL, int NCH = 0, int NTH = 256>
 int launch_conv_tail(const ConvK& k, int B, hipStream_t s) {
     constexpr int STEPS = (9 * NG + 3) / 4;
@@ -1394,35 +1404,22 @@ int launch_conv_tail(const ConvK& k, int B, hipStream_t s) {
     const size_t eplds = (size_t)(NTH / 2) * (BN + 4) * 4;
     if (eplds > lds) lds = eplds;
     COLVO_CHECK_ARG(lds <= 160 * 1024, "conv: tile needs %zu bytes of LDS", lds);
-    static size_t configured = 0;   // per instantiation
-    if (lds > 48 * 1024 && lds > configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3x3<T, BN, NG, DEPTH, TAIL, NCH, NTH>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) { set_error("conv: hipFuncSetAttribute failed: %s", hipGetErrorString(e)); return (int)e; }
-        configured = 160 * 1024;
-    }
-    const int xcd_on = (int)TUNE(xcd_remap);
-    ConvK kk = k;
-    kk.ntn = (k.N + BN - 1) / BN;
-    kk.xcd = xcd_on;
-    const long long nwg_ll = (long long)k.tiles_x * k.tiles_y * kk.ntn * B;
-    COLVO_CHECK_ARG(nwg_ll < (1ll << 30), "conv: too many workgroups");
-    dim3 grid((unsigned)nwg_ll, 1, 1);
+    if (int e = allow_dynamic_lds<k_conv3x3<T, BN, NG, DEPTH, TAIL, NCH, NTH>>(lds, 160 * 1024, "conv")) return e;
 #ifdef COLVO_ABLATE
-    ConvK ka = kk;
+    ConvK ka = k;
     { const char* e = getenv("COLVO_ABL"); ka.abl = e ? atoi(e) : 0; }
     ka.trace = nullptr;
     static long long* tbuf = nullptr;
     static int tcount = 0;
-    const size_t nwg = (size_t)grid.x * grid.y * grid.z;
+    const dim3 grid((unsigned)tile_grid(ka, BN, B));
+    const size_t nwg = grid.x;
     const bool tracing = getenv("COLVO_TRACE") && nwg <= (1u << 16);
     if (tracing) {
         if (!tbuf) hipMalloc(&tbuf, (size_t)(1u << 16) * 8 * sizeof(long long));
         hipMemsetAsync(tbuf, 0, nwg * 8 * sizeof(long long), s);
         ka.trace = tbuf;
     }
-    colvo::launch((k_conv3x3<T, BN, NG, DEPTH, TAIL, NCH, NTH>), grid, dim3(NTH), lds, s, ka);
-    COLVO_CHECK_LAUNCH("k_conv3x3");
+    if (int e = launch_tiles<k_conv3x3<T, BN, NG, DEPTH, TAIL, NCH, NTH>>(ka, BN, B, NTH, lds, s, "k_conv3x3")) return e;
     if (tracing && (++tcount % atoi(getenv("COLVO_TRACE"))) == 0) {     // every n-th launch: print the phase statistics
         hipStreamSynchronize(s);
         std::vector<long long> h(nwg * 8);
@@ -1445,9 +1442,7 @@ int launch_conv_tail(const ConvK& k, int B, hipStream_t s) {
     }
     return 0;
 #endif
-    colvo::launch((k_conv3x3<T, BN, NG, DEPTH, TAIL, NCH, NTH>), grid, dim3(NTH), lds, s, kk);
-    COLVO_CHECK_LAUNCH("k_conv3x3");
-    return 0;
+    return launch_tiles<k_conv3x3<T, BN, NG, DEPTH, TAIL, NCH, NTH>>(k, BN, B, NTH, lds, s, "k_conv3x3");
 }
 
 template <typename T, int BN, int NG, int DEPTH = 1>
@@ -1475,13 +1470,7 @@ int launch_conv_res(const ConvK& k, int B, hipStream_t s) {
     const size_t p_or_out = std::max((size_t)PH * k.pwp * PIXP, (size_t)BM * (BN + 4) * 4);
     const size_t lds = (size_t)BN * WROW + p_or_out;
     COLVO_CHECK_ARG(lds <= 160 * 1024, "conv (weights-resident): tile needs %zu bytes of LDS", lds);
-    static bool configured = false;             // per instantiation
-    if (lds > 48 * 1024 && !configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3x3_res<T, BN, NG, S2>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) { set_error("conv: hipFuncSetAttribute failed: %s", hipGetErrorString(e)); return (int)e; }
-        configured = true;
-    }
+    if (int e = allow_dynamic_lds<k_conv3x3_res<T, BN, NG, S2>>(lds, 160 * 1024, "conv")) return e;
     const int ntiles = k.tiles_x * k.tiles_y * B;
     // workgroups per CU, each walking ntiles / gx tiles (stride 2: as many as its LDS footprint lets a CU hold)
     const int per_cu = S2 ? std::max(1, std::min((int)TUNE(res_wg_per_cu), (int)(160 * 1024 / lds))) : (int)TUNE(res_wg_per_cu);
@@ -1564,13 +1553,10 @@ int launch_conv_ng(const ConvK& k, int B, int ng, hipStream_t s) {
 }
 
 inline void set_tile(ConvK& k, const Tile& t) {
-    k.toh = t.toh; k.tow = t.tow;
-    k.tiles_x = (k.Wo + t.tow - 1) / t.tow; k.tiles_y = (k.Ho + t.toh - 1) / t.toh;
-    k.m_tow = mdiv_magic(t.tow); k.m_pw = mdiv_magic((t.tow - 1) * k.g.stride + 3);
     const int pw = (t.tow - 1) * k.g.stride + 3;
-    k.pwp = t.pwp > pw ? t.pwp : pw;
     // patches beyond 3 x 256 granules are staged partly by the linear tail loop: no row padding there
-    if ((long)((t.toh - 1) * k.g.stride + 3) * pw * 4 > 3 * NT) k.pwp = pw;
+    const bool tail = (long)((t.toh - 1) * k.g.stride + 3) * pw * 4 > 3 * NT;
+    apply_tile(k, t, pw, tail ? pw : std::max(t.pwp, pw));
 }
 
 template <typename T, int BN>
@@ -1648,13 +1634,9 @@ int try_launch_conv_q(const ConvK& k0, int B, hipStream_t s) {
     const Tile t = pick_tile((k.Ho + 1) / 2, (k.Wo + 1) / 2, 1, false, 128, true, 3);   // the sub-tile: at most half the image each way
     const int PH = 2 * t.toh + 2, PW = 2 * t.tow + 2;
     if (PH * PW * 4 > 10 * NT) return -1;
-    k.toh = t.toh; k.tow = t.tow;
-    k.tiles_x = (k.Wo + 2 * t.tow - 1) / (2 * t.tow); k.tiles_y = (k.Ho + 2 * t.toh - 1) / (2 * t.toh);
-    k.m_tow = mdiv_magic(t.tow); k.m_pw = mdiv_magic(PW);
-    k.pwp = PW;
     // sub-tile reads are conflict-free when the sub-tile's own rows are (pick_tile) AND the patch pitch keeps the row phase:
     // keep the padding pick_tile chose relative to ITS patch width (tow + 2)
-    if (t.pwp > t.tow + 2) k.pwp = PW + (t.pwp - (t.tow + 2));
+    apply_tile(k, t, PW, PW + std::max(0, t.pwp - (t.tow + 2)), 2);
     const long tiles = (long)k.tiles_x * k.tiles_y * B;
     const int bn = (k.N > 16 && tiles * ((k.N + 31) / 32) >= min_wgs) ? 32 : 16;
     k.ntn = (k.N + bn - 1) / bn;
@@ -1664,13 +1646,8 @@ int try_launch_conv_q(const ConvK& k0, int B, hipStream_t s) {
     constexpr int WROW = wrow_bytes(36), PIXP = pitch_bytes(64);
     const size_t lds = (size_t)bn * WROW + (size_t)PH * k.pwp * PIXP;
     if (lds > 160 * 1024) return -1;
-    static bool configured[2] = {false, false};
-    if (lds > 48 * 1024 && !configured[bn == 32]) {
-        const void* f = bn == 32 ? reinterpret_cast<const void*>(&k_conv_q<T, 32>) : reinterpret_cast<const void*>(&k_conv_q<T, 16>);
-        hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) { set_error("conv: hipFuncSetAttribute failed: %s", hipGetErrorString(e)); return (int)e; }
-        configured[bn == 32] = true;
-    }
+    if (int e = bn == 32 ? allow_dynamic_lds<k_conv_q<T, 32>>(lds, 160 * 1024, "conv") : allow_dynamic_lds<k_conv_q<T, 16>>(lds, 160 * 1024, "conv"))
+        return e;
     const dim3 grid((unsigned)(tiles * k.ntn));
     form_hit(FORM_CONV_Q);
     if (bn == 32) colvo::launch((k_conv_q<T, 32>), grid, dim3(NT), lds, s, k);
@@ -1681,17 +1658,11 @@ int try_launch_conv_q(const ConvK& k0, int B, hipStream_t s) {
 
 // forward over an up-sampled source (k_conv_up2): tiles over the stored half-size source
 template <typename T, int BN, int DEPTH, int NCH>
-int launch_conv_up2_inst(ConvK k, int B, hipStream_t s) {
+int launch_conv_up2_inst(const ConvK& k, int B, hipStream_t s) {
     constexpr int WROW = wrow_bytes(36), PIXP = pitch_bytes(64);
     const size_t lds = (size_t)BN * WROW + (size_t)(k.toh + 2) * k.pwp * PIXP;
-    const int xcd_on = (int)TUNE(xcd_remap);
-    k.ntn = (k.N + BN - 1) / BN;
-    k.xcd = xcd_on;
-    const long long nwg = (long long)k.tiles_x * k.tiles_y * k.ntn * B;
-    COLVO_CHECK_ARG(nwg < (1ll << 30) && lds <= 48 * 1024, "conv (up-sampled source): bad launch geometry");
-    colvo::launch((k_conv_up2<T, BN, DEPTH, NCH>), dim3((unsigned)nwg), dim3(NT), lds, s, k);
-    COLVO_CHECK_LAUNCH("k_conv_up2");
-    return 0;
+    COLVO_CHECK_ARG(lds <= 48 * 1024, "conv (up-sampled source): tile needs %zu bytes of LDS", lds);
+    return launch_tiles<k_conv_up2<T, BN, DEPTH, NCH>>(k, BN, B, NT, lds, s, "k_conv_up2");
 }
 
 template <typename T, int BN>
@@ -1704,25 +1675,12 @@ int launch_conv_up2_bn(const ConvK& k, int B, hipStream_t s) {
 
 // input gradient w.r.t. an up-sampled source (k_dgrad_up2): tiles over the half-size source
 template <typename T, int BN, int DEPTH, int NCH, int NG = 4>
-int launch_dgrad_up2_inst(ConvK k, int B, hipStream_t s) {
+int launch_dgrad_up2_inst(const ConvK& k, int B, hipStream_t s) {
     constexpr int WROW = wrow_bytes((9 * NG + 3) / 4 * 4), PIXP = pitch_bytes(NG * 16);
     const size_t lds = (size_t)BN * WROW + (size_t)(2 * k.toh + 2) * k.pwp * PIXP;
     COLVO_CHECK_ARG(lds <= 160 * 1024, "dgrad (up-sampled source): tile needs %zu bytes of LDS", lds);
-    static size_t configured = 0;
-    if (lds > 48 * 1024 && lds > configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_dgrad_up2<T, BN, DEPTH, NCH, NG>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) { set_error("dgrad: hipFuncSetAttribute failed: %s", hipGetErrorString(e)); return (int)e; }
-        configured = 160 * 1024;
-    }
-    const int xcd_on = (int)TUNE(xcd_remap);
-    k.ntn = (k.N + BN - 1) / BN;
-    k.xcd = xcd_on;
-    const long long nwg = (long long)k.tiles_x * k.tiles_y * k.ntn * B;
-    COLVO_CHECK_ARG(nwg < (1ll << 30), "dgrad (up-sampled source): too many workgroups");
-    colvo::launch((k_dgrad_up2<T, BN, DEPTH, NCH, NG>), dim3((unsigned)nwg), dim3(NT), lds, s, k);
-    COLVO_CHECK_LAUNCH("k_dgrad_up2");
-    return 0;
+    if (int e = allow_dynamic_lds<k_dgrad_up2<T, BN, DEPTH, NCH, NG>>(lds, 160 * 1024, "dgrad")) return e;
+    return launch_tiles<k_dgrad_up2<T, BN, DEPTH, NCH, NG>>(k, BN, B, NT, lds, s, "k_dgrad_up2");
 }
 
 template <typename T, int BN>
@@ -1736,17 +1694,11 @@ int launch_dgrad_up2_bn(const ConvK& k, int B, hipStream_t s) {
 
 // parity-decomposed stride-2 input gradient (k_dgrad_s2): tiles over dy, four output pixels per tile position
 template <typename T, int BN, int DEPTH, int NCH>
-int launch_dgrad_s2_inst(ConvK k, int B, hipStream_t s) {
+int launch_dgrad_s2_inst(const ConvK& k, int B, hipStream_t s) {
     constexpr int WROW = wrow_bytes(36), PIXP = pitch_bytes(64);
     const size_t lds = (size_t)BN * WROW + (size_t)(k.toh + 1) * k.pwp * PIXP;
-    const int xcd_on = (int)TUNE(xcd_remap);
-    k.ntn = (k.N + BN - 1) / BN;
-    k.xcd = xcd_on;
-    const long long nwg = (long long)k.tiles_x * k.tiles_y * k.ntn * B;
-    COLVO_CHECK_ARG(nwg < (1ll << 30) && lds <= 48 * 1024, "dgrad (stride 2): bad launch geometry");
-    colvo::launch((k_dgrad_s2<T, BN, DEPTH, NCH>), dim3((unsigned)nwg), dim3(NT), lds, s, k);
-    COLVO_CHECK_LAUNCH("k_dgrad_s2");
-    return 0;
+    COLVO_CHECK_ARG(lds <= 48 * 1024, "dgrad (stride 2): tile needs %zu bytes of LDS", lds);
+    return launch_tiles<k_dgrad_s2<T, BN, DEPTH, NCH>>(k, BN, B, NT, lds, s, "k_dgrad_s2");
 }
 
 template <typename T, int BN>
@@ -1764,10 +1716,26 @@ int launch_dgrad_s2_bn(const ConvK& k, int B, hipStream_t s) {
 template <typename T>
 int launch_dgrad_s2(ConvK k, int B, hipStream_t s) {
     const Tile t = pick_tile(k.Ho, k.Wo, 1, false, 128, true, 2);
-    k.toh = t.toh; k.tow = t.tow; k.pwp = std::max(t.pwp, t.tow + 1);
-    k.tiles_x = (k.Wo + t.tow - 1) / t.tow; k.tiles_y = (k.Ho + t.toh - 1) / t.toh;
-    k.m_tow = mdiv_magic(t.tow); k.m_pw = mdiv_magic(t.tow + 1);
+    apply_tile(k, t, t.tow + 1, std::max(t.pwp, t.tow + 1));
     return k.N > 16 ? launch_dgrad_s2_bn<T, 32>(k, B, s) : launch_dgrad_s2_bn<T, 16>(k, B, s);
+}
+
+// Input gradient as a conv: dy (Cout channels) is the single direct source, the weights are the rows of w_bwd from input channel
+// coff on, N output channels go to dx (masked by relu_mask).  Tiles and output run over dy's extent; the callers change that.
+inline ConvK dgrad_conv(const ColvoConvDesc* d, const void* dy, const void* w_bwd, int coff, int N, void* dx, const void* relu_mask,
+                        int accumulate) {
+    const int es = d->dtype == COLVO_F32 ? 4 : 2;
+    ConvK k{};
+    k.g.src[0] = (const char*)dy; k.g.src[1] = nullptr;
+    k.g.C[0] = d->Cout; k.g.C[1] = 0;
+    k.g.Hs[0] = d->Ho; k.g.Ws[0] = d->Wo; k.g.Hs[1] = k.g.Ws[1] = 0;
+    k.g.mode[0] = k.g.mode[1] = MODE_DIRECT;
+    k.g.Hi = d->Ho; k.g.Wi = d->Wo; k.g.stride = 1;
+    k.Ho = d->Ho; k.Wo = d->Wo;
+    k.w = (const char*)w_bwd + (size_t)coff * 9 * d->Cout * es; k.Ctot = d->Cout; k.N = N;
+    k.bias = nullptr; k.relu = 0; k.out = (char*)dx; k.mask = (const char*)relu_mask;
+    k.accumulate = accumulate; k.pool2 = 0;
+    return k;
 }
 
 }  // namespace
@@ -1799,9 +1767,7 @@ extern "C" int colvo_conv_fwd(const ColvoConvDesc* d, const void* x0, const void
             u.Ho = d->Hi / 2; u.Wo = d->Wi / 2;           // tiles run over source positions; the kernel writes (2 Ho) x (2 Wo)
             const Tile t = pick_tile(u.Ho, u.Wo, 1, false, 128, true, 3);
             if ((t.toh + 2) * (t.tow + 2) * 4 <= 3 * NT) {
-                u.toh = t.toh; u.tow = t.tow; u.pwp = std::max(t.pwp, t.tow + 2);
-                u.tiles_x = (u.Wo + t.tow - 1) / t.tow; u.tiles_y = (u.Ho + t.toh - 1) / t.toh;
-                u.m_tow = mdiv_magic(t.tow); u.m_pw = mdiv_magic(t.tow + 2);
+                apply_tile(u, t, t.tow + 2, std::max(t.pwp, t.tow + 2));
                 hipStream_t s = (hipStream_t)stream;
                 // 16-wide channel tiles while 32-wide ones would leave CUs without a workgroup
                 const long bn16_max = TUNE(up2_bn16_max_wgs);   // tuning knob
@@ -1834,7 +1800,6 @@ extern "C" int colvo_conv_dgrad(const ColvoConvDesc* d, int src, const void* dy,
     const int Csrc = src == 0 ? d->C0 : d->C1;
     const int coff = src == 0 ? 0 : d->C0;
     const int up = src == 0 ? d->up0 : d->up1;
-    ConvK k{};
     {
         // stride 2, even input extent, 32-channel chunks of dy: the parity-decomposed kernel (a quarter of the MFMAs)
         const int s2_on = (int)TUNE(dgrad_s2);
@@ -1842,15 +1807,8 @@ extern "C" int colvo_conv_dgrad(const ColvoConvDesc* d, int src, const void* dy,
         const long long out_bytes = (long long)d->Hi * d->Wi * Csrc * es, in_bytes = (long long)d->Ho * d->Wo * d->Cout * es;
         if (s2_on && d->stride == 2 && !up && d->Hi == 2 * d->Ho && d->Wi == 2 * d->Wo && d->Cout % ck == 0 &&
             out_bytes < 0x40000000LL && in_bytes < 0x40000000LL) {
-            k.g.src[0] = (const char*)dy; k.g.src[1] = nullptr;
-            k.g.C[0] = d->Cout; k.g.C[1] = 0;
-            k.g.Hs[0] = d->Ho; k.g.Ws[0] = d->Wo; k.g.Hs[1] = k.g.Ws[1] = 0;
-            k.g.mode[0] = k.g.mode[1] = MODE_DIRECT;
-            k.g.Hi = d->Ho; k.g.Wi = d->Wo; k.g.stride = 1;
-            k.Ho = d->Ho; k.Wo = d->Wo;                // tiles run over dy; the kernel writes a (2 Ho) x (2 Wo) image
-            k.w = (const char*)w_bwd + (size_t)coff * 9 * d->Cout * es; k.Ctot = d->Cout; k.N = Csrc;
-            k.bias = nullptr; k.relu = 0; k.out = (char*)dx; k.mask = (const char*)relu_mask;
-            k.accumulate = accumulate; k.pool2 = 0;
+            // tiles run over dy; the kernel writes a (2 Ho) x (2 Wo) image
+            const ConvK k = dgrad_conv(d, dy, w_bwd, coff, Csrc, dx, relu_mask, accumulate);
             return d->dtype == COLVO_F32 ? launch_dgrad_s2<float>(k, d->B, (hipStream_t)stream)
                                          : launch_dgrad_s2<bf16_t>(k, d->B, (hipStream_t)stream);
         }
@@ -1861,21 +1819,11 @@ extern "C" int colvo_conv_dgrad(const ColvoConvDesc* d, int src, const void* dy,
         const int ck = d->dtype == COLVO_F32 ? 16 : 32;
         const long long out_bytes = (long long)(d->Hi / 2) * (d->Wi / 2) * Csrc * es, in_bytes = (long long)d->Ho * d->Wo * d->Cout * es;
         if (up2_on && up && d->stride == 1 && d->Cout % (ck / 2) == 0 && out_bytes < 0x40000000LL && in_bytes < 0x40000000LL) {
-            ConvK u{};
-            u.g.src[0] = (const char*)dy; u.g.src[1] = nullptr;
-            u.g.C[0] = d->Cout; u.g.C[1] = 0;
-            u.g.Hs[0] = d->Ho; u.g.Ws[0] = d->Wo; u.g.Hs[1] = u.g.Ws[1] = 0;
-            u.g.mode[0] = u.g.mode[1] = MODE_DIRECT;
-            u.g.Hi = d->Ho; u.g.Wi = d->Wo; u.g.stride = 1;
+            ConvK u = dgrad_conv(d, dy, w_bwd, coff, Csrc, dx, relu_mask, accumulate);
             u.Ho = d->Hi / 2; u.Wo = d->Wi / 2;          // tiles and output: the stored half-size source
-            u.w = (const char*)w_bwd + (size_t)coff * 9 * d->Cout * es; u.Ctot = d->Cout; u.N = Csrc;
-            u.bias = nullptr; u.relu = 0; u.out = (char*)dx; u.mask = (const char*)relu_mask;
-            u.accumulate = accumulate; u.pool2 = 0;
             const Tile t = pick_tile(u.Ho, u.Wo, 2, false, 128, true, 4);   // patch rows of 2 tow + 2 pixels, pixel stride 2
             if ((2 * t.toh + 2) * (2 * t.tow + 2) * 4 <= 10 * NT) {                 // (x NG / 4 granules <= PPF x 256 for either NG)
-                u.toh = t.toh; u.tow = t.tow; u.pwp = std::max(t.pwp, 2 * t.tow + 2);
-                u.tiles_x = (u.Wo + t.tow - 1) / t.tow; u.tiles_y = (u.Ho + t.toh - 1) / t.toh;
-                u.m_tow = mdiv_magic(t.tow); u.m_pw = mdiv_magic(2 * t.tow + 2);
+                apply_tile(u, t, 2 * t.tow + 2, std::max(t.pwp, 2 * t.tow + 2));
                 hipStream_t s = (hipStream_t)stream;
                 // only where the grid still covers the chip: at batch 16 the 1/8- and 1/16-resolution layers measured 1-2 us
                 // SLOWER in this form (up5 19.4 -> 21.0, up4 18.2 -> 19.4; up3 20.7 -> 19.4, up2 26.8 -> 19.1)
@@ -1891,17 +1839,10 @@ extern "C" int colvo_conv_dgrad(const ColvoConvDesc* d, int src, const void* dy,
         }
     }
     // the conv input is dy (Cout channels), dilated by zero insertion when the forward stride was 2
-    k.g.src[0] = (const char*)dy; k.g.src[1] = nullptr;
-    k.g.C[0] = d->Cout; k.g.C[1] = 0;
-    k.g.Hs[0] = d->Ho; k.g.Ws[0] = d->Wo; k.g.Hs[1] = k.g.Ws[1] = 0;
-    k.g.mode[0] = d->stride == 2 ? MODE_DILATE : MODE_DIRECT; k.g.mode[1] = MODE_DIRECT;
-    k.g.Hi = d->stride == 2 ? 2 * d->Ho : d->Ho;
-    k.g.Wi = d->stride == 2 ? 2 * d->Wo : d->Wo;
-    k.g.stride = 1;
+    ConvK k = dgrad_conv(d, dy, w_bwd, coff, Csrc, dx, relu_mask, accumulate);
+    if (d->stride == 2) { k.g.mode[0] = MODE_DILATE; k.g.Hi = 2 * d->Ho; k.g.Wi = 2 * d->Wo; }
     k.Ho = d->Hi; k.Wo = d->Wi;                    // gradient w.r.t. the (virtual) forward input
-    k.w = (const char*)w_bwd + (size_t)coff * 9 * d->Cout * es; k.Ctot = d->Cout; k.N = Csrc;
-    k.bias = nullptr; k.relu = 0; k.out = (char*)dx; k.mask = (const char*)relu_mask;
-    k.accumulate = accumulate; k.pool2 = up;
+    k.pool2 = up;
     if (d->stride == 1 && !up) {
         int r = try_launch_conv_rt(k, d->B, d->dtype, (hipStream_t)stream);
         if (r >= 0) return r;
@@ -1930,16 +1871,8 @@ extern "C" int colvo_conv_dgrad_both(const ColvoConvDesc* d, const void* dy, con
         if (int e = colvo_conv_dgrad(d, 0, dy, w_bwd, relu_mask0, dx0, 0, stream)) return e;
         return colvo_conv_dgrad(d, 1, dy, w_bwd, relu_mask1, dx1, 0, stream);
     }
-    ConvK k{};
-    k.g.src[0] = (const char*)dy; k.g.src[1] = nullptr;
-    k.g.C[0] = d->Cout; k.g.C[1] = 0;
-    k.g.Hs[0] = d->Ho; k.g.Ws[0] = d->Wo; k.g.Hs[1] = k.g.Ws[1] = 0;
-    k.g.mode[0] = k.g.mode[1] = MODE_DIRECT;
-    k.g.Hi = d->Ho; k.g.Wi = d->Wo; k.g.stride = 1;
+    ConvK k = dgrad_conv(d, dy, w_bwd, 0, d->C0 + d->C1, dx0, relu_mask0, 0);
     k.Ho = d->Hi; k.Wo = d->Wi;
-    k.w = (const char*)w_bwd; k.Ctot = d->Cout; k.N = d->C0 + d->C1;
-    k.bias = nullptr; k.relu = 0; k.accumulate = 0; k.pool2 = 0;
-    k.out = (char*)dx0; k.mask = (const char*)relu_mask0;
     k.out2 = (char*)dx1; k.mask2 = (const char*)relu_mask1; k.nsplit = d->C0;
     {
         const int r = try_launch_conv_rt(k, d->B, d->dtype, (hipStream_t)stream);

@@ -361,5 +361,21 @@ void fill_gather(const ColvoConvDesc* d, const void* x0, const void* x1, Gather&
     g.Hi = d->Hi; g.Wi = d->Wi; g.stride = d->stride;
 }
 
+// Put tile t on k: patch rows of pw pixels, staged in LDS at a pitch of pwp pixels; one tile position covers cover x cover tiles
+// (the quad-tile kernel: 2)
+inline void apply_tile(ConvK& k, const Tile& t, int pw, int pwp, int cover = 1) {
+    k.toh = t.toh; k.tow = t.tow;
+    k.tiles_x = (k.Wo + cover * t.tow - 1) / (cover * t.tow); k.tiles_y = (k.Ho + cover * t.toh - 1) / (cover * t.toh);
+    k.m_tow = mdiv_magic(t.tow); k.m_pw = mdiv_magic(pw);
+    k.pwp = pwp;
+}
+
+// 1-D grid of a one-tile kernel: tiles_x x tiles_y x B pixel tiles, each with ceil(N / BN) output-channel tiles (n-tile fastest)
+inline long long tile_grid(ConvK& k, int BN, int B) {
+    k.ntn = (k.N + BN - 1) / BN;
+    k.xcd = (int)TUNE(xcd_remap);
+    return (long long)k.tiles_x * k.tiles_y * k.ntn * B;
+}
+
 }  // namespace
 }  // namespace colvo

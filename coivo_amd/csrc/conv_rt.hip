@@ -324,13 +324,7 @@ int launch_conv_rt(ConvK k, long long ntiles, hipStream_t s) {
     constexpr int BN = 16 * NF;
     constexpr size_t lds = (size_t)BN * wrow_bytes(36) + (size_t)RT_PH * RT_PW * pitch_bytes(64);
     static_assert(lds <= 80 * 1024, "k_conv_rt: two workgroups per CU need <= 80 KB of LDS each");
-    static bool configured = false;        // per instantiation
-    if (lds > 48 * 1024 && !configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv_rt<T, NF>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)lds);
-        if (e != hipSuccess) { set_error("conv (register-tiled): hipFuncSetAttribute failed: %s", hipGetErrorString(e)); return (int)e; }
-        configured = true;
-    }
+    if (int e = allow_dynamic_lds<k_conv_rt<T, NF>>(lds, (int)lds, "conv (register-tiled)")) return e;
     // one tile per workgroup by default; rt_wgs_per_cu > 0: a persistent grid (256 CUs x n, + 1 for the 32-channel form), every
     // workgroup walking the same number of consecutive tiles (tuning.h has the measurement that keeps it off)
     const long per_cu = TUNE(rt_wgs_per_cu) > 0 ? TUNE(rt_wgs_per_cu) + (NF == 2 ? 1 : 0) : 0;
@@ -359,19 +353,14 @@ int try_launch_conv_rt(const ConvK& k0, int B, int dtype, hipStream_t s) {
     if ((long long)B * g.Hi * g.Wi * std::max(g.C[0], g.C[1]) * es >= 0x40000000LL || (long long)B * k0.Ho * k0.Wo * k0.N * es >= 0x40000000LL)
         return -1;
     ConvK k = k0;
-    k.toh = RT_TH; k.tow = RT_TW; k.pwp = RT_PW;
-    k.tiles_x = (k.Wo + RT_TW - 1) / RT_TW; k.tiles_y = (k.Ho + RT_TH - 1) / RT_TH;
-    k.m_tow = mdiv_magic(RT_TW); k.m_pw = mdiv_magic(RT_PW);
+    apply_tile(k, Tile{RT_TH, RT_TW, RT_PW}, RT_PW, RT_PW);
     // the 16 x 16 tiling must not waste much of the image (a 32 x 40 map computes 1.2 x its pixels, a 16 x 20 map 1.6 x)
     const long long covered = (long long)k.tiles_x * k.tiles_y * RT_TH * RT_TW;
     if ((long long)k.Ho * k.Wo * 100 < covered * TUNE(rt_min_fill_pct)) return -1;
     // 64-wide channel tiles where the layer has them (two-output form: a tile must not straddle the two sources)
     const bool bn64 = k.N >= 64 && (k.nsplit == 0 || k.nsplit % 64 == 0);
     if (k.nsplit % 32 != 0) return -1;
-    const int bn = bn64 ? 64 : 32;
-    k.ntn = (k.N + bn - 1) / bn;
-    k.xcd = (int)TUNE(xcd_remap);
-    const long long nwg = (long long)k.tiles_x * k.tiles_y * B * k.ntn;
+    const long long nwg = tile_grid(k, bn64 ? 64 : 32, B);
     if (nwg < (bn64 ? TUNE(rt_min_wgs) : TUNE(rt_bn32_min_wgs)) || nwg >= (1ll << 30)) return -1;
     form_hit(FORM_CONV_RT);
     if (dtype == COLVO_F32) return bn64 ? launch_conv_rt<float, 4>(k, nwg, s) : launch_conv_rt<float, 2>(k, nwg, s);

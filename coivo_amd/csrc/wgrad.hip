@@ -610,126 +610,6 @@ inline int wgrad_finish(const WgradK& k, int nsplit, hipStream_t s) {
     return 0;
 }
 
-// The floor of a weight-gradient grid: `base` workgroups (tuning: wgrad_wg_lo / wgrad_team_wgs), but HALF of that while a workgroup of
-// the full grid would walk fewer than wgrad_short_walk pixel tiles.  A workgroup's fixed costs -- 2 us of set-up and first loads, 6-7 us
-// of fp32 atomics at the end (profiles/r4_wgrad_phases.md) -- are then most of its life; alone on the GPU the kernel is still fastest
-// with one workgroup per CU (what round 2-3 tuned for), but in the step three kernels share the CUs and the sum of workgroup lives is
-// what counts: 128 instead of 256 workgroups at 16 frames measured -2.8 % per step (1.3097 -> 1.2726 ms), 96 -> +1 %, 64 -> +9 %;
-// at 64 / 128 frames, where the walks are 4-8 times longer, halving every layer cost 0.4-0.5 %.
-static thread_local bool g_grid_halved = false;     // what the last wgrad_grid_floor() decided (colvo_form_counts)
-static inline int wgrad_grid_floor(int base, int ntiles, int per_split) {
-    const int short_walk = (int)TUNE(wgrad_short_walk);
-    const int nsplit_at_base = std::max(1, (base + per_split - 1) / per_split);
-    g_grid_halved = short_walk > 0 && ntiles / nsplit_at_base < short_walk;
-    return g_grid_halved ? std::max(1, base / 2) : base;
-}
-
-template <typename T, int MT, int NG, bool TAIL, int KS>
-int launch_wgrad_teams(WgradK k, hipStream_t s) {
-    constexpr int G = TT<T>::G;
-    constexpr int CK = NG * G, PIXP = TAIL ? pitch_bytes_s2(NG * 16) : pitch_bytes(NG * 16), DYP = dy_pitch<T, MT>();
-    constexpr int NFR = (9 * CK + 15) / 16, FPW = (NFR + 3) / 4;
-    const int S = k.g.stride;
-    const int PH = (k.toh - 1) * S + 3;
-    const size_t stage = ((size_t)BM * DYP + (size_t)PH * k.pwl * PIXP + 15) & ~(size_t)15;
-    const size_t lds = std::max(stage * KS, (size_t)MT * FPW * NT * 16 + (size_t)NT * KS * 4) + 64;   // staging | exchange slab + db
-    COLVO_CHECK_ARG(lds <= 160 * 1024, "wgrad: %d teams need %zu bytes of LDS", KS, lds);
-    static size_t configured = 0;
-    if (lds > 48 * 1024 && lds > configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_wgrad3x3<T, MT, NG, TAIL, KS>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) { set_error("wgrad: hipFuncSetAttribute failed: %s", hipGetErrorString(e)); return (int)e; }
-        configured = 160 * 1024;
-    }
-    const int chunks = (k.g.C[0] + k.g.C[1]) / CK;
-    const int cot = (k.Cout + 16 * MT - 1) / (16 * MT);
-    // one workgroup per CU (KS * 4 waves fill its SIMDs): as many pixel-range splits as keep the grid within 256
-    const int per_split = chunks * cot;
-    const int wg_target = wgrad_grid_floor((int)TUNE(wgrad_team_wgs), k.ntiles, per_split);
-    int nsplit = std::max(1, wg_target / per_split);
-    if (nsplit > k.ntiles) nsplit = k.ntiles;
-    k.tiles_per_split = (k.ntiles + nsplit - 1) / nsplit;
-    nsplit = (k.ntiles + k.tiles_per_split - 1) / k.tiles_per_split;
-    const int xcd_on = (int)TUNE(xcd_remap);
-    k.nsplit = nsplit; k.cot = cot; k.xcd = xcd_on;
-    { int err; if (wgrad_prepare(k, nsplit, &err)) return err; }
-    dim3 grid((unsigned)(nsplit * cot * chunks), 1, 1);
-#ifdef COLVO_WTRACE
-    wtrace_begin(k, grid.x, s);
-#endif
-    form_hit(g_grid_halved ? FORM_WGRAD_HALVED_GRID : FORM_WGRAD_FULL_GRID);
-    if (k.det == 2) form_hit(FORM_WGRAD_STORE_CLEAN);
-    colvo::launch((k_wgrad3x3<T, MT, NG, TAIL, KS>), grid, dim3(NT * KS), lds, s, k);
-    COLVO_CHECK_LAUNCH("k_wgrad3x3 (teams)");
-#ifdef COLVO_WTRACE
-    wtrace_end(k, grid.x, MT, NG, TAIL, KS, s);
-#endif
-    return wgrad_finish(k, nsplit, s);
-}
-
-template <typename T, int MT, int NG, bool TAIL>
-int launch_wgrad_tail(WgradK k, hipStream_t s) {
-    constexpr int G = TT<T>::G;
-    constexpr int CK = NG * G, PIXP = TAIL ? pitch_bytes_s2(NG * 16) : pitch_bytes(NG * 16), DYP = dy_pitch<T, MT>();
-    const int S = k.g.stride;
-    const int PH = (k.toh - 1) * S + 3, PW = k.pwl;
-    {
-        // Teams pay only on the two full-resolution layers (16 output channels: a one-fragment co tile, so the exchange is
-        // 20 KB per team, and one or two slabs in the (co tile, channel chunk) grid, so 256 workgroups walk 40-80 tiles each).
-        // Measured at batch 16, us: up1 47.8 -> 37.5, iconv1 38.5 -> 28.9; with 32-wide co tiles it loses (enc1b 30.7 -> 40.2,
-        // up2 / iconv2 32.8 -> 37.5) and everywhere else the walk is short and the per-workgroup costs decide: -1...+8
-        // (gpurun_out/r2_bench_conv_slabs*.log).  4 teams = 1024 threads, 128 registers per lane.
-        const int teams = (int)TUNE(wgrad_teams);          // tuning knob; 1 = off
-        const int max_slabs = (int)TUNE(wgrad_team_max_slabs);   // tuning knob
-        const int slabs = ((k.g.C[0] + k.g.C[1]) / CK) * ((k.Cout + 16 * MT - 1) / (16 * MT));
-        const size_t stage = ((size_t)BM * DYP + (size_t)PH * PW * PIXP + 15) & ~(size_t)15;
-        if constexpr (!TAIL && MT == 1)
-            if (teams >= 4 && slabs <= max_slabs && stage * 4 + 64 <= 160 * 1024) return launch_wgrad_teams<T, MT, NG, TAIL, 4>(k, s);
-    }
-    const size_t lds = (size_t)BM * DYP + (size_t)PH * PW * PIXP + 64;
-    COLVO_CHECK_ARG(lds <= 160 * 1024, "wgrad: tile needs %zu bytes of LDS", lds);
-    static size_t configured = 0;
-    if (lds > 48 * 1024 && lds > configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_wgrad3x3<T, MT, NG, TAIL>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) { set_error("wgrad: hipFuncSetAttribute failed: %s", hipGetErrorString(e)); return (int)e; }
-        configured = 160 * 1024;
-    }
-    const int chunks = (k.g.C[0] + k.g.C[1]) / CK;
-    const int cot = (k.Cout + 16 * MT - 1) / (16 * MT);
-    // Pixel-range splits: every split adds one fp32 atomic per weight (chip-wide ~1.3 TB/s of atomics), so cap
-    // the atomic traffic at ~3 MB per launch (re-tuned for the 32-wide co tile: 12 MB 592 us, 6 MB 575, 3 MB 566),
-    // but keep at least ~256 workgroups in flight and at most ~1024.
-    const double wbytes = (double)k.Cout * 9.0 * k.Ctot * 4.0;
-    const int per_split = chunks * cot;
-    const double atomic_budget = TUNE_F(wgrad_atomic_mb) * 1e6;
-    const int wg_lo = wgrad_grid_floor((int)TUNE(wgrad_wg_lo), k.ntiles, per_split);
-    const int wg_hi = (int)TUNE(wgrad_wg_hi);
-    int nsplit = (int)(atomic_budget / wbytes);
-    const int lo = (wg_lo + per_split - 1) / per_split, hi = (wg_hi + per_split - 1) / per_split;
-    if (nsplit > hi) nsplit = hi;
-    if (nsplit < lo) nsplit = lo;
-    if (nsplit > k.ntiles) nsplit = k.ntiles;
-    if (nsplit < 1) nsplit = 1;
-    k.tiles_per_split = (k.ntiles + nsplit - 1) / nsplit;
-    nsplit = (k.ntiles + k.tiles_per_split - 1) / k.tiles_per_split;
-    const int xcd_on = (int)TUNE(xcd_remap);
-    k.nsplit = nsplit; k.cot = cot; k.xcd = xcd_on;
-    { int err; if (wgrad_prepare(k, nsplit, &err)) return err; }
-    dim3 grid((unsigned)(nsplit * cot * chunks), 1, 1);
-#ifdef COLVO_WTRACE
-    wtrace_begin(k, grid.x, s);
-#endif
-    form_hit(g_grid_halved ? FORM_WGRAD_HALVED_GRID : FORM_WGRAD_FULL_GRID);
-    if (k.det == 2) form_hit(FORM_WGRAD_STORE_CLEAN);
-    colvo::launch((k_wgrad3x3<T, MT, NG, TAIL>), grid, dim3(NT), lds, s, k);
-    COLVO_CHECK_LAUNCH("k_wgrad3x3");
-#ifdef COLVO_WTRACE
-    wtrace_end(k, grid.x, MT, NG, TAIL, 1, s);
-#endif
-    return wgrad_finish(k, nsplit, s);
-}
-
 // --------------------------------------------------------------------------------------------- //
 // weight gradient of a conv over a nearest-2x UP-SAMPLED source: four output classes, 16 products   //
 // --------------------------------------------------------------------------------------------- //
@@ -1018,61 +898,103 @@ __global__ __launch_bounds__(NT) void k_wgrad_up2(const WgradK a) {
     }
 }
 
-template <typename T, int MT>
-int launch_wgrad_up2(WgradK k, hipStream_t s) {
-    constexpr int G = TT<T>::G, CK = 4 * G, PIXP = pitch_bytes(64), DYP = dy_pitch<T, MT>();
-    // staging buffers | the class exchange: 4 classes x 4 source taps x MT x CK/16 accumulator blocks of 64 lanes x 16 bytes
-    const size_t lds = std::max((size_t)4 * BM * DYP + (size_t)(k.toh + 2) * k.pwl * PIXP, (size_t)16 * MT * (CK / 16) * 64 * 16) + 64;
-    COLVO_CHECK_ARG(lds <= 160 * 1024, "wgrad (up-sampled source): tile needs %zu bytes of LDS", lds);
-    static size_t configured = 0;
-    if (lds > 48 * 1024 && lds > configured && !k.plan_out) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_wgrad_up2<T, MT>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) { set_error("wgrad: hipFuncSetAttribute failed: %s", hipGetErrorString(e)); return (int)e; }
-        configured = 160 * 1024;
-    }
-    const int chunks = k.g.C[0] / CK;
-    const int cot = (k.Cout + 16 * MT - 1) / (16 * MT);
+// --------------------------------------------------------------------------------------------- //
+// host side: the plan of a launch, then the launch                                               //
+// --------------------------------------------------------------------------------------------- //
+// The floor of a weight-gradient grid: `base` workgroups (tuning: wgrad_wg_lo / wgrad_team_wgs), but HALF of that while a workgroup of
+// the full grid would walk fewer than wgrad_short_walk pixel tiles.  A workgroup's fixed costs -- 2 us of set-up and first loads, 6-7 us
+// of fp32 atomics at the end (profiles/r4_wgrad_phases.md) -- are then most of its life; alone on the GPU the kernel is still fastest
+// with one workgroup per CU (what round 2-3 tuned for), but in the step three kernels share the CUs and the sum of workgroup lives is
+// what counts: 128 instead of 256 workgroups at 16 frames measured -2.8 % per step (1.3097 -> 1.2726 ms), 96 -> +1 %, 64 -> +9 %;
+// at 64 / 128 frames, where the walks are 4-8 times longer, halving every layer cost 0.4-0.5 %.
+struct GridFloor { int wgs; bool halved; };        // (halved: colvo_form_counts)
+static inline GridFloor wgrad_grid_floor(int base, int ntiles, int per_split) {
+    const int short_walk = (int)TUNE(wgrad_short_walk);
+    const int nsplit_at_base = std::max(1, (base + per_split - 1) / per_split);
+    const bool halved = short_walk > 0 && ntiles / nsplit_at_base < short_walk;
+    return {halved ? std::max(1, base / 2) : base, halved};
+}
+
+// Pixel-range splits of the one-team and up-sampled-source forms: every split adds one fp32 atomic per weight (chip-wide ~1.3 TB/s
+// of atomics), so cap the atomic traffic at ~3 MB per launch (re-tuned for the 32-wide co tile: 12 MB 592 us, 6 MB 575, 3 MB 566),
+// but keep at least ~256 workgroups in flight and at most ~1024.
+static inline int wgrad_atomic_splits(const WgradK& k, int per_split, bool& halved) {
     const double wbytes = (double)k.Cout * 9.0 * k.Ctot * 4.0;
-    const int per_split = chunks * cot;
+    const GridFloor lo_wgs = wgrad_grid_floor((int)TUNE(wgrad_wg_lo), k.ntiles, per_split);
+    halved = lo_wgs.halved;
     int nsplit = (int)(TUNE_F(wgrad_atomic_mb) * 1e6 / wbytes);
-    const int lo = (wgrad_grid_floor((int)TUNE(wgrad_wg_lo), k.ntiles, per_split) + per_split - 1) / per_split;
-    const int hi = ((int)TUNE(wgrad_wg_hi) + per_split - 1) / per_split;
+    const int lo = (lo_wgs.wgs + per_split - 1) / per_split, hi = ((int)TUNE(wgrad_wg_hi) + per_split - 1) / per_split;
     if (nsplit > hi) nsplit = hi;
     if (nsplit < lo) nsplit = lo;
+    return nsplit;
+}
+
+// Everything a weight-gradient launch needs, decided by wgrad_plan before any HIP call (plan-only calls stop after it)
+enum { WGRAD_RT, WGRAD_UP2, WGRAD_TEAMS, WGRAD_TAIL };
+struct WgradPlan {
+    int form;
+    int mt, ng;               // co tile of 16 MT channels, channel chunks of NG granules (k_wgrad_up2: 4)
+    bool tail;                // k_wgrad3x3<.., TAIL>; the teams form is KS = 4, MT = 1, no tail
+    size_t lds;
+    int nsplit;
+    unsigned nwg;
+    bool halved;              // the grid floor was halved (wgrad_grid_floor)
+    WgradRtPlan rt;           // WGRAD_RT: the register-tiled form's own plan (wgrad_rt.hip)
+};
+
+inline void set_wgrad_tile(WgradK& k, const Tile& t, int Ho, int Wo, int pw) {
+    k.toh = t.toh; k.tow = t.tow;
+    k.tiles_x = (Wo + t.tow - 1) / t.tow; k.tiles_y = (Ho + t.toh - 1) / t.toh;
+    k.ntiles = k.B * k.tiles_x * k.tiles_y;
+    k.m_tow = mdiv_magic(t.tow); k.m_pw = mdiv_magic(pw);
+    k.pwl = wgrad_row_pitch(pw, t.tow);
+}
+
+// the pixel-range splits evened out over the tiles; 1-D grid with (co tile, chunk) fastest
+inline void set_wgrad_grid(WgradK& k, WgradPlan& p, int nsplit, int cot, int chunks) {
     if (nsplit > k.ntiles) nsplit = k.ntiles;
     if (nsplit < 1) nsplit = 1;
     k.tiles_per_split = (k.ntiles + nsplit - 1) / nsplit;
-    nsplit = (k.ntiles + k.tiles_per_split - 1) / k.tiles_per_split;
-    k.nsplit = nsplit; k.cot = cot; k.xcd = (int)TUNE(xcd_remap);
-    { int err; if (wgrad_prepare(k, nsplit, &err)) return err; }
-    form_hit(FORM_WGRAD_UP2);
-    form_hit(g_grid_halved ? FORM_WGRAD_HALVED_GRID : FORM_WGRAD_FULL_GRID);
-    if (k.det == 2) form_hit(FORM_WGRAD_STORE_CLEAN);
-    colvo::launch((k_wgrad_up2<T, MT>), dim3((unsigned)(nsplit * cot * chunks)), dim3(NT), lds, s, k);
-    COLVO_CHECK_LAUNCH("k_wgrad_up2");
-    return wgrad_finish(k, nsplit, s);
-}
-
-template <typename T, int MT, int NG>
-int launch_wgrad(const WgradK& k, hipStream_t s) {
-    const int S = k.g.stride;
-    const long ptotal = (long)((k.toh - 1) * S + 3) * ((k.tow - 1) * S + 3) * NG;
-    if (ptotal > 3 * NT) return launch_wgrad_tail<T, MT, NG, true>(k, s);
-    return launch_wgrad_tail<T, MT, NG, false>(k, s);
-}
-
-template <typename T, int MT>
-int launch_wgrad_ng(const WgradK& k, int ng, hipStream_t s) {
-    switch (ng) {
-        case 4: return launch_wgrad<T, MT, 4>(k, s);
-        case 2: return launch_wgrad<T, MT, 2>(k, s);
-        default: return launch_wgrad<T, MT, 1>(k, s);
-    }
+    p.nsplit = k.nsplit = (k.ntiles + k.tiles_per_split - 1) / k.tiles_per_split;
+    k.cot = cot; k.xcd = (int)TUNE(xcd_remap);
+    p.nwg = (unsigned)(p.nsplit * cot * chunks);
 }
 
 template <typename T>
-int launch_wgrad_t(const WgradK& k, hipStream_t s) {
+int dy_pitch_of(int mt) { return mt == 4 ? dy_pitch<T, 4>() : mt == 2 ? dy_pitch<T, 2>() : dy_pitch<T, 1>(); }
+
+// The form, instantiation, tile, splits and LDS of a launch; sets k's tile and grid fields.  Reads the tuning table, calls no HIP.
+template <typename T>
+int wgrad_plan(const ColvoConvDesc* d, WgradK& k, WgradPlan& p) {
     constexpr int G = TT<T>::G;
+    // single up-sampled source in whole 32-channel (bf16) / 16-channel (f32) chunks: the four-class form over source positions
+    const bool up2_form = TUNE(wgrad_up2) && d->up0 && d->C1 == 0 && d->stride == 1 && d->C0 % (4 * G) == 0 && d->Cout >= 16;
+    // bf16 stride-1 layers: the register-tiled form (csrc/wgrad_rt.hip); its ways out are set up exactly as for the kernels below
+    if ((!up2_form || TUNE(wgrad_rt_over_up2)) && wgrad_rt_plan(d, p.rt)) {
+        p.form = WGRAD_RT;
+        p.nsplit = p.rt.nsplit;
+        return 0;
+    }
+    if (up2_form) {
+        const int Hs = d->Hi / 2, Ws = d->Wi / 2;
+        const Tile t = pick_tile(Hs, Ws, 1, false);
+        if ((t.toh + 2) * (t.tow + 2) * 4 <= 3 * NT) {
+            constexpr int CK = 4 * G;
+            set_wgrad_tile(k, t, Hs, Ws, t.tow + 2);
+            p.form = WGRAD_UP2;
+            p.mt = d->Cout >= 32 ? 2 : 1;
+            p.ng = 4;
+            // staging buffers | the class exchange: 4 classes x 4 source taps x MT x CK/16 accumulator blocks of 64 lanes x 16 bytes
+            p.lds = std::max((size_t)4 * BM * dy_pitch_of<T>(p.mt) + (size_t)(k.toh + 2) * k.pwl * pitch_bytes(64),
+                             (size_t)16 * p.mt * (CK / 16) * 64 * 16) + 64;
+            COLVO_CHECK_ARG(p.lds <= 160 * 1024, "wgrad (up-sampled source): tile needs %zu bytes of LDS", p.lds);
+            const int chunks = k.g.C[0] / CK, cot = (k.Cout + 16 * p.mt - 1) / (16 * p.mt);
+            set_wgrad_grid(k, p, wgrad_atomic_splits(k, chunks * cot, p.halved), cot, chunks);
+            return 0;
+        }
+    }
+    const Tile t = pick_tile(d->Ho, d->Wo, d->stride, false);
+    set_wgrad_tile(k, t, d->Ho, d->Wo, (t.tow - 1) * d->stride + 3);
     const int ng_max = (int)TUNE(wgrad_ng_max);   // tuning knob
     int ng = ng_max;
     for (int i = 0; i < 2; ++i)
@@ -1091,9 +1013,90 @@ int launch_wgrad_t(const WgradK& k, hipStream_t s) {
     // 16 images 533 -> 596 us (32-wide stays), 64 images 1651 -> 1423, 128 images 3162 -> 2662, 64 images of 512x640 5854 -> 4775
     // (profiles/r3_tuning_check.md)
     const long walk = (long)k.ntiles * ((k.g.C[0] + k.g.C[1]) / (ng * G)) * ((k.Cout + 63) / 64) / 256;
-    if (k.Cout >= 64 && (mt_max >= 4 || walk >= TUNE(wgrad_mt4_min_walk))) return launch_wgrad_ng<T, 4>(k, ng, s);
-    if (k.Cout >= 32 && mt_max >= 2 && !one_chunk) return launch_wgrad_ng<T, 2>(k, ng, s);
-    return launch_wgrad_ng<T, 1>(k, ng, s);
+    if (k.Cout >= 64 && (mt_max >= 4 || walk >= TUNE(wgrad_mt4_min_walk))) p.mt = 4;
+    else if (k.Cout >= 32 && mt_max >= 2 && !one_chunk) p.mt = 2;
+    else p.mt = 1;
+    p.ng = (ng == 4 || ng == 2) ? ng : 1;                 // (the instantiated chunk widths)
+    const int S = d->stride, CK = p.ng * G;
+    const int PH = (k.toh - 1) * S + 3, PW = k.pwl;
+    p.tail = (long)PH * ((k.tow - 1) * S + 3) * p.ng > 3 * NT;
+    const int PIXP = p.tail ? pitch_bytes_s2(p.ng * 16) : pitch_bytes(p.ng * 16), DYP = dy_pitch_of<T>(p.mt);
+    const int chunks = (k.g.C[0] + k.g.C[1]) / CK;
+    const int cot = (k.Cout + 16 * p.mt - 1) / (16 * p.mt);
+    const size_t stage = ((size_t)BM * DYP + (size_t)PH * PW * PIXP + 15) & ~(size_t)15;
+    // Teams pay only on the two full-resolution layers (16 output channels: a one-fragment co tile, so the exchange is
+    // 20 KB per team, and one or two slabs in the (co tile, channel chunk) grid, so 256 workgroups walk 40-80 tiles each).
+    // Measured at batch 16, us: up1 47.8 -> 37.5, iconv1 38.5 -> 28.9; with 32-wide co tiles it loses (enc1b 30.7 -> 40.2,
+    // up2 / iconv2 32.8 -> 37.5) and everywhere else the walk is short and the per-workgroup costs decide: -1...+8
+    // (gpurun_out/r2_bench_conv_slabs*.log).  4 teams = 1024 threads, 128 registers per lane.
+    const int teams = (int)TUNE(wgrad_teams);          // tuning knob; 1 = off
+    const int max_slabs = (int)TUNE(wgrad_team_max_slabs);   // tuning knob
+    if (!p.tail && p.mt == 1 && teams >= 4 && chunks * cot <= max_slabs && stage * 4 + 64 <= 160 * 1024) {
+        constexpr int KS = 4;
+        const int FPW = ((9 * CK + 15) / 16 + 3) / 4;        // column fragments per wave
+        p.form = WGRAD_TEAMS;
+        p.lds = std::max(stage * KS, (size_t)p.mt * FPW * NT * 16 + (size_t)NT * KS * 4) + 64;   // staging | exchange slab + db
+        COLVO_CHECK_ARG(p.lds <= 160 * 1024, "wgrad: %d teams need %zu bytes of LDS", KS, p.lds);
+        // one workgroup per CU (KS * 4 waves fill its SIMDs): as many pixel-range splits as keep the grid within 256
+        const GridFloor target = wgrad_grid_floor((int)TUNE(wgrad_team_wgs), k.ntiles, chunks * cot);
+        p.halved = target.halved;
+        set_wgrad_grid(k, p, std::max(1, target.wgs / (chunks * cot)), cot, chunks);
+        return 0;
+    }
+    p.form = WGRAD_TAIL;
+    p.lds = (size_t)BM * DYP + (size_t)PH * PW * PIXP + 64;
+    COLVO_CHECK_ARG(p.lds <= 160 * 1024, "wgrad: tile needs %zu bytes of LDS", p.lds);
+    set_wgrad_grid(k, p, wgrad_atomic_splits(k, chunks * cot, p.halved), cot, chunks);
+    return 0;
+}
+
+template <typename T, int MT, int NG, bool TAIL, int KS = 1>
+int launch_wgrad3x3(WgradK& k, const WgradPlan& p, hipStream_t s) {
+    if (int e = allow_dynamic_lds<k_wgrad3x3<T, MT, NG, TAIL, KS>>(p.lds, 160 * 1024, "wgrad")) return e;
+#ifdef COLVO_WTRACE
+    wtrace_begin(k, p.nwg, s);
+#endif
+    colvo::launch((k_wgrad3x3<T, MT, NG, TAIL, KS>), dim3(p.nwg), dim3(NT * KS), p.lds, s, k);
+    COLVO_CHECK_LAUNCH(KS > 1 ? "k_wgrad3x3 (teams)" : "k_wgrad3x3");
+#ifdef COLVO_WTRACE
+    wtrace_end(k, p.nwg, MT, NG, TAIL, KS, s);
+#endif
+    return 0;
+}
+
+template <typename T, int MT>
+int launch_wgrad_up2(const WgradK& k, const WgradPlan& p, hipStream_t s) {
+    if (int e = allow_dynamic_lds<k_wgrad_up2<T, MT>>(p.lds, 160 * 1024, "wgrad")) return e;
+    colvo::launch((k_wgrad_up2<T, MT>), dim3(p.nwg), dim3(NT), p.lds, s, k);
+    COLVO_CHECK_LAUNCH("k_wgrad_up2");
+    return 0;
+}
+
+template <typename T, int MT>
+int launch_wgrad_ng(WgradK& k, const WgradPlan& p, hipStream_t s) {
+    switch (p.ng) {
+        case 4: return p.tail ? launch_wgrad3x3<T, MT, 4, true>(k, p, s) : launch_wgrad3x3<T, MT, 4, false>(k, p, s);
+        case 2: return p.tail ? launch_wgrad3x3<T, MT, 2, true>(k, p, s) : launch_wgrad3x3<T, MT, 2, false>(k, p, s);
+        default: return p.tail ? launch_wgrad3x3<T, MT, 1, true>(k, p, s) : launch_wgrad3x3<T, MT, 1, false>(k, p, s);
+    }
+}
+
+// the kernel launch of a plan other than WGRAD_RT
+template <typename T>
+int launch_wgrad_t(WgradK& k, const WgradPlan& p, hipStream_t s) {
+    if (p.form == WGRAD_UP2) return p.mt == 2 ? launch_wgrad_up2<T, 2>(k, p, s) : launch_wgrad_up2<T, 1>(k, p, s);
+    if (p.form == WGRAD_TEAMS) {
+        switch (p.ng) {
+            case 4: return launch_wgrad3x3<T, 1, 4, false, 4>(k, p, s);
+            case 2: return launch_wgrad3x3<T, 1, 2, false, 4>(k, p, s);
+            default: return launch_wgrad3x3<T, 1, 1, false, 4>(k, p, s);
+        }
+    }
+    switch (p.mt) {
+        case 4: return launch_wgrad_ng<T, 4>(k, p, s);
+        case 2: return launch_wgrad_ng<T, 2>(k, p, s);
+        default: return launch_wgrad_ng<T, 1>(k, p, s);
+    }
 }
 
 }  // namespace
@@ -1167,8 +1170,8 @@ extern "C" int colvo_wgrad_reduce_group(const ColvoWgradSlabs* sets, int n, colv
 
 extern "C" size_t colvo_conv_wgrad_scratch_bytes(const ColvoConvDesc* d) {
     if (!d || check_desc(d, "colvo_conv_wgrad_scratch_bytes")) return 0;
-    // the launch planner itself, in plan-only mode (no pointer is dereferenced); a batch the call would slice (tensors >= 1 GiB)
-    // is planned per slice, every slice re-using the same scratch
+    // the launch planner itself, in plan-only mode (no HIP call, no pointer is dereferenced); a batch the call would slice
+    // (tensors >= 1 GiB) is planned per slice, every slice re-using the same scratch
     int nsplit = 0;
     static const char dummy = 0;
     if (wgrad_impl(d, &dummy, d->C1 ? &dummy : nullptr, &dummy, (float*)&dummy, nullptr, nullptr, 0, &nsplit, nullptr)) return 0;
@@ -1212,42 +1215,18 @@ static int wgrad_impl(const ColvoConvDesc* d, const void* x0, const void* x1, co
     k.scratch = (const char*)scratch; k.scratch_bytes = scratch ? (long long)scratch_bytes : 0; k.plan_out = plan_out;
     k.slabs_only = slabs_only;
     k.clean = clean;
-    // single up-sampled source in whole 32-channel (bf16) / 16-channel (f32) chunks: the four-class form over source positions
-    const int ck = d->dtype == COLVO_F32 ? 16 : 32;
-    const bool up2_form = TUNE(wgrad_up2) && d->up0 && d->C1 == 0 && d->stride == 1 && d->C0 % ck == 0 && d->Cout >= 16;
-    {
-        // bf16 stride-1 layers: the register-tiled form (csrc/wgrad_rt.hip); the ways out are set up here exactly as for the kernels below
-        WgradRtPlan rp;
-        if ((!up2_form || TUNE(wgrad_rt_over_up2)) && wgrad_rt_plan(d, rp)) {
-            { int err; if (wgrad_prepare(k, rp.nsplit, &err)) return err; }
-            form_hit(FORM_WGRAD_RT);
-            if (int e = wgrad_rt_launch(rp, d, x0, d->C1 ? x1 : nullptr, dy, dw, db, k.slabs, k.db_slabs, k.det, (hipStream_t)stream)) return e;
-            return wgrad_finish(k, rp.nsplit, (hipStream_t)stream);
-        }
+    WgradPlan p{};
+    if (int e = d->dtype == COLVO_F32 ? wgrad_plan<float>(d, k, p) : wgrad_plan<bf16_t>(d, k, p)) return e;
+    { int err; if (wgrad_prepare(k, p.nsplit, &err)) return err; }
+    const hipStream_t s = (hipStream_t)stream;
+    if (p.form == WGRAD_RT) {
+        form_hit(FORM_WGRAD_RT);
+        if (int e = wgrad_rt_launch(p.rt, d, x0, d->C1 ? x1 : nullptr, dy, dw, db, k.slabs, k.db_slabs, k.det, s)) return e;
+    } else {
+        if (p.form == WGRAD_UP2) form_hit(FORM_WGRAD_UP2);
+        form_hit(p.halved ? FORM_WGRAD_HALVED_GRID : FORM_WGRAD_FULL_GRID);
+        if (k.det == 2) form_hit(FORM_WGRAD_STORE_CLEAN);
+        if (int e = d->dtype == COLVO_F32 ? launch_wgrad_t<float>(k, p, s) : launch_wgrad_t<bf16_t>(k, p, s)) return e;
     }
-    {
-        if (up2_form) {
-            const int Hs = d->Hi / 2, Ws = d->Wi / 2;
-            const Tile t = pick_tile(Hs, Ws, 1, false);
-            if ((t.toh + 2) * (t.tow + 2) * 4 <= 3 * NT) {
-                k.toh = t.toh; k.tow = t.tow;
-                k.tiles_x = (Ws + t.tow - 1) / t.tow; k.tiles_y = (Hs + t.toh - 1) / t.toh;
-                k.ntiles = d->B * k.tiles_x * k.tiles_y;
-                k.m_tow = mdiv_magic(t.tow); k.m_pw = mdiv_magic(t.tow + 2);
-                k.pwl = wgrad_row_pitch(t.tow + 2, t.tow);
-                hipStream_t s = (hipStream_t)stream;
-                const bool wide = d->Cout >= 32;
-                if (d->dtype == COLVO_F32) return wide ? launch_wgrad_up2<float, 2>(k, s) : launch_wgrad_up2<float, 1>(k, s);
-                return wide ? launch_wgrad_up2<bf16_t, 2>(k, s) : launch_wgrad_up2<bf16_t, 1>(k, s);
-            }
-        }
-    }
-    const Tile t = pick_tile(d->Ho, d->Wo, d->stride, false);
-    k.toh = t.toh; k.tow = t.tow;
-    k.tiles_x = (d->Wo + t.tow - 1) / t.tow; k.tiles_y = (d->Ho + t.toh - 1) / t.toh;
-    k.ntiles = d->B * k.tiles_x * k.tiles_y;
-    k.m_tow = mdiv_magic(t.tow); k.m_pw = mdiv_magic((t.tow - 1) * d->stride + 3);
-    k.pwl = wgrad_row_pitch((t.tow - 1) * d->stride + 3, t.tow);
-    return d->dtype == COLVO_F32 ? launch_wgrad_t<float>(k, (hipStream_t)stream)
-                                 : launch_wgrad_t<bf16_t>(k, (hipStream_t)stream);
+    return wgrad_finish(k, p.nsplit, s);
 }

@@ -592,12 +592,7 @@ int wgrad_rt_launch(const WgradRtPlan& p, const ColvoConvDesc* d, const void* x0
     // always the whole exchange area: one workgroup per CU (eight waves at <= 256 registers fill its SIMDs two deep)
     const size_t lds = std::max<size_t>((size_t)2 * k.buf_bytes + WR_TAB_BYTES, (size_t)WR_EX_BYTES + WR_DB_BYTES);
     COLVO_CHECK_ARG(lds <= (size_t)WR_LDS_MAX, "wgrad_rt: %zu bytes of LDS", lds);
-    static bool configured = false;
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_wgrad_rt), hipFuncAttributeMaxDynamicSharedMemorySize, WR_LDS_MAX);
-        if (e != hipSuccess) { set_error("wgrad_rt: hipFuncSetAttribute failed: %s", hipGetErrorString(e)); return (int)e; }
-        configured = true;
-    }
+    if (int e = allow_dynamic_lds<k_wgrad_rt>(lds, WR_LDS_MAX, "wgrad_rt")) return e;
     const unsigned nwg = (unsigned)(p.nsplit * p.nci * p.nco);
 #ifdef COLVO_WTRACE
     static long long* g_tr = nullptr;

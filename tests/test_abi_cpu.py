@@ -155,3 +155,36 @@ def test_tuning_table_hooks_and_no_stray_getenv(lib):
         os.environ.pop("COLVO_DEV", None)
         if dev is not None:
             os.environ["COLVO_DEV"] = dev
+
+
+def _network_conv_descs():
+    """Every conv layer of DepthNet (the descriptors DepthNet._plan builds) and of PoseNet (its stride-2 chain, as
+    PoseNet._forward_impl builds it) at 16, 64 and 128 frames of 256x320 and 64 frames of 512x640, bf16 and f32."""
+    import types
+    from coivo_amd import nn as hnn, ops
+    for dt in (torch.bfloat16, torch.float32):
+        for B, H, W in ((16, 256, 320), (64, 256, 320), (128, 256, 320), (64, 512, 640)):
+            plan = hnn.DepthNet._plan(types.SimpleNamespace(compute_dtype=dt, _plans={}), B, H, W)
+            for name, d in plan.items():
+                yield f"DepthNet.{name} {dt} B={B} {H}x{W}", d
+            h, w, cin = H, W, 8
+            for i, c in enumerate(hnn.POSE_CH, start=1):
+                d = ops.conv_desc(dt, B, h, w, cin, c, stride=2)
+                yield f"PoseNet.conv{i} {dt} B={B} {H}x{W}", d
+                h, w, cin = d.Ho, d.Wo, c
+
+
+def test_wgrad_plan_queries_have_no_side_effects(lib):
+    """colvo_conv_wgrad_splits / colvo_conv_wgrad_scratch_bytes run the weight-gradient planner alone: no HIP call (so they
+    answer without a GPU), no kernel form counted, and the scratch size follows from the split count."""
+    from coivo_amd import _lib
+    n = 0
+    for name, d in _network_conv_descs():
+        before = _lib.form_counts()
+        splits = lib.colvo_conv_wgrad_splits(C.byref(d))
+        assert splits >= 1, f"{name}: {lib.colvo_last_error()}"
+        scratch = lib.colvo_conv_wgrad_scratch_bytes(C.byref(d))
+        assert scratch == splits * (d.Cout * 9 * (d.C0 + d.C1) + d.Cout) * 4, f"{name}: {lib.colvo_last_error()}"
+        assert _lib.form_counts() == before, name
+        n += 1
+    assert n == 2 * 4 * (20 + 7)
