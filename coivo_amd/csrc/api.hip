@@ -30,7 +30,10 @@ extern "C" void colvo_form_counts_reset(void) {
 }
 extern "C" const char* colvo_form_name(int id) {
     static const char* names[colvo::FORM_COUNT] = {"conv_rt", "wgrad_full_grid", "wgrad_halved_grid", "wgrad_up2", "wgrad_rt", "wgrad_store_clean",
-                                                   "conv_res_s2", "conv_q"};
+                                                   "conv_res_s2", "conv_q", "conv_up2_bn16", "conv_up2_bn32", "dgrad_s2", "dgrad_s2_ring",
+                                                   "dgrad_up2", "dgrad_both", "conv_tile", "conv_ring", "conv_wide", "conv_res", "conv_bn64",
+                                                   "wgrad_teams", "wgrad_tail", "wgrad_mt4", "wgrad_sliced", "bwd16", "fwd16_head",
+                                                   "dgrad_planes_mfma", "conv_rt_bn32"};
     return id >= 0 && id < colvo::FORM_COUNT ? names[id] : nullptr;
 }
 

@@ -665,6 +665,7 @@ int colvo::launch_dgrad_planes_s2_mfma(const void* g, const float* w, int Cin, i
     // 2 groups per wave up to 8 pairs of 256x320 (1280 workgroups), more beyond
     k.groups_per_wave = std::max((int)TUNE(planes_groups), (k.ngroups + 4 * 2048 - 1) / (4 * 2048));
     const int wgs = (k.ngroups + 4 * k.groups_per_wave - 1) / (4 * k.groups_per_wave);
+    form_hit(FORM_DGRAD_PLANES_MFMA);
     colvo::launch(k_dgrad_planes_s2_mfma, dim3((unsigned)wgs), dim3(NT), 0, stream, k);
     COLVO_CHECK_LAUNCH("k_dgrad_planes_s2_mfma");
     return 0;
@@ -737,6 +738,7 @@ extern "C" int colvo_conv_bwd_fused(const ColvoConvDesc* d, const void* dy, cons
     k.ntiles = k.B * k.tiles_x * k.tiles_y;
     const int wgs = bwd16_grid(d, head_partials ? 2 : head_dpre ? 1 : 0, &k.tiles_per_wg);
     k.dpre = head_dpre; k.head_w = head_w; k.head_partials = head_partials;
+    form_hit(FORM_BWD16);
     if (head_partials) colvo::launch(k_bwd16<2>, dim3((unsigned)wgs), dim3(NT), 0, (hipStream_t)stream, k);
     else if (head_dpre) colvo::launch(k_bwd16<1>, dim3((unsigned)wgs), dim3(NT), 0, (hipStream_t)stream, k);
     else colvo::launch(k_bwd16<0>, dim3((unsigned)wgs), dim3(NT), 0, (hipStream_t)stream, k);

@@ -73,9 +73,27 @@ inline int allow_dynamic_lds(size_t lds, int limit, const char* who) {
 }
 
 // Which kernel FORM a dispatcher chose, counted per process (colvo_form_counts: the tests of the grid-size-selected forms read it --
-// a parity test at a small shape must be able to say that the large-grid kernel is what actually ran).
+// a parity test at a small shape must be able to say that the large-grid kernel is what actually ran).  Every leaf of
+// the forward / input-gradient / weight-gradient dispatch trees and every fused kernel has a counter; the grid and store attributes of
+// the weight gradient (full / halved grid, clean-arena store, 64-wide co tile) and the 64-wide one-tile channel tile count beside their
+// leaf.  Names: api.hip (same order).
 enum { FORM_CONV_RT = 0, FORM_WGRAD_FULL_GRID, FORM_WGRAD_HALVED_GRID, FORM_WGRAD_UP2, FORM_WGRAD_RT, FORM_WGRAD_STORE_CLEAN, FORM_CONV_RES_S2,
-       FORM_CONV_Q, FORM_COUNT };
+       FORM_CONV_Q,
+       FORM_CONV_UP2_BN16, FORM_CONV_UP2_BN32,    // k_conv_up2, 16- / 32-wide channel tiles
+       FORM_DGRAD_S2, FORM_DGRAD_S2_RING,         // k_dgrad_s2, one chunk / two chunks in flight
+       FORM_DGRAD_UP2,                            // k_dgrad_up2
+       FORM_DGRAD_BOTH,                           // colvo_conv_dgrad_both's merged launch (beside the leaf it took: conv_rt or a one-tile form)
+       FORM_CONV_TILE, FORM_CONV_RING,            // k_conv3x3 one-tile kernel (256 threads), its two-chunk register ring
+       FORM_CONV_WIDE,                            // ... its 512-thread / 256-pixel form (tuning `wide`, off by default)
+       FORM_CONV_RES,                             // k_conv3x3_res, stride 1
+       FORM_CONV_BN64,                            // a one-tile (256- or 512-thread) or weights-resident launch with 64-wide channel tiles
+       FORM_WGRAD_TEAMS, FORM_WGRAD_TAIL,         // k_wgrad3x3 with four pixel-tile teams / one team
+       FORM_WGRAD_MT4,                            // ... one team, 64-wide co tile
+       FORM_WGRAD_SLICED,                         // a weight-gradient call processed in image slices (tensors >= 1 GiB)
+       FORM_BWD16, FORM_FWD16_HEAD, FORM_DGRAD_PLANES_MFMA,
+       FORM_CONV_RT_BN32,                         // k_conv_rt's 32-channel form (beside conv_rt)
+       FORM_COUNT };
+static_assert(FORM_COUNT <= 32, "coivo_amd/_lib.py form_counts reads 32 counters");
 void form_hit(int id);
 
 // csrc/bwd16.hip: the MFMA form of colvo_conv_dgrad_planes (bf16, stride 2, 16 output channels, two input channels, even extents)

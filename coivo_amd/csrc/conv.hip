@@ -1477,7 +1477,8 @@ int launch_conv_res(const ConvK& k, int B, hipStream_t s) {
     int gx = 256 * per_cu;
     if (gx > ntiles) gx = ntiles;
     dim3 grid(gx, (k.N + BN - 1) / BN, 1);
-    if (S2) form_hit(FORM_CONV_RES_S2);
+    form_hit(S2 ? FORM_CONV_RES_S2 : FORM_CONV_RES);
+    if (BN == 64) form_hit(FORM_CONV_BN64);
     colvo::launch((k_conv3x3_res<T, BN, NG, S2>), grid, dim3(NT), lds, s, k, ntiles, mdiv_magic(k.tiles_x * k.tiles_y),
                        mdiv_magic(k.tiles_x));
     COLVO_CHECK_LAUNCH("k_conv3x3_res");
@@ -1543,12 +1544,14 @@ int launch_conv_ng(const ConvK& k, int B, int ng, hipStream_t s) {
                 const long lone_max = TUNE(lone_max_wgs);
                 const long wgs = (long)k.tiles_x * k.tiles_y * B * ((k.N + BN - 1) / BN);
                 if (wgs <= lone_max && (k.g.C[0] + k.g.C[1]) / (4 * TT<T>::G) >= depth2_min) {
+                    form_hit(FORM_CONV_RING);
                     return launch_conv<T, BN, 4, 2>(k, B, s);     // (a three-chunk ring measured no better)
                 }
             }
+            form_hit(FORM_CONV_TILE);
             return launch_conv<T, BN, 4>(k, B, s);
-        case 2: return launch_conv<T, BN, 2>(k, B, s);
-        default: return launch_conv<T, BN, 1>(k, B, s);
+        case 2: form_hit(FORM_CONV_TILE); return launch_conv<T, BN, 2>(k, B, s);
+        default: form_hit(FORM_CONV_TILE); return launch_conv<T, BN, 1>(k, B, s);
     }
 }
 
@@ -1561,6 +1564,7 @@ inline void set_tile(ConvK& k, const Tile& t) {
 
 template <typename T, int BN>
 int launch_conv_wide(const ConvK& k, int B, int ng, hipStream_t s) {
+    form_hit(FORM_CONV_WIDE);
     switch (ng) {
         case 4: return launch_conv_tail<T, BN, 4, 1, false, 0, 512>(k, B, s);
         case 2: return launch_conv_tail<T, BN, 2, 1, false, 0, 512>(k, B, s);
@@ -1594,6 +1598,7 @@ int launch_conv_t(ConvK k, int B, bool even, hipStream_t s) {
             const long wgs = (long)((k.Ho + tw.toh - 1) / tw.toh) * ((k.Wo + tw.tow - 1) / tw.tow) * B * ((k.N + bn - 1) / bn);
             if (patch <= 3 * 512 && tw.toh * tw.tow > 128 && wgs >= wide_min_wgs) {
                 set_tile(k, tw);
+                if (bn == 64) form_hit(FORM_CONV_BN64);
                 return bn == 64 ? launch_conv_wide<T, 64>(k, B, ng, s) : launch_conv_wide<T, 32>(k, B, ng, s);
             }
         }
@@ -1609,7 +1614,10 @@ int launch_conv_t(ConvK k, int B, bool even, hipStream_t s) {
     const long bn64_min_wgs = TUNE(bn64_min_wgs);   // tuning knob
     const long bn32_min_wgs = TUNE(bn32_min_wgs);      // tuning knob (16-wide tiles: measured ~neutral)
     // (two-output form: a channel tile must not straddle the two sources -- nsplit is a multiple of 32)
-    if (k.nsplit == 0 && k.N >= 64 && tiles * ((k.N + 63) / 64) >= bn64_min_wgs) return launch_conv_ng<T, 64>(k, B, ng, s);
+    if (k.nsplit == 0 && k.N >= 64 && tiles * ((k.N + 63) / 64) >= bn64_min_wgs) {
+        form_hit(FORM_CONV_BN64);
+        return launch_conv_ng<T, 64>(k, B, ng, s);
+    }
     if (k.N >= 32 && tiles * ((k.N + 31) / 32) >= bn32_min_wgs) return launch_conv_ng<T, 32>(k, B, ng, s);
     return launch_conv_ng<T, 16>(k, B, ng, s);
 }
@@ -1667,6 +1675,7 @@ int launch_conv_up2_inst(const ConvK& k, int B, hipStream_t s) {
 
 template <typename T, int BN>
 int launch_conv_up2_bn(const ConvK& k, int B, hipStream_t s) {
+    form_hit(BN == 32 ? FORM_CONV_UP2_BN32 : FORM_CONV_UP2_BN16);
     const int nch = k.g.C[0] / (4 * TT<T>::G);
     if (nch == 8) return launch_conv_up2_inst<T, BN, 2, 8>(k, B, s);
     if (nch == 16) return launch_conv_up2_inst<T, BN, 2, 16>(k, B, s);
@@ -1685,6 +1694,7 @@ int launch_dgrad_up2_inst(const ConvK& k, int B, hipStream_t s) {
 
 template <typename T, int BN>
 int launch_dgrad_up2_bn(const ConvK& k, int B, hipStream_t s) {
+    form_hit(FORM_DGRAD_UP2);
     if (k.g.C[0] % (4 * TT<T>::G)) return launch_dgrad_up2_inst<T, BN, 1, 0, 2>(k, B, s);       // 2-granule chunks
     const int nch = k.g.C[0] / (4 * TT<T>::G);
     if (nch == 8) return launch_dgrad_up2_inst<T, BN, 2, 8>(k, B, s);
@@ -1706,10 +1716,11 @@ int launch_dgrad_s2_bn(const ConvK& k, int B, hipStream_t s) {
     const int nch = k.g.C[0] / (4 * TT<T>::G);
     const long wgs = (long)k.tiles_x * k.tiles_y * B * ((k.N + BN - 1) / BN);
     const long lone_max = TUNE(lone_max_wgs);
-    if (wgs <= lone_max) {          // about one workgroup per CU: two chunks in flight, K loop unrolled (see launch_conv_ng)
-        if (nch == 8) return launch_dgrad_s2_inst<T, BN, 2, 8>(k, B, s);
-        if (nch == 16) return launch_dgrad_s2_inst<T, BN, 2, 16>(k, B, s);
+    if (wgs <= lone_max && (nch == 8 || nch == 16)) {      // about one workgroup per CU: two chunks in flight, K loop unrolled (see launch_conv_ng)
+        form_hit(FORM_DGRAD_S2_RING);
+        return nch == 8 ? launch_dgrad_s2_inst<T, BN, 2, 8>(k, B, s) : launch_dgrad_s2_inst<T, BN, 2, 16>(k, B, s);
     }
+    form_hit(FORM_DGRAD_S2);
     return launch_dgrad_s2_inst<T, BN, 1, 0>(k, B, s);
 }
 
@@ -1874,6 +1885,7 @@ extern "C" int colvo_conv_dgrad_both(const ColvoConvDesc* d, const void* dy, con
     ConvK k = dgrad_conv(d, dy, w_bwd, 0, d->C0 + d->C1, dx0, relu_mask0, 0);
     k.Ho = d->Hi; k.Wo = d->Wi;
     k.out2 = (char*)dx1; k.mask2 = (const char*)relu_mask1; k.nsplit = d->C0;
+    form_hit(FORM_DGRAD_BOTH);
     {
         const int r = try_launch_conv_rt(k, d->B, d->dtype, (hipStream_t)stream);
         if (r >= 0) return r;

@@ -363,6 +363,7 @@ int try_launch_conv_rt(const ConvK& k0, int B, int dtype, hipStream_t s) {
     const long long nwg = tile_grid(k, bn64 ? 64 : 32, B);
     if (nwg < (bn64 ? TUNE(rt_min_wgs) : TUNE(rt_bn32_min_wgs)) || nwg >= (1ll << 30)) return -1;
     form_hit(FORM_CONV_RT);
+    if (!bn64) form_hit(FORM_CONV_RT_BN32);
     if (dtype == COLVO_F32) return bn64 ? launch_conv_rt<float, 4>(k, nwg, s) : launch_conv_rt<float, 2>(k, nwg, s);
     return bn64 ? launch_conv_rt<bf16_t, 4>(k, nwg, s) : launch_conv_rt<bf16_t, 2>(k, nwg, s);
 }

@@ -43,7 +43,8 @@ namespace tune {
     X(dgrad_both, 1, "both sources' input gradients of a concat layer in one launch")                                               \
     X(conv_quad, 1, "quad-tile kernel for ordinary stride-1 layers (k_conv_q)")                                                     \
     X(quad_min_wgs, 8192, "... from this many quad-tile workgroups on (iconv2 at configs[2] size 370 -> 275 us; at 2560-5120 "      \
-                          "workgroups of 256x320 frames it loses 3-6 % of the pass)")                                               \
+                          "workgroups of 256x320 frames it loses 3-6 % of the pass).  k_conv_rt is tried first and takes those "  \
+                          "grids: no benchmark shape reaches k_conv_q (tests/test_conv_exact_gpu.py)")          \
     X(quad_max_chunks, 4, "... and at most this many chunks (deeper layers keep the two-chunk ring)")                               \
     X(conv_rt, 1, "register-tiled stride-1 kernel (k_conv_rt, csrc/conv_rt.hip: 16x16 pixels x 64/32 channels, 4x4 fragments per wave)") \
     X(rt_min_wgs, 1024, "... from this many of its workgroups on (64 frames, us fwd / dgrad, one-tile -> this: enc2b 42.4 / 52.6 -> 35.6 / "  \

@@ -1191,6 +1191,7 @@ static int wgrad_impl(const ColvoConvDesc* d, const void* x0, const void* x1, co
         COLVO_CHECK_ARG(per_img < 0x40000000LL, "colvo_conv_wgrad: a single image of %lld bytes is not supported", per_img);
         const int bmax = (int)std::max(1LL, (0x40000000LL - 1) / per_img);
         if (d->B > bmax) {
+            if (!plan_out) form_hit(FORM_WGRAD_SLICED);
             COLVO_CHECK_ARG(!slabs_only, "colvo_conv_wgrad_slabs: batch %d would be sliced (tensors >= 1 GiB); use colvo_conv_wgrad_det", d->B);
             const long long e0 = (long long)(d->up0 ? (d->Hi / 2) * (d->Wi / 2) : d->Hi * d->Wi) * d->C0 * es;
             const long long e1 = (long long)(d->up1 ? (d->Hi / 2) * (d->Wi / 2) : d->Hi * d->Wi) * d->C1 * es;
@@ -1223,7 +1224,8 @@ static int wgrad_impl(const ColvoConvDesc* d, const void* x0, const void* x1, co
         form_hit(FORM_WGRAD_RT);
         if (int e = wgrad_rt_launch(p.rt, d, x0, d->C1 ? x1 : nullptr, dy, dw, db, k.slabs, k.db_slabs, k.det, s)) return e;
     } else {
-        if (p.form == WGRAD_UP2) form_hit(FORM_WGRAD_UP2);
+        form_hit(p.form == WGRAD_UP2 ? FORM_WGRAD_UP2 : p.form == WGRAD_TEAMS ? FORM_WGRAD_TEAMS : FORM_WGRAD_TAIL);
+        if (p.form == WGRAD_TAIL && p.mt == 4) form_hit(FORM_WGRAD_MT4);
         form_hit(p.halved ? FORM_WGRAD_HALVED_GRID : FORM_WGRAD_FULL_GRID);
         if (k.det == 2) form_hit(FORM_WGRAD_STORE_CLEAN);
         if (int e = d->dtype == COLVO_F32 ? launch_wgrad_t<float>(k, p, s) : launch_wgrad_t<bf16_t>(k, p, s)) return e;

@@ -532,10 +532,16 @@ int colvo_capture_reset(colvo_stream_t stream);
 /* Dispatch thresholds (coivo_amd/csrc/tuning.h: ONE table, defaults measured on MI355X; production reads no environment
  * variable).  Developer / test hooks: set or read an entry by name ("quad_min_wgs", "wgrad_atomic_mb", ...); with COLVO_DEV=1 in
  * the environment at load time every entry can also be overridden by COLVO_<UPPER-CASE NAME>. */
-/* Which kernel form the dispatchers chose, counted per process since the last reset (developer / test hook: the forms that are
- * selected by grid size -- k_conv_rt, the halved weight-gradient grids, the four-class / register-tiled weight gradients, the
- * clean-arena stores -- are invisible in a result; a test that means to cover one asserts that it ran).  colvo_form_counts fills
- * out[0..n) and returns the number of forms; colvo_form_name(id) names them (NULL beyond the last). */
+/* Which kernel form the dispatchers chose, counted per process since the last reset (developer / test hook: which form ran is
+ * invisible in a result; a test that means to cover one asserts that it ran).  Every leaf of the forward, input-gradient and
+ * weight-gradient dispatch trees has a counter (k_conv_rt, k_conv_q, k_conv_up2 16- / 32-wide, k_dgrad_s2 and its two-chunk ring,
+ * k_dgrad_up2, the one-tile kernel, its two-chunk ring and 512-thread form, the weights-resident kernel stride 1 / 2, the weight
+ * gradient's register-tiled, four-class, teams and one-team forms), so do the fused kernels (k_bwd16, k_fwd16_head,
+ * k_dgrad_planes_s2_mfma), colvo_conv_dgrad_both's merged launch, and the attributes 32-channel k_conv_rt, 64-wide channel tile
+ * of the one-tile and weights-resident kernels, full / halved
+ * weight-gradient grid, 64-wide weight-gradient co tile, clean-arena store and image-sliced weight gradient.  One relaxed atomic per
+ * launch; plan-only queries count nothing.  colvo_form_counts fills out[0..n) and returns the number of forms (at most 32);
+ * colvo_form_name(id) names them (NULL beyond the last). */
 int colvo_form_counts(long long* out, int n);
 void colvo_form_counts_reset(void);
 const char* colvo_form_name(int id);

@@ -188,3 +188,46 @@ def test_wgrad_plan_queries_have_no_side_effects(lib):
         assert _lib.form_counts() == before, name
         n += 1
     assert n == 2 * 4 * (20 + 7)
+
+
+def test_every_kernel_form_has_a_distinct_name(lib):
+    """colvo_form_counts / colvo_form_name: at most the 32 counters _lib.form_counts reads, every one named, no two alike, NULL beyond
+    the last; the counters start at zero and a name lookup out of range does not crash."""
+    from coivo_amd import _lib
+    buf = (C.c_longlong * 32)()
+    n = lib.colvo_form_counts(buf, 32)
+    assert 8 <= n <= 32
+    names = [lib.colvo_form_name(i) for i in range(n)]
+    assert all(isinstance(x, bytes) and x for x in names), names
+    assert len(set(names)) == n, names
+    assert lib.colvo_form_name(n) is None and lib.colvo_form_name(-1) is None
+    assert list(_lib.form_counts()) == [x.decode() for x in names]
+    # the leaves the dispatch trees of csrc/conv.hip, conv_rt.hip, wgrad.hip, bwd16.hip and fwd16.hip count
+    for leaf in ("conv_rt", "conv_q", "conv_up2_bn16", "conv_up2_bn32", "dgrad_s2", "dgrad_s2_ring", "dgrad_up2", "dgrad_both", "conv_tile",
+                 "conv_ring", "conv_wide", "conv_res", "conv_res_s2", "conv_bn64", "wgrad_teams", "wgrad_tail", "wgrad_mt4", "wgrad_sliced",
+                 "wgrad_up2", "wgrad_rt", "bwd16", "fwd16_head", "dgrad_planes_mfma", "conv_rt_bn32"):
+        assert leaf.encode() in names, leaf
+
+
+def test_exact_data_stays_in_the_exact_regime_at_every_production_shape():
+    """tests/conv_exact.py's value sets and dy density rule keep every output element of every pass within 2^22 quanta (fp32 exact
+    below 2^24, whatever the summation order) for every conv layer of the benchmark's shapes: the exact GPU tests cannot silently
+    leave the exact regime at a future shape."""
+    from tests import conv_exact as X
+    n = 0
+    for name, d in _network_conv_descs():
+        cin = d.C0 + d.C1
+        assert X.bound_fwd(cin) <= X.BOUND, name
+        assert X.bound_dgrad(d.Cout, bool(d.up0 or d.up1)) <= X.BOUND, name
+        npix = d.B * d.Ho * d.Wo
+        assert X.bound_wgrad(npix) <= X.BOUND, (name, X.bound_wgrad(npix))
+        assert X.dy_density(npix) * npix >= min(npix / 4, 1e5), name          # ... and dy is not so sparse that the check is empty
+        n += 1
+    assert n == 2 * 4 * (20 + 7)
+    # the value sets: every magnitude in its quantum, representable in bf16
+    g = torch.Generator().manual_seed(1)
+    for t, q, m in ((X.make_source((4096,), g, "cpu"), X.QX, X.X_MAX), (X.make_weights(16, 16, g, "cpu"), X.QW, X.W_MAX),
+                    (X.make_bias(4096, g, "cpu"), X.QB, X.B_MAX), (X.make_dy((4096,), 0.5, g, "cpu"), X.QDY, X.DY_MAX),
+                    (X.make_base((4096,), g, "cpu"), X.QBASE, X.BASE_MAX)):
+        assert torch.equal(t.to(torch.bfloat16).float(), t)
+        assert torch.equal(t / q, (t / q).round()) and float((t / q).abs().max()) == m

@@ -49,8 +49,9 @@ CASES = [
     (2, 16, 24, 8, 0, False, False, 8, 1),        # narrower than the smallest channel tile (rows beyond N read as zero)
     (2, 8, 10, 256, 0, False, False, 64, 1),      # 8 chunks, <= 256 workgroups: the two-chunk register ring
     (4, 256, 320, 16, 0, False, False, 16, 1),    # >= 2048 tiles, single chunk: weights-resident persistent kernel
-    (4, 256, 320, 32, 0, True, False, 16, 1),     # ... its dgrad with the 2x2 sum-pool of an up-sampled source
-    (8, 128, 160, 32, 0, False, False, 32, 1),    # ... 32-wide
+    (4, 256, 288, 32, 0, True, False, 16, 1),     # ... its dgrad with the 2x2 sum-pool of an up-sampled source (form0: 2304 tiles, and the
+                                                  #     k_dgrad_up2 grid below dgrad_up2_min_wgs; form1 / form2 lower that: k_dgrad_up2)
+    (13, 128, 160, 32, 0, False, False, 32, 1),   # ... 32-wide (bf16: one chunk; 2080 tiles); f32: two chunks, the one-tile kernel
     # stride 2 with an even input: the parity-decomposed input gradient (k_dgrad_s2)
     (2, 32, 40, 64, 0, False, False, 128, 2),     # 4 chunks (bf16), two N tiles, ragged tiles (16 x 20 positions)
     (2, 16, 20, 128, 0, False, False, 256, 2),    # 8 chunks, few workgroups: unrolled two-chunk ring
@@ -76,9 +77,9 @@ CASES = [
     (2, 16, 20, 256, 0, False, False, 256, 1),    # 8 chunks
     (1, 8, 10, 288, 0, False, False, 64, 1),      # 9 (bf16) / 18 (f32) chunks: odd count on the two-chunk ring
     # stride 2, ONE chunk (32 bf16 / 16 f32 channels): the stride-2 form of the weights-resident persistent kernel in the form2 runs
-    (3, 32, 48, 32, 0, False, False, 64, 2),      # 64-wide channel tile (bf16), several tiles per image and per workgroup
-    (2, 40, 56, 16, 0, False, False, 32, 2),      # f32: one chunk of 16; bf16: two-granule chunks; ragged tiles (20 x 28 outputs)
-    (5, 16, 32, 32, 0, False, False, 48, 2),      # N = 48 in a 64-wide (bf16) tile: rows beyond N read as zero
+    (3, 32, 48, 32, 0, False, False, 64, 2),      # 64-wide channel tile (bf16), several tiles per image and per workgroup; f32: two chunks
+    (2, 40, 112, 16, 0, False, False, 32, 2),     # f32: one chunk of 16; bf16: two-granule chunks; 20 x 56 outputs
+    (5, 16, 64, 32, 0, False, False, 48, 2),      # N = 48 (bf16): two 32-wide channel tiles, rows beyond N of the second read as zero
     # stride 1, direct sources: the register-tiled kernel (k_conv_rt) in the form2 runs -- 16 x 16 tiles x 64 / 32 channels
     (2, 32, 48, 64, 0, False, False, 64, 1),      # exact tiles, one 64-wide channel tile, 2 chunks
     (1, 48, 32, 64, 64, False, False, 128, 1),    # concat 64 + 64 (two-output input gradient, 64-wide tiles), two N tiles
@@ -124,22 +125,23 @@ def _close(got, ref, rtol, atol_scale, what):
     assert not bad.any(), f"{what}: max err {err.max().item():.3e} (atol {atol:.3e}), {int(bad.sum())} bad of {bad.numel()}"
 
 
-@pytest.fixture(autouse=True)
-def _both_kernel_forms(request):
+_FORM_TUNING = ("dgrad_up2_min_wgs", "quad_min_wgs", "quad_max_chunks", "rt_min_wgs", "rt_bn32_min_wgs", "rt_min_fill_pct", "rt_min_chunks",
+                "rt_tiles_per_wg", "res_s2_min_tiles", "wgrad_rt", "wgrad_rt_min_c", "wgrad_rt_over_up2", "wgrad_rt_wgs", "wgrad_rt_max_px")
+
+
+def _set_form(form, dtype):
     """The fat-workgroup kernels (k_conv_q: quad tiles for stride-1 layers; k_dgrad_up2: sum-pool in the K loop) are selected
-    only for large grids (>= 2048 / 640 workgroups); the parametrised cases are small, so half of the runs lower the thresholds
-    in the library's tuning table (colvo_tune_set, csrc/tuning.h) to reach them -- the other half exercises the one-tile kernels
-    on the same shapes."""
+    only for large grids (>= 2048 / 640 workgroups); the parametrised cases are small, so form1 / form2 lower the thresholds
+    in the library's tuning table (colvo_tune_set, csrc/tuning.h) to reach them -- form0 exercises the production dispatch on the
+    same shapes.  Returns the entries to restore."""
     from coivo_amd import _lib
-    names = ("dgrad_up2_min_wgs", "quad_min_wgs", "quad_max_chunks", "rt_min_wgs", "rt_bn32_min_wgs", "rt_min_fill_pct", "rt_min_chunks", "rt_tiles_per_wg", "res_s2_min_tiles",
-             "wgrad_rt", "wgrad_rt_min_c", "wgrad_rt_over_up2", "wgrad_rt_wgs", "wgrad_rt_max_px")
-    saved = {n: _lib.tune_get(n) for n in names}
+    saved = {n: _lib.tune_get(n) for n in _FORM_TUNING}
     # The register-tiled weight gradient (k_wgrad_rt, csrc/wgrad_rt.hip; bf16 stride-1 layers; measured level alone and a loss in the step,
     # so production leaves it off -- profiles/r6_wgrad_rt.md -- and form0 is the production dispatch): form1 runs it on EVERY bf16 stride-1
     # case (8-, 16-, 24-, 40-channel tensors in 32-wide tiles, up-sampled sources read through its staging addresses) with tiles of
     # at most 48 pixels and three workgroups per (co, ci) tile -- long walks over both staging buffers, ragged tiles, image groups cut
     # short by the batch; form2 the same tensors in full-size tiles on 256-workgroup grids.
-    if "form1" in request.node.name:
+    if form == "form1":
         _lib.tune_set("wgrad_rt", 1)
         _lib.tune_set("wgrad_rt_min_c", 8)
         _lib.tune_set("wgrad_rt_over_up2", 1)
@@ -148,7 +150,7 @@ def _both_kernel_forms(request):
         _lib.tune_set("dgrad_up2_min_wgs", 0)
         _lib.tune_set("quad_min_wgs", 0)
         _lib.tune_set("quad_max_chunks", 64)
-    if "form2" in request.node.name:
+    if form == "form2":
         _lib.tune_set("wgrad_rt", 1)
         _lib.tune_set("wgrad_rt_min_c", 8)
         _lib.tune_set("wgrad_rt_over_up2", 1)
@@ -162,11 +164,24 @@ def _both_kernel_forms(request):
         _lib.tune_set("res_s2_min_tiles", 2)       # the stride-2 form of the weights-resident persistent kernel (single-chunk layers)
         # ... bf16 runs with workgroups that WALK three consecutive tiles (across channel tiles, tile rows and images; the last
         # workgroup a shorter walk), f32 runs with one tile per workgroup, the production setting
-        params = getattr(getattr(request.node, "callspec", None), "params", {})
-        _lib.tune_set("rt_tiles_per_wg", 3 if params.get("dtype") == torch.bfloat16 else 0)
-    yield
+        _lib.tune_set("rt_tiles_per_wg", 3 if dtype == torch.bfloat16 else 0)
+    return saved
+
+
+def _restore(saved):
+    from coivo_amd import _lib
     for n, v in saved.items():
         _lib.tune_set(n, v)
+
+
+@pytest.fixture(autouse=True)
+def _both_kernel_forms(request):
+    """Runs test_conv_fwd_dgrad_wgrad and its exact-data twin in form0 / form1 / form2 (_set_form) and restores the table."""
+    params = getattr(getattr(request.node, "callspec", None), "params", {})
+    form = next((f for f in ("form0", "form1", "form2") if f in request.node.name), "form0")
+    saved = _set_form(form, params.get("dtype"))
+    yield
+    _restore(saved)
 
 
 @pytest.mark.parametrize("form", ["form0", "form1", "form2"])
@@ -257,6 +272,123 @@ def test_conv_fwd_dgrad_wgrad(case, dtype, form):
     assert torch.equal(dws[0], dws[1]) and torch.equal(dbs[0], dbs[1])
     ops.conv_wgrad(desc, x0d, x1d, dyd, dws[0], dbs[0], scr)
     _close(dws[0], 2 * wr.grad, rt, at, "wgrad (deterministic form) accumulate")
+
+
+# The kernels the comments of CASES name, by case index: (forms, dtypes, acceptable forms) -- at least one pass of the exact twin counts one
+# of them (include/colvo.h colvo_form_counts).  bf16 / f32 differ where the chunk width does (32 / 16 channels).
+_BF, _F32, _ALL = (torch.bfloat16,), (torch.float32,), (torch.bfloat16, torch.float32)
+CASE_FORMS = {
+    11: [("form0", _ALL, {"conv_ring"})],                                   # the two-chunk register ring
+    12: [("form0", _ALL, {"conv_res"})],                                    # weights-resident persistent kernel
+    13: [("form0", _ALL, {"conv_res"}), ("form1", _ALL, {"dgrad_up2"})],   # ... its input gradient with the sum-pool
+    14: [("form0", _BF, {"conv_res"}), ("form1", _BF, {"conv_res"}), ("form0", _F32, {"conv_tile"})],
+    15: [("form0", _BF, {"dgrad_s2"})],                                     # 4 chunks (f32: 8, the ring)
+    16: [("form0", _ALL, {"dgrad_s2_ring"})],                               # unrolled two-chunk ring
+    17: [("form0", _BF, {"dgrad_s2_ring"})],                                # 16 chunks (f32: 32, one chunk in flight)
+    18: [("form0", _ALL, {"dgrad_s2"})],
+    19: [("form0", _ALL, {"dgrad_s2"})],
+    20: [("form0", _ALL, {"dgrad_s2"})],
+    21: [("form0", _ALL, {"conv_up2_bn16", "conv_up2_bn32"})],
+    22: [("form0", _ALL, {"conv_up2_bn16", "conv_up2_bn32"})],
+    23: [("form0", _ALL, {"conv_up2_bn16", "conv_up2_bn32"})],
+    24: [("form0", _ALL, {"conv_up2_bn16", "conv_up2_bn32"})],
+    25: [("form0", _ALL, {"conv_up2_bn16", "conv_up2_bn32"})],
+    26: [("form1", _ALL, {"dgrad_up2"}), ("form2", _ALL, {"dgrad_up2"})],
+    27: [("form1", _ALL, {"dgrad_up2"}), ("form2", _ALL, {"dgrad_up2"})],
+    28: [("form1", _ALL, {"conv_q"})],
+    29: [("form1", _ALL, {"conv_q"})],
+    30: [("form1", _ALL, {"conv_q"})],
+    31: [("form0", _ALL, {"conv_ring"})],                                   # deep layers on few workgroups: the two-chunk ring
+    32: [("form0", _ALL, {"conv_ring"})],
+    33: [("form0", _ALL, {"conv_ring"})],
+    34: [("form0", _ALL, {"conv_ring"})],
+    35: [("form2", _BF, {"conv_res_s2"}), ("form2", _BF, {"conv_bn64"})],
+    36: [("form2", _ALL, {"conv_res_s2"})],
+    37: [("form2", _BF, {"conv_res_s2"})],
+    35: [("form2", _BF, {"conv_res_s2"})],
+    38: [("form2", _ALL, {"conv_rt"})],
+    39: [("form2", _ALL, {"conv_rt"})],
+    40: [("form2", _ALL, {"conv_rt"}), ("form2", _ALL, {"conv_rt_bn32"})],   # 32-wide tiles
+    41: [("form2", _ALL, {"conv_rt"})],
+    42: [("form1", _BF, {"wgrad_rt"}), ("form2", _BF, {"wgrad_rt"})],
+    43: [("form1", _BF, {"wgrad_rt"}), ("form2", _BF, {"wgrad_rt"})],
+    44: [("form1", _BF, {"wgrad_rt"}), ("form2", _BF, {"wgrad_rt"})],
+}
+_EXACT_SEEN = {}         # (case index, dtype, form) -> {form: launches} of the exact twin in this process
+
+
+def _exact_case(ci, dtype, form):
+    from tests import conv_exact as X
+    B, Hi, Wi, C0, C1, up0, up1, Cout, stride = CASES[ci]
+    lay = X.Layer(B, Hi, Wi, C0, C1, up0, up1, Cout, stride)
+    g = torch.Generator(device=dev()).manual_seed(1000 * ci + 7)
+    forms = X.check_layer(lay, dtype, g, dev())
+    X.check_forms(lay, dtype, forms)
+    hit = {}
+    for f in forms.values():
+        for k, v in f.items():
+            hit[k] = hit.get(k, 0) + v
+    for want_form, dts, names in CASE_FORMS.get(ci, ()):
+        if want_form == form and dtype in dts:
+            assert any(hit.get(n, 0) for n in names), f"case {ci} {CASES[ci]} {dtype} {form}: none of {sorted(names)} ran; {forms}"
+    _EXACT_SEEN[(ci, dtype, form)] = hit
+    return hit
+
+
+@pytest.mark.parametrize("form", ["form0", "form1", "form2"])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("ci", range(len(CASES)))
+def test_conv_exact_data_bit_for_bit(ci, dtype, form):
+    """test_conv_fwd_dgrad_wgrad's cases, dtypes and kernel forms on exact data (tests/conv_exact.py): every pass -- forward, input
+    gradients plain / masked + accumulate / both sources in one launch, weight gradient in the atomic, clean-arena, deterministic and
+    slab forms and accumulating -- equal BY VALUE to the float64 reference rounded once to the output dtype; and the kernel each case's
+    comment names ran (CASE_FORMS)."""
+    _exact_case(ci, dtype, form)
+
+
+def test_conv_exact_data_wide_form():
+    """The one-tile kernel's 512-thread / 256-pixel form (tuning `wide`, off by default -- no production shape and no case above reaches
+    it): on, from any grid, at a two-chunk stride-1 layer whose 256-pixel tiles fit; bit for bit as above."""
+    from coivo_amd import _lib
+    from tests import conv_exact as X
+    saved = {n: _lib.tune_get(n) for n in ("wide", "wide_min_wgs")}
+    try:
+        _lib.tune_set("wide", 1)
+        _lib.tune_set("wide_min_wgs", 0)
+        for dtype in (torch.bfloat16, torch.float32):
+            lay = X.Layer(2, 32, 48, 64, 0, False, False, 64, 1)
+            forms = X.check_layer(lay, dtype, torch.Generator(device=dev()).manual_seed(9), dev())
+            X.check_forms(lay, dtype, forms)
+            assert forms["fwd"].get("conv_wide") == 1, (dtype, forms)
+            _EXACT_SEEN[("wide", dtype)] = forms["fwd"]
+    finally:
+        for n, v in saved.items():
+            _lib.tune_set(n, v)
+
+
+def test_every_kernel_form_is_covered():
+    """The forms the exact small cases reach, with those the production sweep asserts (test_conv_exact_gpu.PRODUCTION_FORMS), are
+    every counter the library reports.  Cases not yet run in this process are run here."""
+    from coivo_amd import _lib
+    from tests.test_conv_exact_gpu import PRODUCTION_FORMS
+    for ci in range(len(CASES)):
+        for dtype in (torch.float32, torch.bfloat16):
+            for form in ("form0", "form1", "form2"):
+                if (ci, dtype, form) not in _EXACT_SEEN:
+                    saved = _set_form(form, dtype)
+                    try:
+                        _exact_case(ci, dtype, form)
+                    finally:
+                        _restore(saved)
+    if ("wide", torch.bfloat16) not in _EXACT_SEEN:
+        test_conv_exact_data_wide_form()
+    small = set()
+    for hit in _EXACT_SEEN.values():
+        small |= {k for k, v in hit.items() if v}
+    every = set(_lib.form_counts())
+    assert len(every) == 27
+    assert small | PRODUCTION_FORMS == every, sorted(every - small - PRODUCTION_FORMS)
+    print(f"forms only the production sweep reaches: {sorted(PRODUCTION_FORMS - small)}")
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
