@@ -95,6 +95,10 @@ enum { FORM_CONV_RT = 0, FORM_WGRAD_FULL_GRID, FORM_WGRAD_HALVED_GRID, FORM_WGRA
        FORM_COUNT };
 static_assert(FORM_COUNT <= 32, "coivo_amd/_lib.py form_counts reads 32 counters");
 void form_hit(int id);
+constexpr uint32_t form_bit(int id) { return 1u << id; }
+inline void form_hits(uint32_t mask) {          // every FORM_f whose form_bit is in mask
+    for (; mask; mask &= mask - 1) form_hit(__builtin_ctz(mask));
+}
 
 // csrc/bwd16.hip: the MFMA form of colvo_conv_dgrad_planes (bf16, stride 2, 16 output channels, two input channels, even extents)
 int launch_dgrad_planes_s2_mfma(const void* g, const float* w, int Cin, int c_begin, int B, int Hi, int Wi, int Ho, int Wo, float* dst,

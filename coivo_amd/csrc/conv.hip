@@ -1384,34 +1384,307 @@ __global__ __launch_bounds__(NT) void k_conv3x3_res(const ConvK a, int ntiles, u
 // --------------------------------------------------------------------------------------------- //
 // host side                                                                                      //
 // --------------------------------------------------------------------------------------------- //
-// one launch of a one-tile kernel over the grid of tile_grid
-template <auto Kernel>
-int launch_tiles(ConvK k, int BN, int B, int nthreads, size_t lds, hipStream_t s, const char* name) {
-    const long long nwg = tile_grid(k, BN, B);
+// Every call plans first (conv_plan: form, instantiation, tile, grid, LDS and form counters; no HIP call, no counter moved) and
+// then runs the plan (launch_plan).
+enum { PASS_FWD, PASS_DGRAD, PASS_DGRAD_BOTH };
+
+// The LDS and 1-D grid of a one-tile kernel (k_conv3x3, k_conv_up2, k_dgrad_up2, k_dgrad_s2) over the tile k carries
+int plan_tiles(ConvK& k, int B, ConvPlan& p, size_t lds, size_t lds_max, const char* what, const char* name) {
+    COLVO_CHECK_ARG(lds <= lds_max, "%s: tile needs %zu bytes of LDS", what, lds);
+    const long long nwg = set_tile_grid(k, p.bn, B);
     COLVO_CHECK_ARG(nwg < (1ll << 30), "%s: too many workgroups", name);
-    colvo::launch(Kernel, dim3((unsigned)nwg), dim3(nthreads), lds, s, k);
+    p.lds = lds;
+    p.grid = dim3((unsigned)nwg);
+    return 0;
+}
+
+// LDS of k_conv3x3: weight slab and patch, or the epilogue's output tile where that is larger
+size_t conv3x3_lds(const ConvK& k, const ConvPlan& p) {
+    const int steps = (9 * p.ng + 3) / 4;
+    const int pixp = p.tail ? pitch_bytes_s2(p.ng * 16) : pitch_bytes(p.ng * 16);
+    const int ph = (k.toh - 1) * k.g.stride + 3;
+    const size_t lds = (size_t)p.bn * wrow_bytes(steps * 4) + (size_t)ph * k.pwp * pixp;
+    return std::max(lds, (size_t)(p.nth / 2) * (p.bn + 4) * 4);
+}
+
+// k_conv3x3_res, the weights-resident persistent kernel (stride 2: with the next tile's patch in flight)
+int plan_conv_res(const ConvK& k, int B, bool s2, ConvPlan& p) {
+    const int steps = (9 * p.ng + 3) / 4;
+    const int pixp = s2 ? pitch_bytes_s2(p.ng * 16) : pitch_bytes(p.ng * 16);
+    const int ph = (k.toh - 1) * (s2 ? 2 : 1) + 3;
+    p.lds = (size_t)p.bn * wrow_bytes(steps * 4) + std::max((size_t)ph * k.pwp * pixp, (size_t)BM * (p.bn + 4) * 4);
+    COLVO_CHECK_ARG(p.lds <= 160 * 1024, "conv (weights-resident): tile needs %zu bytes of LDS", p.lds);
+    p.ntiles = k.tiles_x * k.tiles_y * B;
+    // workgroups per CU, each walking ntiles / gx tiles (stride 2: as many as its LDS footprint lets a CU hold)
+    const int per_cu = s2 ? std::max(1, std::min((int)TUNE(res_wg_per_cu), (int)(160 * 1024 / p.lds))) : (int)TUNE(res_wg_per_cu);
+    p.grid = dim3(std::min(256 * per_cu, p.ntiles), (k.N + p.bn - 1) / p.bn, 1);
+    p.m_tpi = mdiv_magic(k.tiles_x * k.tiles_y);
+    p.m_tx = mdiv_magic(k.tiles_x);
+    p.form = s2 ? CONV_RES_S2 : CONV_RES;
+    p.forms |= form_bit(s2 ? FORM_CONV_RES_S2 : FORM_CONV_RES) | (p.bn == 64 ? form_bit(FORM_CONV_BN64) : 0);
+    return 0;
+}
+
+// stride-2 single-chunk layers on large grids: weights-resident persistent kernel with the next tile's patch in flight (see
+// k_conv3x3_res)
+bool res_s2_fits(const ConvK& k, int B, int ng, int G, int ES) {
+    if (!TUNE(res_s2) || k.g.stride != 2 || k.nsplit != 0 || k.pool2 || k.g.C[1] != 0 || k.g.mode[0] != MODE_DIRECT) return false;
+    if (k.g.C[0] != ng * G || k.accumulate || k.mask) return false;   // one chunk; forward only (its input gradient is k_dgrad_s2)
+    const long long src_bytes = (long long)B * k.g.Hs[0] * k.g.Ws[0] * k.g.C[0] * ES;
+    const long long out_bytes = (long long)B * k.Ho * k.Wo * k.N * ES;
+    const long long tpi = (long long)k.tiles_x * k.tiles_y;
+    if (src_bytes >= 0x40000000LL || out_bytes >= 0x40000000LL || tpi < 2 || k.tiles_x < 2 || tpi * tpi * B >= 0x100000000LL) return false;
+    if (tpi * B < TUNE(res_s2_min_tiles)) return false;
+    const long ptotal = (long)((k.toh - 1) * 2 + 3) * ((k.tow - 1) * 2 + 3) * ng;
+    if (ptotal > (long)((17 * 33 * ng + NT - 1) / NT) * NT) return false;        // (what the kernel's register prefetch holds)
+    return k.N >= 32 && (ng == 4 || ng == 2);
+}
+
+// k_conv3x3's tile t
+inline void set_tile(ConvK& k, const Tile& t) {
+    const int pw = (t.tow - 1) * k.g.stride + 3;
+    // patches beyond 3 x 256 granules are staged partly by the linear tail loop: no row padding there
+    const bool tail = (long)((t.toh - 1) * k.g.stride + 3) * pw * 4 > 3 * NT;
+    apply_tile(k, t, pw, tail ? pw : std::max(t.pwp, pw));
+}
+
+// The one-tile kernel k_conv3x3 and its weights-resident form k_conv3x3_res
+int plan_conv_t(ConvK& k, int B, int G, int ES, ConvPlan& p) {
+    const bool even = k.pool2 != 0;        // tile extents must be even (2x2 sum-pool epilogue)
+    int ng = 4;
+    for (int i = 0; i < 2; ++i)
+        if (k.g.C[i] > 0) while (ng > 1 && (k.g.C[i] % (ng * G)) != 0) ng >>= 1;
+    for (int i = 0; i < 2; ++i)
+        COLVO_CHECK_ARG(k.g.C[i] % (ng * G) == 0, "conv: channel count %d is not a multiple of %d", k.g.C[i], G);
+    p.ng = ng;
+    p.depth = 1;
+    // Wide form (512 threads, 256 pixels x BN channels): multi-chunk stride-1 layers whose 256-pixel grid still covers the
+    // chip.  Per MFMA it stages 100 (BN 64) / 136 (BN 32) bytes instead of 208, and the CUs' bytes in flight are what bounds
+    // these layers.
+    {
+        // off by default: at B = 16 the 256-pixel grids are 1-1.25 workgroups per CU and measured 10-20 % slower (up3 18.9 ->
+        // 21.7 us; gpurun_out/r2_bench_conv_w*.log); the form pays once the grid covers the chip several times (configs[2])
+        const int wide_on = (int)TUNE(wide);                 // tuning knob
+        const long wide_min_wgs = TUNE(wide_min_wgs);   // tuning knob
+        const int wide_min_chunks = (int)TUNE(wide_min_chunks);
+        const int nch = (k.g.C[0] + k.g.C[1]) / (ng * G);
+        if (wide_on && k.nsplit == 0 && k.g.stride == 1 && k.N >= 32 && nch >= wide_min_chunks) {
+            const Tile tw = pick_tile(k.Ho, k.Wo, 1, even, 256);
+            const long patch = (long)(tw.toh + 2) * (tw.tow + 2) * ng;
+            const int bn = k.N >= 64 ? 64 : 32;
+            const long wgs = (long)((k.Ho + tw.toh - 1) / tw.toh) * ((k.Wo + tw.tow - 1) / tw.tow) * B * ((k.N + bn - 1) / bn);
+            if (patch <= 3 * 512 && tw.toh * tw.tow > 128 && wgs >= wide_min_wgs) {
+                set_tile(k, tw);
+                p.form = CONV_TILE;
+                p.bn = bn;
+                p.nth = 512;
+                p.forms |= form_bit(FORM_CONV_WIDE) | (bn == 64 ? form_bit(FORM_CONV_BN64) : 0);
+                return plan_tiles(k, B, p, conv3x3_lds(k, p), 160 * 1024, "conv", "k_conv3x3");
+            }
+        }
+    }
+    set_tile(k, pick_tile(k.Ho, k.Wo, k.g.stride, even, 128, true));
+    if (res_s2_fits(k, B, ng, G, ES)) {
+        p.bn = k.N >= 64 ? 64 : 32;
+        return plan_conv_res(k, B, true, p);
+    }
+    // Output-channel tile: 64 wide by default; when that grid would leave CUs idle (deep, low-resolution layers at small
+    // batch) use 32 -- twice the workgroups, each staging half the weight slab per chunk (the chunk is LDS-bound).
+    const long tiles = (long)k.tiles_x * k.tiles_y * B;
+    const long bn64_min_wgs = TUNE(bn64_min_wgs);   // tuning knob
+    const long bn32_min_wgs = TUNE(bn32_min_wgs);      // tuning knob (16-wide tiles: measured ~neutral)
+    // (two-output form: a channel tile must not straddle the two sources -- nsplit is a multiple of 32)
+    if (k.nsplit == 0 && k.N >= 64 && tiles * ((k.N + 63) / 64) >= bn64_min_wgs) {
+        p.bn = 64;
+        p.forms |= form_bit(FORM_CONV_BN64);
+    } else {
+        p.bn = k.N >= 32 && tiles * ((k.N + 31) / 32) >= bn32_min_wgs ? 32 : 16;
+    }
+    // single-chunk layers with narrow outputs: weights-resident persistent kernel
+    if (p.bn <= 32) {
+        const long long src_bytes = (long long)B * k.g.Hs[0] * k.g.Ws[0] * k.g.C[0] * ES;
+        const long long out_bytes = (long long)B * k.Ho * k.Wo * k.N * ES / (k.pool2 ? 4 : 1);
+        const long long tpi = (long long)k.tiles_x * k.tiles_y;
+        const long res_min_tiles = TUNE(res_min_tiles);   // tuning knob
+        if (k.nsplit == 0 && k.g.C[1] == 0 && k.g.C[0] == ng * G && k.g.stride == 1 && src_bytes < 0x40000000LL &&
+            out_bytes < 0x40000000LL && tpi >= 2 && k.tiles_x >= 2 && tpi * tpi * B < 0x100000000LL &&   // magic-division ranges
+            tpi * B >= res_min_tiles)
+            return plan_conv_res(k, B, false, p);
+    }
+    // many-chunk layers at the lowest resolutions: two chunks in flight, because one MFMA phase (~0.5 us) is shorter than the
+    // global-load latency it is supposed to hide
+    if (p.bn == 32 && ng == 4) {
+        // measured: pays only when the grid is about one workgroup per CU (it costs occupancy: ~190 VGPRs)
+        const int depth2_min = (int)TUNE(depth2_min_chunks);
+        const long lone_max = TUNE(lone_max_wgs);
+        const long wgs = tiles * ((k.N + 31) / 32);
+        if (wgs <= lone_max && (k.g.C[0] + k.g.C[1]) / (4 * G) >= depth2_min) p.depth = 2;   // (a three-chunk ring measured no better)
+    }
+    p.forms |= form_bit(p.depth == 2 ? FORM_CONV_RING : FORM_CONV_TILE);
+    // (A persistent multi-chunk form -- grid = resident slots, a workgroup walks several pixel tiles with the register prefetch
+    // running through the tile boundary -- was built and measured this round: 5-25 % SLOWER on every DepthNet layer at B = 16
+    // (up3 18.8 -> 22.7 us): it needs 162 VGPRs, i.e. 3 instead of 4 resident workgroups per CU, and an evened-out walk leaves
+    // 2.5 workgroups per CU.  Removed; DESIGN.md section 3.2.)
+    const int S = k.g.stride;
+    p.tail = (long)((k.toh - 1) * S + 3) * ((k.tow - 1) * S + 3) * ng > 3 * NT;   // (the ring's tail form keeps two chunks: three would spill)
+    if (!p.tail && p.depth == 2) {
+        const int nch = (k.g.C[0] + k.g.C[1]) / (ng * G);
+        if (nch == 8 || nch == 16) p.nch = nch;
+    }
+    p.form = CONV_TILE;
+    return plan_tiles(k, B, p, conv3x3_lds(k, p), 160 * 1024, "conv", "k_conv3x3");
+}
+
+// quad-tile stride-1 kernel (k_conv_q); false: the layer does not qualify
+bool plan_conv_q(ConvK& k, int B, int G, int ES, ConvPlan& p) {
+    const int CK = 4 * G;
+    const int q_on = (int)TUNE(conv_quad);
+    // Measured (bf16; us, one-tile -> quad).  16 frames of 256x320: slower everywhere (enc2b 14.8 -> 23.5, iconv3 19.0 -> 34.2,
+    // iconv2 22.0 -> 24.2, enc5b 17.1 -> 42.1).  64 frames of 512x640: the 2-4-chunk layers at 1/2-1/4 resolution win (enc2b 199 ->
+    // 153, iconv3 265 -> 217, iconv2 370 -> 275), the 8-16-chunk layers lose to the one-tile kernel's two-chunk ring (enc4b 122 ->
+    // 164, iconv5 215 -> 297).  Hence: at least 2048 quad-tile workgroups and at most 4 chunks.
+    const long min_wgs = TUNE(quad_min_wgs);          // (the tests lower / raise these two through colvo_tune_set)
+    const int max_chunks = (int)TUNE(quad_max_chunks);
+    const Gather& g = k.g;
+    if (!q_on || g.stride != 1 || k.pool2 || g.mode[0] != MODE_DIRECT || (g.C[1] > 0 && g.mode[1] != MODE_DIRECT)) return false;
+    if (g.C[0] % CK || g.C[1] % CK || (g.C[0] + g.C[1]) / CK < 2 || (g.C[0] + g.C[1]) / CK > max_chunks) return false;
+    if ((long long)g.Hi * g.Wi * std::max(g.C[0], g.C[1]) * ES >= 0x40000000LL || (long long)k.Ho * k.Wo * k.N * ES >= 0x40000000LL)
+        return false;
+    ConvK q = k;
+    const Tile t = pick_tile((q.Ho + 1) / 2, (q.Wo + 1) / 2, 1, false, 128, true, 3);   // the sub-tile: at most half the image each way
+    const int PH = 2 * t.toh + 2, PW = 2 * t.tow + 2;
+    if (PH * PW * 4 > 10 * NT) return false;
+    // sub-tile reads are conflict-free when the sub-tile's own rows are (pick_tile) AND the patch pitch keeps the row phase:
+    // keep the padding pick_tile chose relative to ITS patch width (tow + 2)
+    apply_tile(q, t, PW, PW + std::max(0, t.pwp - (t.tow + 2)), 2);
+    const long tiles = (long)q.tiles_x * q.tiles_y * B;
+    const int bn = (q.N > 16 && tiles * ((q.N + 31) / 32) >= min_wgs) ? 32 : 16;
+    if (tiles * ((q.N + bn - 1) / bn) < min_wgs) return false;
+    const size_t lds = (size_t)bn * wrow_bytes(36) + (size_t)PH * q.pwp * pitch_bytes(64);
+    if (lds > 160 * 1024) return false;
+    p.grid = dim3((unsigned)set_tile_grid(q, bn, B));
+    k = q;
+    p.form = CONV_Q;
+    p.bn = bn;
+    p.lds = lds;
+    p.forms |= form_bit(FORM_CONV_Q);
+    return true;
+}
+
+// The launch of colvo_conv_fwd (PASS_FWD), colvo_conv_dgrad (PASS_DGRAD; `up`: the source is up-sampled; k from dgrad_conv) or
+// colvo_conv_dgrad_both's merged launch (PASS_DGRAD_BOTH).  Sets k's tile and grid fields, and the extents and source mode of
+// the form it picks.  Reads the tuning table, calls no HIP, counts no form.
+int conv_plan(const ColvoConvDesc* d, int pass, int up, ConvK& k, ConvPlan& p) {
+    const int B = d->B, G = d->dtype == COLVO_F32 ? 4 : 8, ES = d->dtype == COLVO_F32 ? 4 : 2;
+    const int ck = 4 * G;                     // 32 (bf16) / 16 (f32) channels: a chunk of the MFMA kernels
+    const long long y_bytes = (long long)d->Ho * d->Wo * d->Cout * ES;      // the forward output; the input gradient's dy
+    p.nth = NT;
+    if (pass == PASS_FWD) {
+        // single up-sampled source in whole 32-channel chunks: four output pixels per source position (k_conv_up2; the one-chunk
+        // full-resolution layer up1 too: 23.2 -> 18.4 us against the weights-resident one-tile kernel)
+        const int up2_on = (int)TUNE(conv_up2);
+        const long long in_bytes = (long long)(d->Hi / 2) * (d->Wi / 2) * d->C0 * ES;
+        const int up2_min_chunks = (int)TUNE(up2_min_chunks);   // tuning knob
+        if (up2_on && d->up0 && d->C1 == 0 && d->stride == 1 && d->C0 % ck == 0 && d->C0 / ck >= up2_min_chunks &&
+            in_bytes < 0x40000000LL && y_bytes < 0x40000000LL) {
+            ConvK u = k;
+            u.g.mode[0] = MODE_DIRECT;                    // read the stored half-size source as it is
+            u.g.Hi = d->Hi / 2; u.g.Wi = d->Wi / 2;
+            u.Ho = d->Hi / 2; u.Wo = d->Wi / 2;           // tiles run over source positions; the kernel writes (2 Ho) x (2 Wo)
+            const Tile t = pick_tile(u.Ho, u.Wo, 1, false, 128, true, 3);
+            if ((t.toh + 2) * (t.tow + 2) * 4 <= 3 * NT) {
+                apply_tile(u, t, t.tow + 2, std::max(t.pwp, t.tow + 2));
+                // 16-wide channel tiles while 32-wide ones would leave CUs without a workgroup
+                const long bn16_max = TUNE(up2_bn16_max_wgs);   // tuning knob
+                const long wgs32 = (long)u.tiles_x * u.tiles_y * B * ((u.N + 31) / 32);
+                const int nch = u.g.C[0] / ck;
+                k = u;
+                p.form = CONV_UP2;
+                p.bn = k.N > 16 && wgs32 > bn16_max ? 32 : 16;
+                p.nch = nch == 8 || nch == 16 ? nch : 0;
+                p.forms |= form_bit(p.bn == 32 ? FORM_CONV_UP2_BN32 : FORM_CONV_UP2_BN16);
+                return plan_tiles(k, B, p, (size_t)p.bn * wrow_bytes(36) + (size_t)(k.toh + 2) * k.pwp * pitch_bytes(64), 48 * 1024,
+                                  "conv (up-sampled source)", "k_conv_up2");
+            }
+        }
+    }
+    if (pass == PASS_DGRAD) {
+        // stride 2, even input extent, 32-channel chunks of dy: the parity-decomposed kernel (a quarter of the MFMAs)
+        const int s2_on = (int)TUNE(dgrad_s2);
+        const long long dx_bytes = (long long)d->Hi * d->Wi * k.N * ES;
+        if (s2_on && d->stride == 2 && !up && d->Hi == 2 * d->Ho && d->Wi == 2 * d->Wo && d->Cout % ck == 0 &&
+            dx_bytes < 0x40000000LL && y_bytes < 0x40000000LL) {
+            // tiles run over dy; the kernel writes a (2 Ho) x (2 Wo) image
+            const Tile t = pick_tile(k.Ho, k.Wo, 1, false, 128, true, 2);
+            apply_tile(k, t, t.tow + 1, std::max(t.pwp, t.tow + 1));
+            p.form = DGRAD_S2;
+            p.bn = k.N > 16 ? 32 : 16;
+            const int nch = k.g.C[0] / ck;
+            const long wgs = (long)k.tiles_x * k.tiles_y * B * ((k.N + p.bn - 1) / p.bn);
+            const long lone_max = TUNE(lone_max_wgs);
+            // about one workgroup per CU: two chunks in flight, K loop unrolled (see the two-chunk ring in plan_conv_t)
+            if (wgs <= lone_max && (nch == 8 || nch == 16)) p.nch = nch;
+            p.forms |= form_bit(p.nch ? FORM_DGRAD_S2_RING : FORM_DGRAD_S2);
+            return plan_tiles(k, B, p, (size_t)p.bn * wrow_bytes(36) + (size_t)(k.toh + 1) * k.pwp * pitch_bytes(64), 48 * 1024,
+                              "dgrad (stride 2)", "k_dgrad_s2");
+        }
+        // up-sampled source, stride 1, 32-channel chunks of dy: the 2x2 sum-pool folded into the K loop (k_dgrad_up2)
+        const int up2_on = (int)TUNE(dgrad_up2);
+        const long long dxs_bytes = (long long)(d->Hi / 2) * (d->Wi / 2) * k.N * ES;
+        if (up2_on && up && d->stride == 1 && d->Cout % (ck / 2) == 0 && dxs_bytes < 0x40000000LL && y_bytes < 0x40000000LL) {
+            ConvK u = k;
+            u.Ho = d->Hi / 2; u.Wo = d->Wi / 2;          // tiles and output: the stored half-size source
+            const Tile t = pick_tile(u.Ho, u.Wo, 2, false, 128, true, 4);   // patch rows of 2 tow + 2 pixels, pixel stride 2
+            if ((2 * t.toh + 2) * (2 * t.tow + 2) * 4 <= 10 * NT) {                 // (x NG / 4 granules <= PPF x 256 for either NG)
+                apply_tile(u, t, 2 * t.tow + 2, std::max(t.pwp, 2 * t.tow + 2));
+                // only where the grid still covers the chip: at batch 16 the 1/8- and 1/16-resolution layers measured 1-2 us
+                // SLOWER in this form (up5 19.4 -> 21.0, up4 18.2 -> 19.4; up3 20.7 -> 19.4, up2 26.8 -> 19.1)
+                // (read at every call, not once: the tests switch it to reach this kernel with small shapes)
+                const long min_wgs = TUNE(dgrad_up2_min_wgs);
+                const long wgs32 = (long)u.tiles_x * u.tiles_y * B * ((u.N + 31) / 32);
+                if (wgs32 >= min_wgs) {
+                    const int nch = u.g.C[0] / ck;
+                    k = u;
+                    p.form = DGRAD_UP2;
+                    p.bn = k.N > 16 ? 32 : 16;
+                    p.ng = k.g.C[0] % ck ? 2 : 4;                 // 2-granule chunks where dy is not in whole 4-granule ones
+                    p.nch = p.ng == 4 && (nch == 8 || nch == 16) ? nch : 0;
+                    p.forms |= form_bit(FORM_DGRAD_UP2);
+                    const size_t lds = (size_t)p.bn * wrow_bytes((9 * p.ng + 3) / 4 * 4) + (size_t)(2 * k.toh + 2) * k.pwp * pitch_bytes(p.ng * 16);
+                    return plan_tiles(k, B, p, lds, 160 * 1024, "dgrad (up-sampled source)", "k_dgrad_up2");
+                }
+            }
+        }
+        // the conv input is dy (Cout channels), dilated by zero insertion when the forward stride was 2
+        if (d->stride == 2) { k.g.mode[0] = MODE_DILATE; k.g.Hi = 2 * d->Ho; k.g.Wi = 2 * d->Wo; }
+        k.Ho = d->Hi; k.Wo = d->Wi;                    // gradient w.r.t. the (virtual) forward input
+        k.pool2 = up;
+    }
+    // large grids of ordinary stride-1 layers: the register-tiled kernel (conv_rt.hip), then the quad-tile kernel (not for the
+    // merged input gradient).  Both take direct stride-1 sources only: dilated and pooled input gradients skip them.
+    if (conv_rt_plan(k, B, d->dtype, p) || (pass != PASS_DGRAD_BOTH && plan_conv_q(k, B, G, ES, p))) return 0;
+    return plan_conv_t(k, B, G, ES, p);
+}
+
+// one launch of plan p as kernel instantiation Kernel: the dynamic-LDS opt-in, the plan's form counters, the launch
+template <auto Kernel, typename... A>
+int run_plan(const ConvK& k, const ConvPlan& p, hipStream_t s, const char* name, A... args) {
+    if (int e = allow_dynamic_lds<Kernel>(p.lds, 160 * 1024, p.form == DGRAD_UP2 ? "dgrad" : "conv")) return e;
+    form_hits(p.forms);
+    colvo::launch(Kernel, p.grid, dim3(p.nth), (unsigned)p.lds, s, k, args...);
     COLVO_CHECK_LAUNCH(name);
     return 0;
 }
 
 template <typename T, int BN, int NG, int DEPTH, bool TAIL, int NCH = 0, int NTH = 256>
-int launch_conv_tail(const ConvK& k, int B, hipStream_t s) {
-    constexpr int STEPS = (9 * NG + 3) / 4;
-    constexpr int WROW = wrow_bytes(STEPS * 4), PIXP = TAIL ? pitch_bytes_s2(NG * 16) : pitch_bytes(NG * 16);
-    const int S = k.g.stride;
-    const int PH = (k.toh - 1) * S + 3;
-    size_t lds = (size_t)BN * WROW + (size_t)PH * k.pwp * PIXP;
-    const size_t eplds = (size_t)(NTH / 2) * (BN + 4) * 4;
-    if (eplds > lds) lds = eplds;
-    COLVO_CHECK_ARG(lds <= 160 * 1024, "conv: tile needs %zu bytes of LDS", lds);
-    if (int e = allow_dynamic_lds<k_conv3x3<T, BN, NG, DEPTH, TAIL, NCH, NTH>>(lds, 160 * 1024, "conv")) return e;
+int launch_conv3x3(const ConvK& k, const ConvPlan& p, hipStream_t s) {
 #ifdef COLVO_ABLATE
     ConvK ka = k;
     { const char* e = getenv("COLVO_ABL"); ka.abl = e ? atoi(e) : 0; }
     ka.trace = nullptr;
     static long long* tbuf = nullptr;
     static int tcount = 0;
-    const dim3 grid((unsigned)tile_grid(ka, BN, B));
+    const dim3 grid = p.grid;
     const size_t nwg = grid.x;
     const bool tracing = getenv("COLVO_TRACE") && nwg <= (1u << 16);
     if (tracing) {
@@ -1419,7 +1692,7 @@ int launch_conv_tail(const ConvK& k, int B, hipStream_t s) {
         hipMemsetAsync(tbuf, 0, nwg * 8 * sizeof(long long), s);
         ka.trace = tbuf;
     }
-    if (int e = launch_tiles<k_conv3x3<T, BN, NG, DEPTH, TAIL, NCH, NTH>>(ka, BN, B, NTH, lds, s, "k_conv3x3")) return e;
+    if (int e = run_plan<k_conv3x3<T, BN, NG, DEPTH, TAIL, NCH, NTH>>(ka, p, s, "k_conv3x3")) return e;
     if (tracing && (++tcount % atoi(getenv("COLVO_TRACE"))) == 0) {     // every n-th launch: print the phase statistics
         hipStreamSynchronize(s);
         std::vector<long long> h(nwg * 8);
@@ -1442,293 +1715,81 @@ int launch_conv_tail(const ConvK& k, int B, hipStream_t s) {
     }
     return 0;
 #endif
-    return launch_tiles<k_conv3x3<T, BN, NG, DEPTH, TAIL, NCH, NTH>>(k, BN, B, NTH, lds, s, "k_conv3x3");
+    return run_plan<k_conv3x3<T, BN, NG, DEPTH, TAIL, NCH, NTH>>(k, p, s, "k_conv3x3");
 }
 
-template <typename T, int BN, int NG, int DEPTH = 1>
-int launch_conv(const ConvK& k, int B, hipStream_t s) {
-    const int S = k.g.stride;
-    const long ptotal = (long)((k.toh - 1) * S + 3) * ((k.tow - 1) * S + 3) * NG;
-    // (A persistent multi-chunk form -- grid = resident slots, a workgroup walks several pixel tiles with the register prefetch
-    // running through the tile boundary -- was built and measured this round: 5-25 % SLOWER on every DepthNet layer at B = 16
-    // (up3 18.8 -> 22.7 us): it needs 162 VGPRs, i.e. 3 instead of 4 resident workgroups per CU, and an evened-out walk leaves
-    // 2.5 workgroups per CU.  Removed; DESIGN.md section 3.2.)
-    if (ptotal > 3 * NT) return launch_conv_tail<T, BN, NG, (DEPTH > 2 ? 2 : DEPTH), true>(k, B, s);   // depth 3 would spill
-    if constexpr (DEPTH >= 2) {
-        const int nch = (k.g.C[0] + k.g.C[1]) / (NG * TT<T>::G);
-        if (nch == 8) return launch_conv_tail<T, BN, NG, DEPTH, false, 8>(k, B, s);
-        if (nch == 16) return launch_conv_tail<T, BN, NG, DEPTH, false, 16>(k, B, s);
-    }
-    return launch_conv_tail<T, BN, NG, DEPTH, false>(k, B, s);
-}
-
-template <typename T, int BN, int NG, bool S2 = false>
-int launch_conv_res(const ConvK& k, int B, hipStream_t s) {
-    constexpr int STEPS = (9 * NG + 3) / 4;
-    constexpr int WROW = wrow_bytes(STEPS * 4), PIXP = S2 ? pitch_bytes_s2(NG * 16) : pitch_bytes(NG * 16);
-    const int PH = (k.toh - 1) * (S2 ? 2 : 1) + 3;
-    const size_t p_or_out = std::max((size_t)PH * k.pwp * PIXP, (size_t)BM * (BN + 4) * 4);
-    const size_t lds = (size_t)BN * WROW + p_or_out;
-    COLVO_CHECK_ARG(lds <= 160 * 1024, "conv (weights-resident): tile needs %zu bytes of LDS", lds);
-    if (int e = allow_dynamic_lds<k_conv3x3_res<T, BN, NG, S2>>(lds, 160 * 1024, "conv")) return e;
-    const int ntiles = k.tiles_x * k.tiles_y * B;
-    // workgroups per CU, each walking ntiles / gx tiles (stride 2: as many as its LDS footprint lets a CU hold)
-    const int per_cu = S2 ? std::max(1, std::min((int)TUNE(res_wg_per_cu), (int)(160 * 1024 / lds))) : (int)TUNE(res_wg_per_cu);
-    int gx = 256 * per_cu;
-    if (gx > ntiles) gx = ntiles;
-    dim3 grid(gx, (k.N + BN - 1) / BN, 1);
-    form_hit(S2 ? FORM_CONV_RES_S2 : FORM_CONV_RES);
-    if (BN == 64) form_hit(FORM_CONV_BN64);
-    colvo::launch((k_conv3x3_res<T, BN, NG, S2>), grid, dim3(NT), lds, s, k, ntiles, mdiv_magic(k.tiles_x * k.tiles_y),
-                       mdiv_magic(k.tiles_x));
-    COLVO_CHECK_LAUNCH("k_conv3x3_res");
-    return 0;
-}
-
-// stride-2 single-chunk layers on large grids: weights-resident persistent kernel with the next tile's patch in flight (see
-// k_conv3x3_res).  -1: the layer does not qualify.
-template <typename T>
-int try_launch_conv_res_s2(const ConvK& k, int B, int ng, hipStream_t s) {
-    if (!TUNE(res_s2) || k.g.stride != 2 || k.nsplit != 0 || k.pool2 || k.g.C[1] != 0 || k.g.mode[0] != MODE_DIRECT) return -1;
-    if (k.g.C[0] != ng * TT<T>::G || k.accumulate || k.mask) return -1;       // one chunk; forward only (its input gradient is k_dgrad_s2)
-    const long long src_bytes = (long long)B * k.g.Hs[0] * k.g.Ws[0] * k.g.C[0] * TT<T>::ES;
-    const long long out_bytes = (long long)B * k.Ho * k.Wo * k.N * TT<T>::ES;
-    const long long tpi = (long long)k.tiles_x * k.tiles_y;
-    if (src_bytes >= 0x40000000LL || out_bytes >= 0x40000000LL || tpi < 2 || k.tiles_x < 2 || tpi * tpi * B >= 0x100000000LL) return -1;
-    if (tpi * B < TUNE(res_s2_min_tiles)) return -1;
-    const long ptotal = (long)((k.toh - 1) * 2 + 3) * ((k.tow - 1) * 2 + 3) * ng;
-    if (ptotal > (long)((17 * 33 * ng + NT - 1) / NT) * NT) return -1;        // (what the kernel's register prefetch holds)
-    if (k.N >= 64) {
-        switch (ng) {
-            case 4: return launch_conv_res<T, 64, 4, true>(k, B, s);
-            case 2: return launch_conv_res<T, 64, 2, true>(k, B, s);
-            default: return -1;
-        }
-    }
-    if (k.N >= 32) {
-        switch (ng) {
-            case 4: return launch_conv_res<T, 32, 4, true>(k, B, s);
-            case 2: return launch_conv_res<T, 32, 2, true>(k, B, s);
-            default: return -1;
-        }
-    }
-    return -1;
-}
-
+// a CONV_TILE plan with channel tile BN: the 512-thread form (BN 64 / 32), the two-chunk ring (BN 32, NG 4), one chunk in flight
 template <typename T, int BN>
-int launch_conv_ng(const ConvK& k, int B, int ng, hipStream_t s) {
-    // single-chunk layers with narrow outputs: weights-resident persistent kernel
-    if constexpr (BN <= 32) {
-        const int ck = ng * TT<T>::G;
-        const long long src_bytes = (long long)B * k.g.Hs[0] * k.g.Ws[0] * k.g.C[0] * TT<T>::ES;
-        const long long out_bytes = (long long)B * k.Ho * k.Wo * k.N * TT<T>::ES / (k.pool2 ? 4 : 1);
-        const long long tpi = (long long)k.tiles_x * k.tiles_y;
-        const long res_min_tiles = TUNE(res_min_tiles);   // tuning knob
-        if (k.nsplit == 0 && k.g.C[1] == 0 && k.g.C[0] == ck && k.g.stride == 1 && src_bytes < 0x40000000LL && out_bytes < 0x40000000LL &&
-            tpi >= 2 && k.tiles_x >= 2 && tpi * tpi * B < 0x100000000LL &&        // magic-division ranges
-            tpi * B >= res_min_tiles) {
-            switch (ng) {
-                case 4: return launch_conv_res<T, BN, 4>(k, B, s);
-                case 2: return launch_conv_res<T, BN, 2>(k, B, s);
-                default: return launch_conv_res<T, BN, 1>(k, B, s);
+int launch_tile(const ConvK& k, const ConvPlan& p, hipStream_t s) {
+    if constexpr (BN >= 32) {
+        if (p.nth == 512) {
+            switch (p.ng) {
+                case 4: return launch_conv3x3<T, BN, 4, 1, false, 0, 512>(k, p, s);
+                case 2: return launch_conv3x3<T, BN, 2, 1, false, 0, 512>(k, p, s);
+                default: return launch_conv3x3<T, BN, 1, 1, false, 0, 512>(k, p, s);
             }
         }
     }
-    switch (ng) {
-        case 4:
-            // many-chunk layers at the lowest resolutions: two chunks in flight, because one MFMA phase (~0.5 us) is
-            // shorter than the global-load latency it is supposed to hide
-            if constexpr (BN == 32) {
-                // measured: pays only when the grid is about one workgroup per CU (it costs occupancy: ~190 VGPRs)
-                const int depth2_min = (int)TUNE(depth2_min_chunks);
-                const long lone_max = TUNE(lone_max_wgs);
-                const long wgs = (long)k.tiles_x * k.tiles_y * B * ((k.N + BN - 1) / BN);
-                if (wgs <= lone_max && (k.g.C[0] + k.g.C[1]) / (4 * TT<T>::G) >= depth2_min) {
-                    form_hit(FORM_CONV_RING);
-                    return launch_conv<T, BN, 4, 2>(k, B, s);     // (a three-chunk ring measured no better)
-                }
-            }
-            form_hit(FORM_CONV_TILE);
-            return launch_conv<T, BN, 4>(k, B, s);
-        case 2: form_hit(FORM_CONV_TILE); return launch_conv<T, BN, 2>(k, B, s);
-        default: form_hit(FORM_CONV_TILE); return launch_conv<T, BN, 1>(k, B, s);
-    }
-}
-
-inline void set_tile(ConvK& k, const Tile& t) {
-    const int pw = (t.tow - 1) * k.g.stride + 3;
-    // patches beyond 3 x 256 granules are staged partly by the linear tail loop: no row padding there
-    const bool tail = (long)((t.toh - 1) * k.g.stride + 3) * pw * 4 > 3 * NT;
-    apply_tile(k, t, pw, tail ? pw : std::max(t.pwp, pw));
-}
-
-template <typename T, int BN>
-int launch_conv_wide(const ConvK& k, int B, int ng, hipStream_t s) {
-    form_hit(FORM_CONV_WIDE);
-    switch (ng) {
-        case 4: return launch_conv_tail<T, BN, 4, 1, false, 0, 512>(k, B, s);
-        case 2: return launch_conv_tail<T, BN, 2, 1, false, 0, 512>(k, B, s);
-        default: return launch_conv_tail<T, BN, 1, 1, false, 0, 512>(k, B, s);
-    }
-}
-
-// `even`: tile extents must be even (2x2 sum-pool epilogue)
-template <typename T>
-int launch_conv_t(ConvK k, int B, bool even, hipStream_t s) {
-    constexpr int G = TT<T>::G;
-    int ng = 4;
-    for (int i = 0; i < 2; ++i)
-        if (k.g.C[i] > 0) while (ng > 1 && (k.g.C[i] % (ng * G)) != 0) ng >>= 1;
-    for (int i = 0; i < 2; ++i)
-        COLVO_CHECK_ARG(k.g.C[i] % (ng * G) == 0, "conv: channel count %d is not a multiple of %d", k.g.C[i], G);
-    // Wide form (512 threads, 256 pixels x BN channels): multi-chunk stride-1 layers whose 256-pixel grid still covers the
-    // chip.  Per MFMA it stages 100 (BN 64) / 136 (BN 32) bytes instead of 208, and the CUs' bytes in flight are what bounds
-    // these layers.
-    {
-        // off by default: at B = 16 the 256-pixel grids are 1-1.25 workgroups per CU and measured 10-20 % slower (up3 18.9 ->
-        // 21.7 us; gpurun_out/r2_bench_conv_w*.log); the form pays once the grid covers the chip several times (configs[2])
-        const int wide_on = (int)TUNE(wide);                 // tuning knob
-        const long wide_min_wgs = TUNE(wide_min_wgs);   // tuning knob
-        const int wide_min_chunks = (int)TUNE(wide_min_chunks);
-        const int nch = (k.g.C[0] + k.g.C[1]) / (ng * G);
-        if (wide_on && k.nsplit == 0 && k.g.stride == 1 && k.N >= 32 && nch >= wide_min_chunks) {
-            const Tile tw = pick_tile(k.Ho, k.Wo, 1, even, 256);
-            const long patch = (long)(tw.toh + 2) * (tw.tow + 2) * ng;
-            const int bn = k.N >= 64 ? 64 : 32;
-            const long wgs = (long)((k.Ho + tw.toh - 1) / tw.toh) * ((k.Wo + tw.tow - 1) / tw.tow) * B * ((k.N + bn - 1) / bn);
-            if (patch <= 3 * 512 && tw.toh * tw.tow > 128 && wgs >= wide_min_wgs) {
-                set_tile(k, tw);
-                if (bn == 64) form_hit(FORM_CONV_BN64);
-                return bn == 64 ? launch_conv_wide<T, 64>(k, B, ng, s) : launch_conv_wide<T, 32>(k, B, ng, s);
-            }
+    if constexpr (BN == 32) {
+        if (p.depth == 2) {
+            if (p.tail) return launch_conv3x3<T, 32, 4, 2, true>(k, p, s);
+            if (p.nch == 8) return launch_conv3x3<T, 32, 4, 2, false, 8>(k, p, s);
+            if (p.nch == 16) return launch_conv3x3<T, 32, 4, 2, false, 16>(k, p, s);
+            return launch_conv3x3<T, 32, 4, 2, false>(k, p, s);
         }
     }
-    set_tile(k, pick_tile(k.Ho, k.Wo, k.g.stride, even, 128, true));
-    if (k.g.stride == 2) {
-        const int r = try_launch_conv_res_s2<T>(k, B, ng, s);
-        if (r >= 0) return r;
+    switch (p.ng) {
+        case 4: return p.tail ? launch_conv3x3<T, BN, 4, 1, true>(k, p, s) : launch_conv3x3<T, BN, 4, 1, false>(k, p, s);
+        case 2: return p.tail ? launch_conv3x3<T, BN, 2, 1, true>(k, p, s) : launch_conv3x3<T, BN, 2, 1, false>(k, p, s);
+        default: return p.tail ? launch_conv3x3<T, BN, 1, 1, true>(k, p, s) : launch_conv3x3<T, BN, 1, 1, false>(k, p, s);
     }
-    // Output-channel tile: 64 wide by default; when that grid would leave CUs idle (deep, low-resolution layers at small
-    // batch) use 32 -- twice the workgroups, each staging half the weight slab per chunk (the chunk is LDS-bound).
-    const long tiles = (long)k.tiles_x * k.tiles_y * B;
-    const long bn64_min_wgs = TUNE(bn64_min_wgs);   // tuning knob
-    const long bn32_min_wgs = TUNE(bn32_min_wgs);      // tuning knob (16-wide tiles: measured ~neutral)
-    // (two-output form: a channel tile must not straddle the two sources -- nsplit is a multiple of 32)
-    if (k.nsplit == 0 && k.N >= 64 && tiles * ((k.N + 63) / 64) >= bn64_min_wgs) {
-        form_hit(FORM_CONV_BN64);
-        return launch_conv_ng<T, 64>(k, B, ng, s);
-    }
-    if (k.N >= 32 && tiles * ((k.N + 31) / 32) >= bn32_min_wgs) return launch_conv_ng<T, 32>(k, B, ng, s);
-    return launch_conv_ng<T, 16>(k, B, ng, s);
 }
 
-// quad-tile stride-1 kernel (k_conv_q): returns -1 when the layer does not qualify (the caller then takes the one-tile path)
+template <typename T, int BN, bool S2>
+int launch_res(const ConvK& k, const ConvPlan& p, hipStream_t s) {
+    if (p.ng == 4) return run_plan<k_conv3x3_res<T, BN, 4, S2>>(k, p, s, "k_conv3x3_res", p.ntiles, p.m_tpi, p.m_tx);
+    if constexpr (!S2) {            // (stride 2 takes two- and four-granule chunks only)
+        if (p.ng == 1) return run_plan<k_conv3x3_res<T, BN, 1, S2>>(k, p, s, "k_conv3x3_res", p.ntiles, p.m_tpi, p.m_tx);
+    }
+    return run_plan<k_conv3x3_res<T, BN, 2, S2>>(k, p, s, "k_conv3x3_res", p.ntiles, p.m_tpi, p.m_tx);
+}
+
+template <typename T, int BN>
+int launch_up2(const ConvK& k, const ConvPlan& p, hipStream_t s) {
+    if (p.nch == 8) return run_plan<k_conv_up2<T, BN, 2, 8>>(k, p, s, "k_conv_up2");
+    if (p.nch == 16) return run_plan<k_conv_up2<T, BN, 2, 16>>(k, p, s, "k_conv_up2");
+    return run_plan<k_conv_up2<T, BN, 1, 0>>(k, p, s, "k_conv_up2");
+}
+
+template <typename T, int BN>
+int launch_dgrad_s2(const ConvK& k, const ConvPlan& p, hipStream_t s) {
+    if (p.nch == 8) return run_plan<k_dgrad_s2<T, BN, 2, 8>>(k, p, s, "k_dgrad_s2");
+    if (p.nch == 16) return run_plan<k_dgrad_s2<T, BN, 2, 16>>(k, p, s, "k_dgrad_s2");
+    return run_plan<k_dgrad_s2<T, BN, 1, 0>>(k, p, s, "k_dgrad_s2");
+}
+
+template <typename T, int BN>
+int launch_dgrad_up2(const ConvK& k, const ConvPlan& p, hipStream_t s) {
+    if (p.ng == 2) return run_plan<k_dgrad_up2<T, BN, 1, 0, 2>>(k, p, s, "k_dgrad_up2");
+    if (p.nch == 8) return run_plan<k_dgrad_up2<T, BN, 2, 8>>(k, p, s, "k_dgrad_up2");
+    if (p.nch == 16) return run_plan<k_dgrad_up2<T, BN, 2, 16>>(k, p, s, "k_dgrad_up2");
+    return run_plan<k_dgrad_up2<T, BN, 1, 0>>(k, p, s, "k_dgrad_up2");
+}
+
+// The launch of a plan: its kernel instantiation for element type T
 template <typename T>
-int try_launch_conv_q(const ConvK& k0, int B, hipStream_t s) {
-    constexpr int G = TT<T>::G, ES = TT<T>::ES, CK = 4 * G;
-    const int q_on = (int)TUNE(conv_quad);
-    // Measured (bf16; us, one-tile -> quad).  16 frames of 256x320: slower everywhere (enc2b 14.8 -> 23.5, iconv3 19.0 -> 34.2,
-    // iconv2 22.0 -> 24.2, enc5b 17.1 -> 42.1).  64 frames of 512x640: the 2-4-chunk layers at 1/2-1/4 resolution win (enc2b 199 ->
-    // 153, iconv3 265 -> 217, iconv2 370 -> 275), the 8-16-chunk layers lose to the one-tile kernel's two-chunk ring (enc4b 122 ->
-    // 164, iconv5 215 -> 297).  Hence: at least 2048 quad-tile workgroups and at most 4 chunks.
-    const long min_wgs = TUNE(quad_min_wgs);          // (the tests lower / raise these two through colvo_tune_set)
-    const int max_chunks = (int)TUNE(quad_max_chunks);
-    const Gather& g = k0.g;
-    if (!q_on || g.stride != 1 || k0.pool2 || g.mode[0] != MODE_DIRECT || (g.C[1] > 0 && g.mode[1] != MODE_DIRECT)) return -1;
-    if (g.C[0] % CK || g.C[1] % CK || (g.C[0] + g.C[1]) / CK < 2 || (g.C[0] + g.C[1]) / CK > max_chunks) return -1;
-    if ((long long)g.Hi * g.Wi * std::max(g.C[0], g.C[1]) * ES >= 0x40000000LL || (long long)k0.Ho * k0.Wo * k0.N * ES >= 0x40000000LL)
-        return -1;
-    ConvK k = k0;
-    const Tile t = pick_tile((k.Ho + 1) / 2, (k.Wo + 1) / 2, 1, false, 128, true, 3);   // the sub-tile: at most half the image each way
-    const int PH = 2 * t.toh + 2, PW = 2 * t.tow + 2;
-    if (PH * PW * 4 > 10 * NT) return -1;
-    // sub-tile reads are conflict-free when the sub-tile's own rows are (pick_tile) AND the patch pitch keeps the row phase:
-    // keep the padding pick_tile chose relative to ITS patch width (tow + 2)
-    apply_tile(k, t, PW, PW + std::max(0, t.pwp - (t.tow + 2)), 2);
-    const long tiles = (long)k.tiles_x * k.tiles_y * B;
-    const int bn = (k.N > 16 && tiles * ((k.N + 31) / 32) >= min_wgs) ? 32 : 16;
-    k.ntn = (k.N + bn - 1) / bn;
-    if (tiles * k.ntn < min_wgs) return -1;
-    const int xcd_on = (int)TUNE(xcd_remap);
-    k.xcd = xcd_on;
-    constexpr int WROW = wrow_bytes(36), PIXP = pitch_bytes(64);
-    const size_t lds = (size_t)bn * WROW + (size_t)PH * k.pwp * PIXP;
-    if (lds > 160 * 1024) return -1;
-    if (int e = bn == 32 ? allow_dynamic_lds<k_conv_q<T, 32>>(lds, 160 * 1024, "conv") : allow_dynamic_lds<k_conv_q<T, 16>>(lds, 160 * 1024, "conv"))
-        return e;
-    const dim3 grid((unsigned)(tiles * k.ntn));
-    form_hit(FORM_CONV_Q);
-    if (bn == 32) colvo::launch((k_conv_q<T, 32>), grid, dim3(NT), lds, s, k);
-    else colvo::launch((k_conv_q<T, 16>), grid, dim3(NT), lds, s, k);
-    COLVO_CHECK_LAUNCH("k_conv_q");
-    return 0;
-}
-
-// forward over an up-sampled source (k_conv_up2): tiles over the stored half-size source
-template <typename T, int BN, int DEPTH, int NCH>
-int launch_conv_up2_inst(const ConvK& k, int B, hipStream_t s) {
-    constexpr int WROW = wrow_bytes(36), PIXP = pitch_bytes(64);
-    const size_t lds = (size_t)BN * WROW + (size_t)(k.toh + 2) * k.pwp * PIXP;
-    COLVO_CHECK_ARG(lds <= 48 * 1024, "conv (up-sampled source): tile needs %zu bytes of LDS", lds);
-    return launch_tiles<k_conv_up2<T, BN, DEPTH, NCH>>(k, BN, B, NT, lds, s, "k_conv_up2");
-}
-
-template <typename T, int BN>
-int launch_conv_up2_bn(const ConvK& k, int B, hipStream_t s) {
-    form_hit(BN == 32 ? FORM_CONV_UP2_BN32 : FORM_CONV_UP2_BN16);
-    const int nch = k.g.C[0] / (4 * TT<T>::G);
-    if (nch == 8) return launch_conv_up2_inst<T, BN, 2, 8>(k, B, s);
-    if (nch == 16) return launch_conv_up2_inst<T, BN, 2, 16>(k, B, s);
-    return launch_conv_up2_inst<T, BN, 1, 0>(k, B, s);
-}
-
-// input gradient w.r.t. an up-sampled source (k_dgrad_up2): tiles over the half-size source
-template <typename T, int BN, int DEPTH, int NCH, int NG = 4>
-int launch_dgrad_up2_inst(const ConvK& k, int B, hipStream_t s) {
-    constexpr int WROW = wrow_bytes((9 * NG + 3) / 4 * 4), PIXP = pitch_bytes(NG * 16);
-    const size_t lds = (size_t)BN * WROW + (size_t)(2 * k.toh + 2) * k.pwp * PIXP;
-    COLVO_CHECK_ARG(lds <= 160 * 1024, "dgrad (up-sampled source): tile needs %zu bytes of LDS", lds);
-    if (int e = allow_dynamic_lds<k_dgrad_up2<T, BN, DEPTH, NCH, NG>>(lds, 160 * 1024, "dgrad")) return e;
-    return launch_tiles<k_dgrad_up2<T, BN, DEPTH, NCH, NG>>(k, BN, B, NT, lds, s, "k_dgrad_up2");
-}
-
-template <typename T, int BN>
-int launch_dgrad_up2_bn(const ConvK& k, int B, hipStream_t s) {
-    form_hit(FORM_DGRAD_UP2);
-    if (k.g.C[0] % (4 * TT<T>::G)) return launch_dgrad_up2_inst<T, BN, 1, 0, 2>(k, B, s);       // 2-granule chunks
-    const int nch = k.g.C[0] / (4 * TT<T>::G);
-    if (nch == 8) return launch_dgrad_up2_inst<T, BN, 2, 8>(k, B, s);
-    if (nch == 16) return launch_dgrad_up2_inst<T, BN, 2, 16>(k, B, s);
-    return launch_dgrad_up2_inst<T, BN, 1, 0>(k, B, s);
-}
-
-// parity-decomposed stride-2 input gradient (k_dgrad_s2): tiles over dy, four output pixels per tile position
-template <typename T, int BN, int DEPTH, int NCH>
-int launch_dgrad_s2_inst(const ConvK& k, int B, hipStream_t s) {
-    constexpr int WROW = wrow_bytes(36), PIXP = pitch_bytes(64);
-    const size_t lds = (size_t)BN * WROW + (size_t)(k.toh + 1) * k.pwp * PIXP;
-    COLVO_CHECK_ARG(lds <= 48 * 1024, "dgrad (stride 2): tile needs %zu bytes of LDS", lds);
-    return launch_tiles<k_dgrad_s2<T, BN, DEPTH, NCH>>(k, BN, B, NT, lds, s, "k_dgrad_s2");
-}
-
-template <typename T, int BN>
-int launch_dgrad_s2_bn(const ConvK& k, int B, hipStream_t s) {
-    const int nch = k.g.C[0] / (4 * TT<T>::G);
-    const long wgs = (long)k.tiles_x * k.tiles_y * B * ((k.N + BN - 1) / BN);
-    const long lone_max = TUNE(lone_max_wgs);
-    if (wgs <= lone_max && (nch == 8 || nch == 16)) {      // about one workgroup per CU: two chunks in flight, K loop unrolled (see launch_conv_ng)
-        form_hit(FORM_DGRAD_S2_RING);
-        return nch == 8 ? launch_dgrad_s2_inst<T, BN, 2, 8>(k, B, s) : launch_dgrad_s2_inst<T, BN, 2, 16>(k, B, s);
+int launch_plan(const ConvK& k, const ConvPlan& p, hipStream_t s) {
+    switch (p.form) {
+        case CONV_UP2: return p.bn == 32 ? launch_up2<T, 32>(k, p, s) : launch_up2<T, 16>(k, p, s);
+        case CONV_RT: return conv_rt_launch(k, p, TT<T>::ES == 4 ? COLVO_F32 : COLVO_BF16, s);
+        case CONV_Q: return p.bn == 32 ? run_plan<k_conv_q<T, 32>>(k, p, s, "k_conv_q") : run_plan<k_conv_q<T, 16>>(k, p, s, "k_conv_q");
+        case CONV_RES: return p.bn == 32 ? launch_res<T, 32, false>(k, p, s) : launch_res<T, 16, false>(k, p, s);
+        case CONV_RES_S2: return p.bn == 64 ? launch_res<T, 64, true>(k, p, s) : launch_res<T, 32, true>(k, p, s);
+        case CONV_TILE:
+            return p.bn == 64 ? launch_tile<T, 64>(k, p, s) : p.bn == 32 ? launch_tile<T, 32>(k, p, s) : launch_tile<T, 16>(k, p, s);
+        case DGRAD_S2: return p.bn == 32 ? launch_dgrad_s2<T, 32>(k, p, s) : launch_dgrad_s2<T, 16>(k, p, s);
+        default: return p.bn == 32 ? launch_dgrad_up2<T, 32>(k, p, s) : launch_dgrad_up2<T, 16>(k, p, s);   // DGRAD_UP2
     }
-    form_hit(FORM_DGRAD_S2);
-    return launch_dgrad_s2_inst<T, BN, 1, 0>(k, B, s);
-}
-
-template <typename T>
-int launch_dgrad_s2(ConvK k, int B, hipStream_t s) {
-    const Tile t = pick_tile(k.Ho, k.Wo, 1, false, 128, true, 2);
-    apply_tile(k, t, t.tow + 1, std::max(t.pwp, t.tow + 1));
-    return k.N > 16 ? launch_dgrad_s2_bn<T, 32>(k, B, s) : launch_dgrad_s2_bn<T, 16>(k, B, s);
 }
 
 // Input gradient as a conv: dy (Cout channels) is the single direct source, the weights are the rows of w_bwd from input channel
@@ -1763,43 +1824,9 @@ extern "C" int colvo_conv_fwd(const ColvoConvDesc* d, const void* x0, const void
     k.Ho = d->Ho; k.Wo = d->Wo;
     k.w = (const char*)w_fwd; k.Ctot = d->C0 + d->C1; k.N = d->Cout;
     k.bias = bias; k.relu = d->relu; k.out = (char*)y; k.mask = nullptr; k.accumulate = 0; k.pool2 = 0;
-    {
-        // single up-sampled source in whole 32-channel chunks: four output pixels per source position (k_conv_up2; the one-chunk
-        // full-resolution layer up1 too: 23.2 -> 18.4 us against the weights-resident one-tile kernel)
-        const int up2_on = (int)TUNE(conv_up2);
-        const int es = d->dtype == COLVO_F32 ? 4 : 2, ck = d->dtype == COLVO_F32 ? 16 : 32;
-        const long long in_bytes = (long long)(d->Hi / 2) * (d->Wi / 2) * d->C0 * es, out_bytes = (long long)d->Ho * d->Wo * d->Cout * es;
-        const int up2_min_chunks = (int)TUNE(up2_min_chunks);   // tuning knob
-        if (up2_on && d->up0 && d->C1 == 0 && d->stride == 1 && d->C0 % ck == 0 && d->C0 / ck >= up2_min_chunks &&
-            in_bytes < 0x40000000LL && out_bytes < 0x40000000LL) {
-            ConvK u = k;
-            u.g.mode[0] = MODE_DIRECT;                    // read the stored half-size source as it is
-            u.g.Hi = d->Hi / 2; u.g.Wi = d->Wi / 2;
-            u.Ho = d->Hi / 2; u.Wo = d->Wi / 2;           // tiles run over source positions; the kernel writes (2 Ho) x (2 Wo)
-            const Tile t = pick_tile(u.Ho, u.Wo, 1, false, 128, true, 3);
-            if ((t.toh + 2) * (t.tow + 2) * 4 <= 3 * NT) {
-                apply_tile(u, t, t.tow + 2, std::max(t.pwp, t.tow + 2));
-                hipStream_t s = (hipStream_t)stream;
-                // 16-wide channel tiles while 32-wide ones would leave CUs without a workgroup
-                const long bn16_max = TUNE(up2_bn16_max_wgs);   // tuning knob
-                const long wgs32 = (long)u.tiles_x * u.tiles_y * d->B * ((u.N + 31) / 32);
-                const bool wide = u.N > 16 && wgs32 > bn16_max;
-                if (d->dtype == COLVO_F32)
-                    return wide ? launch_conv_up2_bn<float, 32>(u, d->B, s) : launch_conv_up2_bn<float, 16>(u, d->B, s);
-                return wide ? launch_conv_up2_bn<bf16_t, 32>(u, d->B, s) : launch_conv_up2_bn<bf16_t, 16>(u, d->B, s);
-            }
-        }
-    }
-    {
-        // large grids of ordinary stride-1 layers: the register-tiled kernel (conv_rt.hip), then the quad-tile kernel
-        int r = try_launch_conv_rt(k, d->B, d->dtype, (hipStream_t)stream);
-        if (r >= 0) return r;
-        r = d->dtype == COLVO_F32 ? try_launch_conv_q<float>(k, d->B, (hipStream_t)stream)
-                                  : try_launch_conv_q<bf16_t>(k, d->B, (hipStream_t)stream);
-        if (r >= 0) return r;
-    }
-    return d->dtype == COLVO_F32 ? launch_conv_t<float>(k, d->B, false, (hipStream_t)stream)
-                                 : launch_conv_t<bf16_t>(k, d->B, false, (hipStream_t)stream);
+    ConvPlan p{};
+    if (int e = conv_plan(d, PASS_FWD, 0, k, p)) return e;
+    return d->dtype == COLVO_F32 ? launch_plan<float>(k, p, (hipStream_t)stream) : launch_plan<bf16_t>(k, p, (hipStream_t)stream);
 }
 
 extern "C" int colvo_conv_dgrad(const ColvoConvDesc* d, int src, const void* dy, const void* w_bwd,
@@ -1807,62 +1834,10 @@ extern "C" int colvo_conv_dgrad(const ColvoConvDesc* d, int src, const void* dy,
     if (int e = check_desc(d, "colvo_conv_dgrad")) return e;
     COLVO_CHECK_ARG(dy && w_bwd && dx, "colvo_conv_dgrad: null pointer argument");
     COLVO_CHECK_ARG(src == 0 || (src == 1 && d->C1 > 0), "colvo_conv_dgrad: bad source index %d", src);
-    const int es = d->dtype == COLVO_F32 ? 4 : 2;
-    const int Csrc = src == 0 ? d->C0 : d->C1;
-    const int coff = src == 0 ? 0 : d->C0;
-    const int up = src == 0 ? d->up0 : d->up1;
-    {
-        // stride 2, even input extent, 32-channel chunks of dy: the parity-decomposed kernel (a quarter of the MFMAs)
-        const int s2_on = (int)TUNE(dgrad_s2);
-        const int ck = d->dtype == COLVO_F32 ? 16 : 32;
-        const long long out_bytes = (long long)d->Hi * d->Wi * Csrc * es, in_bytes = (long long)d->Ho * d->Wo * d->Cout * es;
-        if (s2_on && d->stride == 2 && !up && d->Hi == 2 * d->Ho && d->Wi == 2 * d->Wo && d->Cout % ck == 0 &&
-            out_bytes < 0x40000000LL && in_bytes < 0x40000000LL) {
-            // tiles run over dy; the kernel writes a (2 Ho) x (2 Wo) image
-            const ConvK k = dgrad_conv(d, dy, w_bwd, coff, Csrc, dx, relu_mask, accumulate);
-            return d->dtype == COLVO_F32 ? launch_dgrad_s2<float>(k, d->B, (hipStream_t)stream)
-                                         : launch_dgrad_s2<bf16_t>(k, d->B, (hipStream_t)stream);
-        }
-    }
-    {
-        // up-sampled source, stride 1, 32-channel chunks of dy: the 2x2 sum-pool folded into the K loop (k_dgrad_up2)
-        const int up2_on = (int)TUNE(dgrad_up2);
-        const int ck = d->dtype == COLVO_F32 ? 16 : 32;
-        const long long out_bytes = (long long)(d->Hi / 2) * (d->Wi / 2) * Csrc * es, in_bytes = (long long)d->Ho * d->Wo * d->Cout * es;
-        if (up2_on && up && d->stride == 1 && d->Cout % (ck / 2) == 0 && out_bytes < 0x40000000LL && in_bytes < 0x40000000LL) {
-            ConvK u = dgrad_conv(d, dy, w_bwd, coff, Csrc, dx, relu_mask, accumulate);
-            u.Ho = d->Hi / 2; u.Wo = d->Wi / 2;          // tiles and output: the stored half-size source
-            const Tile t = pick_tile(u.Ho, u.Wo, 2, false, 128, true, 4);   // patch rows of 2 tow + 2 pixels, pixel stride 2
-            if ((2 * t.toh + 2) * (2 * t.tow + 2) * 4 <= 10 * NT) {                 // (x NG / 4 granules <= PPF x 256 for either NG)
-                apply_tile(u, t, 2 * t.tow + 2, std::max(t.pwp, 2 * t.tow + 2));
-                hipStream_t s = (hipStream_t)stream;
-                // only where the grid still covers the chip: at batch 16 the 1/8- and 1/16-resolution layers measured 1-2 us
-                // SLOWER in this form (up5 19.4 -> 21.0, up4 18.2 -> 19.4; up3 20.7 -> 19.4, up2 26.8 -> 19.1)
-                // (read at every call, not once: the tests switch it to reach this kernel with small shapes)
-                const long min_wgs = TUNE(dgrad_up2_min_wgs);
-                const long wgs32 = (long)u.tiles_x * u.tiles_y * d->B * ((u.N + 31) / 32);
-                if (wgs32 >= min_wgs) {
-                    if (d->dtype == COLVO_F32)
-                        return u.N > 16 ? launch_dgrad_up2_bn<float, 32>(u, d->B, s) : launch_dgrad_up2_bn<float, 16>(u, d->B, s);
-                    return u.N > 16 ? launch_dgrad_up2_bn<bf16_t, 32>(u, d->B, s) : launch_dgrad_up2_bn<bf16_t, 16>(u, d->B, s);
-                }
-            }
-        }
-    }
-    // the conv input is dy (Cout channels), dilated by zero insertion when the forward stride was 2
-    ConvK k = dgrad_conv(d, dy, w_bwd, coff, Csrc, dx, relu_mask, accumulate);
-    if (d->stride == 2) { k.g.mode[0] = MODE_DILATE; k.g.Hi = 2 * d->Ho; k.g.Wi = 2 * d->Wo; }
-    k.Ho = d->Hi; k.Wo = d->Wi;                    // gradient w.r.t. the (virtual) forward input
-    k.pool2 = up;
-    if (d->stride == 1 && !up) {
-        int r = try_launch_conv_rt(k, d->B, d->dtype, (hipStream_t)stream);
-        if (r >= 0) return r;
-        r = d->dtype == COLVO_F32 ? try_launch_conv_q<float>(k, d->B, (hipStream_t)stream)
-                                  : try_launch_conv_q<bf16_t>(k, d->B, (hipStream_t)stream);
-        if (r >= 0) return r;
-    }
-    return d->dtype == COLVO_F32 ? launch_conv_t<float>(k, d->B, up != 0, (hipStream_t)stream)
-                                 : launch_conv_t<bf16_t>(k, d->B, up != 0, (hipStream_t)stream);
+    ConvK k = dgrad_conv(d, dy, w_bwd, src == 0 ? 0 : d->C0, src == 0 ? d->C0 : d->C1, dx, relu_mask, accumulate);
+    ConvPlan p{};
+    if (int e = conv_plan(d, PASS_DGRAD, src == 0 ? d->up0 : d->up1, k, p)) return e;
+    return d->dtype == COLVO_F32 ? launch_plan<float>(k, p, (hipStream_t)stream) : launch_plan<bf16_t>(k, p, (hipStream_t)stream);
 }
 
 // Input gradient w.r.t. BOTH sources of a stride-1 concat layer in ONE launch: the two calls of colvo_conv_dgrad stage the
@@ -1885,12 +1860,8 @@ extern "C" int colvo_conv_dgrad_both(const ColvoConvDesc* d, const void* dy, con
     ConvK k = dgrad_conv(d, dy, w_bwd, 0, d->C0 + d->C1, dx0, relu_mask0, 0);
     k.Ho = d->Hi; k.Wo = d->Wi;
     k.out2 = (char*)dx1; k.mask2 = (const char*)relu_mask1; k.nsplit = d->C0;
-    form_hit(FORM_DGRAD_BOTH);
-    {
-        const int r = try_launch_conv_rt(k, d->B, d->dtype, (hipStream_t)stream);
-        if (r >= 0) return r;
-    }
-    return d->dtype == COLVO_F32 ? launch_conv_t<float>(k, d->B, false, (hipStream_t)stream)
-                                 : launch_conv_t<bf16_t>(k, d->B, false, (hipStream_t)stream);
+    ConvPlan p{};
+    p.forms = form_bit(FORM_DGRAD_BOTH);
+    if (int e = conv_plan(d, PASS_DGRAD_BOTH, 0, k, p)) return e;
+    return d->dtype == COLVO_F32 ? launch_plan<float>(k, p, (hipStream_t)stream) : launch_plan<bf16_t>(k, p, (hipStream_t)stream);
 }
-

@@ -52,8 +52,26 @@ struct ConvK {
 #endif
 };
 
-// conv_rt.hip: register-tiled stride-1 kernel for large grids (forward and input gradient); -1: the layer does not qualify
-int try_launch_conv_rt(const ConvK& k, int B, int dtype, hipStream_t s);
+// A forward / input-gradient launch, decided by conv_plan (conv.hip) before any HIP call: the form, its kernel instantiation, LDS,
+// grid, extra kernel arguments and the form counters the launch records.
+enum { CONV_UP2, CONV_RT, CONV_Q, CONV_RES, CONV_RES_S2, CONV_TILE, DGRAD_S2, DGRAD_UP2 };
+struct ConvPlan {
+    int form;
+    int bn, ng;               // output channels per workgroup, granules per channel chunk
+    int depth, nch;           // chunks in flight, chunk count the K loop is unrolled for (0: not unrolled)
+    bool tail;                // k_conv3x3: the patch is staged partly by the linear tail loop
+    int nth;                  // threads per workgroup
+    size_t lds;
+    dim3 grid;
+    int ntiles, per_wg;       // k_conv_rt: (pixel tile, channel tile) pairs, pairs per workgroup; k_conv3x3_res: pixel tiles
+    uint32_t m_tpi, m_tx;     // k_conv3x3_res: magic divisors of the tiles per image and per tile row
+    uint32_t forms;           // form_bit of every FORM_* the launch counts
+};
+
+// conv_rt.hip: register-tiled stride-1 kernel for large grids (forward and input gradient).  conv_rt_plan: false when the layer
+// does not qualify; otherwise sets k's tile and grid and fills p.  Calls no HIP.
+bool conv_rt_plan(ConvK& k, int B, int dtype, ConvPlan& p);
+int conv_rt_launch(const ConvK& k, const ConvPlan& p, int dtype, hipStream_t s);
 
 // wgrad_rt.hip: register-tiled weight gradient (bf16, stride 1).  wgrad.hip asks for a plan (false: the layer does not qualify), sets up
 // the way out that the plan's split count calls for (atomics / slabs / sole writer), launches, and runs its own second launch if any.
@@ -370,8 +388,9 @@ inline void apply_tile(ConvK& k, const Tile& t, int pw, int pwp, int cover = 1) 
     k.pwp = pwp;
 }
 
-// 1-D grid of a one-tile kernel: tiles_x x tiles_y x B pixel tiles, each with ceil(N / BN) output-channel tiles (n-tile fastest)
-inline long long tile_grid(ConvK& k, int BN, int B) {
+// 1-D grid of a one-tile kernel: tiles_x x tiles_y x B pixel tiles, each with ceil(N / BN) output-channel tiles (n-tile fastest).
+// Sets k's channel-tile count and XCD remap; returns the number of workgroups.
+inline long long set_tile_grid(ConvK& k, int BN, int B) {
     k.ntn = (k.N + BN - 1) / BN;
     k.xcd = (int)TUNE(xcd_remap);
     return (long long)k.tiles_x * k.tiles_y * k.ntn * B;

@@ -21,7 +21,7 @@
 //     ds_read_b128 groups (conv_common.h pitch_slots);
 //   * epilogue straight from the accumulators (operands swapped: a lane holds 4 consecutive channels of one pixel): bias, ReLU,
 //     producer's ReLU mask, accumulate, two-output form of colvo_conv_dgrad_both.
-// Selected by try_launch_conv_rt for direct (not up-sampled / dilated) sources in whole 32-channel chunks when the 16 x 16 tiling
+// Selected by conv_rt_plan for direct (not up-sampled / dilated) sources in whole 32-channel chunks when the 16 x 16 tiling
 // wastes little of the image and the grid has at least rt_min_wgs workgroups (tuning.h).
 #define COLVO_ACC_CONSTRAINT "+v"     // built with -mllvm -amdgpu-mfma-vgpr-form (coivo_amd/build.py)
 #include "conv_common.h"
@@ -319,53 +319,64 @@ __global__ __launch_bounds__(NT, (NF == 2 && TT<T>::ES == 2) ? 3 : 2) void k_con
     }
 }
 
+// LDS of k_conv_rt with BN output channels per workgroup: the weight slab and the 18 x 18 patch
+constexpr size_t rt_lds(int BN) { return (size_t)BN * wrow_bytes(36) + (size_t)RT_PH * RT_PW * pitch_bytes(64); }
+static_assert(rt_lds(64) <= 80 * 1024, "k_conv_rt: two workgroups per CU need <= 80 KB of LDS each");
+
 template <typename T, int NF>
-int launch_conv_rt(ConvK k, long long ntiles, hipStream_t s) {
-    constexpr int BN = 16 * NF;
-    constexpr size_t lds = (size_t)BN * wrow_bytes(36) + (size_t)RT_PH * RT_PW * pitch_bytes(64);
-    static_assert(lds <= 80 * 1024, "k_conv_rt: two workgroups per CU need <= 80 KB of LDS each");
-    if (int e = allow_dynamic_lds<k_conv_rt<T, NF>>(lds, (int)lds, "conv (register-tiled)")) return e;
-    // one tile per workgroup by default; rt_wgs_per_cu > 0: a persistent grid (256 CUs x n, + 1 for the 32-channel form), every
-    // workgroup walking the same number of consecutive tiles (tuning.h has the measurement that keeps it off)
-    const long per_cu = TUNE(rt_wgs_per_cu) > 0 ? TUNE(rt_wgs_per_cu) + (NF == 2 ? 1 : 0) : 0;
-    long long slots = per_cu > 0 ? 256 * per_cu : ntiles;
-    if (slots > ntiles) slots = ntiles;
-    long long per_wg = (ntiles + slots - 1) / slots;
-    if (TUNE(rt_tiles_per_wg) > 0) per_wg = std::min<long long>(TUNE(rt_tiles_per_wg), ntiles);
-    const long long nwg = (ntiles + per_wg - 1) / per_wg;
-    colvo::launch((k_conv_rt<T, NF>), dim3((unsigned)nwg), dim3(NT), (unsigned)lds, s, k, (int)ntiles, (int)per_wg);
+int launch_conv_rt(const ConvK& k, const ConvPlan& p, hipStream_t s) {
+    if (int e = allow_dynamic_lds<k_conv_rt<T, NF>>(p.lds, (int)rt_lds(16 * NF), "conv (register-tiled)")) return e;
+    form_hits(p.forms);
+    colvo::launch((k_conv_rt<T, NF>), p.grid, dim3(NT), (unsigned)p.lds, s, k, p.ntiles, p.per_wg);
     COLVO_CHECK_LAUNCH("k_conv_rt");
     return 0;
 }
 
 }  // namespace
 
-int try_launch_conv_rt(const ConvK& k0, int B, int dtype, hipStream_t s) {
-    if (!TUNE(conv_rt)) return -1;
-    const Gather& g = k0.g;
+bool conv_rt_plan(ConvK& k, int B, int dtype, ConvPlan& p) {
+    if (!TUNE(conv_rt)) return false;
+    const Gather& g = k.g;
     const int es = dtype == COLVO_F32 ? 4 : 2, ck = dtype == COLVO_F32 ? 16 : 32;
-    if (g.stride != 1 || k0.pool2 || g.mode[0] != MODE_DIRECT || (g.C[1] > 0 && g.mode[1] != MODE_DIRECT)) return -1;
-    if (g.C[0] % ck || g.C[1] % ck || k0.N <= 16) return -1;
+    if (g.stride != 1 || k.pool2 || g.mode[0] != MODE_DIRECT || (g.C[1] > 0 && g.mode[1] != MODE_DIRECT)) return false;
+    if (g.C[0] % ck || g.C[1] % ck || k.N <= 16) return false;
     // single-chunk layers (enc1b, the input gradients of iconv2) stay with the weights-resident persistent kernel: they are bound
     // by their HBM traffic and it prefetches across tiles (64 frames: enc1b 35.4 -> 41.6 us here, iconv2 dgrad 47.6 -> 59.2)
-    if ((g.C[0] + g.C[1]) / ck < TUNE(rt_min_chunks)) return -1;
+    if ((g.C[0] + g.C[1]) / ck < TUNE(rt_min_chunks)) return false;
     // (the kernel addresses whole tensors -- all images -- with 32-bit offsets and uses 1 GiB as its out-of-range mark)
-    if ((long long)B * g.Hi * g.Wi * std::max(g.C[0], g.C[1]) * es >= 0x40000000LL || (long long)B * k0.Ho * k0.Wo * k0.N * es >= 0x40000000LL)
-        return -1;
-    ConvK k = k0;
-    apply_tile(k, Tile{RT_TH, RT_TW, RT_PW}, RT_PW, RT_PW);
+    if ((long long)B * g.Hi * g.Wi * std::max(g.C[0], g.C[1]) * es >= 0x40000000LL || (long long)B * k.Ho * k.Wo * k.N * es >= 0x40000000LL)
+        return false;
+    ConvK r = k;
+    apply_tile(r, Tile{RT_TH, RT_TW, RT_PW}, RT_PW, RT_PW);
     // the 16 x 16 tiling must not waste much of the image (a 32 x 40 map computes 1.2 x its pixels, a 16 x 20 map 1.6 x)
-    const long long covered = (long long)k.tiles_x * k.tiles_y * RT_TH * RT_TW;
-    if ((long long)k.Ho * k.Wo * 100 < covered * TUNE(rt_min_fill_pct)) return -1;
+    const long long covered = (long long)r.tiles_x * r.tiles_y * RT_TH * RT_TW;
+    if ((long long)r.Ho * r.Wo * 100 < covered * TUNE(rt_min_fill_pct)) return false;
     // 64-wide channel tiles where the layer has them (two-output form: a tile must not straddle the two sources)
-    const bool bn64 = k.N >= 64 && (k.nsplit == 0 || k.nsplit % 64 == 0);
-    if (k.nsplit % 32 != 0) return -1;
-    const long long nwg = tile_grid(k, bn64 ? 64 : 32, B);
-    if (nwg < (bn64 ? TUNE(rt_min_wgs) : TUNE(rt_bn32_min_wgs)) || nwg >= (1ll << 30)) return -1;
-    form_hit(FORM_CONV_RT);
-    if (!bn64) form_hit(FORM_CONV_RT_BN32);
-    if (dtype == COLVO_F32) return bn64 ? launch_conv_rt<float, 4>(k, nwg, s) : launch_conv_rt<float, 2>(k, nwg, s);
-    return bn64 ? launch_conv_rt<bf16_t, 4>(k, nwg, s) : launch_conv_rt<bf16_t, 2>(k, nwg, s);
+    const bool bn64 = r.N >= 64 && (r.nsplit == 0 || r.nsplit % 64 == 0);
+    if (r.nsplit % 32 != 0) return false;
+    const long long ntiles = set_tile_grid(r, bn64 ? 64 : 32, B);
+    if (ntiles < (bn64 ? TUNE(rt_min_wgs) : TUNE(rt_bn32_min_wgs)) || ntiles >= (1ll << 30)) return false;
+    // one tile per workgroup by default; rt_wgs_per_cu > 0: a persistent grid (256 CUs x n, + 1 for the 32-channel form), every
+    // workgroup walking the same number of consecutive tiles (tuning.h has the measurement that keeps it off)
+    const long per_cu = TUNE(rt_wgs_per_cu) > 0 ? TUNE(rt_wgs_per_cu) + (bn64 ? 0 : 1) : 0;
+    long long slots = per_cu > 0 ? 256 * per_cu : ntiles;
+    if (slots > ntiles) slots = ntiles;
+    long long per_wg = (ntiles + slots - 1) / slots;
+    if (TUNE(rt_tiles_per_wg) > 0) per_wg = std::min<long long>(TUNE(rt_tiles_per_wg), ntiles);
+    k = r;
+    p.form = CONV_RT;
+    p.bn = bn64 ? 64 : 32;
+    p.lds = rt_lds(p.bn);
+    p.ntiles = (int)ntiles;
+    p.per_wg = (int)per_wg;
+    p.grid = dim3((unsigned)((ntiles + per_wg - 1) / per_wg));
+    p.forms |= form_bit(FORM_CONV_RT) | (bn64 ? 0 : form_bit(FORM_CONV_RT_BN32));
+    return true;
+}
+
+int conv_rt_launch(const ConvK& k, const ConvPlan& p, int dtype, hipStream_t s) {
+    if (dtype == COLVO_F32) return p.bn == 64 ? launch_conv_rt<float, 4>(k, p, s) : launch_conv_rt<float, 2>(k, p, s);
+    return p.bn == 64 ? launch_conv_rt<bf16_t, 4>(k, p, s) : launch_conv_rt<bf16_t, 2>(k, p, s);
 }
 
 }  // namespace colvo
