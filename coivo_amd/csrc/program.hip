@@ -156,6 +156,16 @@ static int run_one(const ColvoCmd& c, int k, colvo_stream_t s) {
     }
 }
 
+// one command issued eagerly (coivo_amd/ops.py outside a recording): exactly the entry point call run_one makes -- no capture
+// handling, no events, no launch tap -- so under stream capture its launches stay plain nodes on the capturing stream
+extern "C" int colvo_run_command(const ColvoCmd* cmd, colvo_stream_t stream) {
+    COLVO_CHECK_ARG(cmd, "colvo_run_command: null command");
+    COLVO_CHECK_ARG(cmd->stream == 0, "colvo_run_command: stream selector %d (a single command runs on `stream`)", cmd->stream);
+    COLVO_CHECK_ARG(cmd->op != COLVO_CMD_FORK && cmd->op != COLVO_CMD_JOIN && cmd->op != COLVO_CMD_SIDE_SYNC,
+                    "colvo_run_command: op %d orders streams and needs colvo_run_commands", cmd->op);
+    return run_one(*cmd, 0, stream);
+}
+
 // ---- hipGraph form ------------------------------------------------------------------------------------------------------------ //
 // While `main_stream` is being captured (hipStreamBeginCapture -- torch.cuda.graph) the command list is turned into graph nodes with
 // EXPLICIT dependencies on that ONE capturing stream: no side stream, no events.  hipStreamGetCaptureInfo_v2 reads the dependency

@@ -16,7 +16,7 @@ MI355X-first host design
   * Each pass (forward / backward of a network at one shape) is RECORDED once as a command list with persistent
     activation buffers and replayed by one native call (program.py, colvo_run_commands): driven layer by layer from
     Python the batch-8 step was bound by the host's ~18 us per launch, not by the GPU.  COLVO_NO_PROGRAM=1 keeps the
-    layer-by-layer path (same code, not recorded).
+    layer-by-layer path: the same commands, each issued on its own as it is made (colvo_run_command), not recorded.
 """
 from __future__ import annotations
 

@@ -1,7 +1,8 @@
 """Op-level host wrappers over the C-ABI (include/colvo.h): tensors in, raw pointers + stream out.
 
 Feature maps are NHWC torch tensors (float32 or bfloat16); everything is enqueued on PyTorch's current
-stream.  No op here has a CPU or PyTorch fallback.
+stream.  No op here has a CPU or PyTorch fallback.  The conv, packing and head ops are commands (_issue): one argument
+encoding, whether they are recorded into a Program or run at once.
 """
 from __future__ import annotations
 
@@ -31,6 +32,16 @@ def _need_cuda(*ts):
             raise RuntimeError("coivo_amd ops run on the GPU only; there is no CPU fallback")
 
 
+def _issue(op: int, desc=None, p=(), i=(), f=(), raw=(), flag_slot: Optional[int] = None) -> None:
+    """One command (include/colvo.h COLVO_CMD_*, program.encode): appended to the Program being recorded, otherwise run now on the
+    current stream by colvo_run_command.  Either way the library's one decoder picks the entry point and its form."""
+    rec = program.recording()
+    if rec is not None:
+        return rec.add(op, desc, p, i, f, raw, flag_slot)
+    c, _ = program.encode(op, desc, p, i, f, raw)
+    _lib.check(_lib.load().colvo_run_command(C.byref(c), _lib.stream_ptr()), "colvo_run_command")
+
+
 def conv_desc(dtype: torch.dtype, B: int, Hi: int, Wi: int, C0: int, Cout: int, *, stride: int = 1, relu: bool = True,
               C1: int = 0, up0: bool = False, up1: bool = False) -> ConvDesc:
     d = ConvDesc()
@@ -44,45 +55,25 @@ def conv_desc(dtype: torch.dtype, B: int, Hi: int, Wi: int, C0: int, Cout: int, 
 
 def conv_fwd(d: ConvDesc, x0, x1, w_fwd, bias, y) -> None:
     _need_cuda(x0, x1, w_fwd, bias, y)
-    rec = program.recording()
-    if rec is not None:
-        return rec.add(_lib.CMD_CONV_FWD, d, (x0, x1, w_fwd, bias, y))
-    lib = _lib.load()
-    _lib.check(lib.colvo_conv_fwd(C.byref(d), _lib.ptr(x0), _lib.ptr(x1), _lib.ptr(w_fwd), _lib.ptr(bias),
-                                  _lib.ptr(y), _lib.stream_ptr()), "colvo_conv_fwd")
+    _issue(_lib.CMD_CONV_FWD, d, (x0, x1, w_fwd, bias, y))
 
 
 def conv_dgrad(d: ConvDesc, src: int, dy, w_bwd, relu_mask, dx, accumulate: bool) -> None:
     _need_cuda(dy, w_bwd, relu_mask, dx)
-    rec = program.recording()
-    if rec is not None:
-        return rec.add(_lib.CMD_CONV_DGRAD, d, (dy, w_bwd, relu_mask, dx), (src, int(accumulate)))
-    lib = _lib.load()
-    _lib.check(lib.colvo_conv_dgrad(C.byref(d), src, _lib.ptr(dy), _lib.ptr(w_bwd), _lib.ptr(relu_mask),
-                                    _lib.ptr(dx), int(accumulate), _lib.stream_ptr()), "colvo_conv_dgrad")
+    _issue(_lib.CMD_CONV_DGRAD, d, (dy, w_bwd, relu_mask, dx), (src, int(accumulate)))
 
 
 def conv_dgrad_both(d: ConvDesc, dy, w_bwd, relu_mask0, relu_mask1, dx0, dx1) -> None:
     """Input gradients w.r.t. both sources of a concat layer in one launch (colvo_conv_dgrad_both)."""
     _need_cuda(dy, w_bwd, relu_mask0, relu_mask1, dx0, dx1)
-    rec = program.recording()
-    if rec is not None:
-        return rec.add(_lib.CMD_CONV_DGRAD_BOTH, d, (dy, w_bwd, relu_mask0, relu_mask1, dx0, dx1), ())
-    lib = _lib.load()
-    _lib.check(lib.colvo_conv_dgrad_both(C.byref(d), _lib.ptr(dy), _lib.ptr(w_bwd), _lib.ptr(relu_mask0), _lib.ptr(relu_mask1),
-                                         _lib.ptr(dx0), _lib.ptr(dx1), _lib.stream_ptr()), "colvo_conv_dgrad_both")
+    _issue(_lib.CMD_CONV_DGRAD_BOTH, d, (dy, w_bwd, relu_mask0, relu_mask1, dx0, dx1))
 
 
 def conv_dgrad_planes(d: ConvDesc, dy, w_master, c_begin: int, c_count: int, dst, accumulate: bool = False) -> None:
     """Input gradient w.r.t. channels [c_begin, c_begin + c_count) only, as fp32 planes dst [c_count, B, 1, Hi, Wi]
     (include/colvo.h colvo_conv_dgrad_planes)."""
     _need_cuda(dy, w_master, dst)
-    rec = program.recording()
-    if rec is not None:
-        return rec.add(_lib.CMD_CONV_DGRAD_PLANES, d, (dy, w_master, dst), (c_begin, c_count, int(accumulate)))
-    lib = _lib.load()
-    _lib.check(lib.colvo_conv_dgrad_planes(C.byref(d), _lib.ptr(dy), _lib.ptr(w_master), c_begin, c_count, _lib.ptr(dst),
-                                           int(accumulate), _lib.stream_ptr()), "colvo_conv_dgrad_planes")
+    _issue(_lib.CMD_CONV_DGRAD_PLANES, d, (dy, w_master, dst), (c_begin, c_count, int(accumulate)))
 
 
 def conv_head_fused_ok(d: ConvDesc) -> bool:
@@ -93,24 +84,14 @@ def conv_head_fused(d: ConvDesc, x, w_fwd, bias, head_w, head_b, y, depth, pose_
     """The narrow full-resolution layer and the depth head behind it in one pass (include/colvo.h colvo_conv_head_fused): writes the
     layer's output y (NHWC bf16), depth [B,1,H,W] fp32 and -- with pose_in -- the two depth channels of PoseNet's input."""
     _need_cuda(x, w_fwd, bias, head_w, head_b, y, depth, pose_in)
-    rec = program.recording()
-    if rec is not None:
-        return rec.add(_lib.CMD_CONV_HEAD_FUSED, d, (x, w_fwd, bias, head_w, head_b, y, depth, pose_in), (), (MIN_DEPTH, MAX_DEPTH))
-    lib = _lib.load()
-    _lib.check(lib.colvo_conv_head_fused(C.byref(d), _lib.ptr(x), _lib.ptr(w_fwd), _lib.ptr(bias), _lib.ptr(head_w), _lib.ptr(head_b),
-                                         MIN_DEPTH, MAX_DEPTH, _lib.ptr(y), _lib.ptr(depth), _lib.ptr(pose_in), _lib.stream_ptr()),
-               "colvo_conv_head_fused")
+    _issue(_lib.CMD_CONV_HEAD_FUSED, d, (x, w_fwd, bias, head_w, head_b, y, depth, pose_in), (), (MIN_DEPTH, MAX_DEPTH))
 
 
 def pack_stem_pose(frames, stem, pose_in) -> None:
     """frames [2B,3,H,W] fp32 -> stem [2B,H,W,8] bf16 and the rgb channels of pose_in [B,H,W,8] bf16 (colvo_pack_stem_pose)."""
     _need_cuda(frames, stem, pose_in)
     B2, _, H, W = frames.shape
-    rec = program.recording()
-    if rec is not None:
-        return rec.add(_lib.CMD_PACK_STEM_POSE, None, (frames, stem, pose_in), (B2, H, W))
-    _lib.check(_lib.load().colvo_pack_stem_pose(_lib.ptr(frames), B2, H, W, _lib.ptr(stem), _lib.ptr(pose_in), _lib.stream_ptr()),
-               "colvo_pack_stem_pose")
+    _issue(_lib.CMD_PACK_STEM_POSE, None, (frames, stem, pose_in), (B2, H, W))
 
 
 def conv_bwd_fused_ok(d: ConvDesc) -> bool:
@@ -123,13 +104,7 @@ def conv_bwd_fused(d: ConvDesc, dy, w_bwd, x, relu_mask: bool, dx, dw, db, head_
     OUTPUT and the gradient is made on the fly from the depth head's d(pre) plane and weights; head_partials
     ([conv_bwd_fused_head_rows(d), 145] floats): the head's own weight gradient as partial rows for depth_head_wgrad_reduce."""
     _need_cuda(dy, w_bwd, x, dx, dw, db, head_dpre, head_w, head_partials)
-    rec = program.recording()
-    if rec is not None:
-        return rec.add(_lib.CMD_CONV_BWD_FUSED, d, (dy, w_bwd, x, dx, dw, db, head_dpre, head_w, head_partials), (int(relu_mask),))
-    lib = _lib.load()
-    _lib.check(lib.colvo_conv_bwd_fused(C.byref(d), _lib.ptr(dy), _lib.ptr(w_bwd), _lib.ptr(x), int(relu_mask), _lib.ptr(dx),
-                                        _lib.ptr(dw), _lib.ptr(db), _lib.ptr(head_dpre), _lib.ptr(head_w), _lib.ptr(head_partials),
-                                        _lib.stream_ptr()), "colvo_conv_bwd_fused")
+    _issue(_lib.CMD_CONV_BWD_FUSED, d, (dy, w_bwd, x, dx, dw, db, head_dpre, head_w, head_partials), (int(relu_mask),))
 
 
 def conv_bwd_fused_head_rows(d: ConvDesc) -> int:
@@ -148,23 +123,14 @@ def depth_head_wgrad_mfma(y, dpre, dw, db) -> None:
     if rows <= 0:
         raise RuntimeError("colvo_depth_head_wgrad_mfma_rows failed")
     hp = torch.empty(rows * 145, device=y.device, dtype=torch.float32)
-    rec = program.recording()
-    if rec is not None:
-        rec.add(_lib.CMD_HEAD_WGRAD_MFMA, None, (y, dpre, hp), (B, H, W))
-        return rec.add(_lib.CMD_HEAD_WGRAD_REDUCE, None, (hp, dw, db), (int(rows),))
-    _lib.check(lib.colvo_depth_head_wgrad_mfma(_lib.ptr(y), _lib.ptr(dpre), B, H, W, _lib.ptr(hp), _lib.stream_ptr()), "colvo_depth_head_wgrad_mfma")
-    _lib.check(lib.colvo_depth_head_wgrad_reduce(_lib.ptr(hp), int(rows), _lib.ptr(dw), _lib.ptr(db), _lib.stream_ptr()),
-               "colvo_depth_head_wgrad_reduce")
+    _issue(_lib.CMD_HEAD_WGRAD_MFMA, None, (y, dpre, hp), (B, H, W))
+    _issue(_lib.CMD_HEAD_WGRAD_REDUCE, None, (hp, dw, db), (int(rows),))
 
 
 def depth_head_wgrad_reduce(partials, rows: int, dw, db) -> None:
     """dw [9][16] / db [1] += the column sums of partials [rows][145] (fixed order)."""
     _need_cuda(partials, dw, db)
-    rec = program.recording()
-    if rec is not None:
-        return rec.add(_lib.CMD_HEAD_WGRAD_REDUCE, None, (partials, dw, db), (int(rows),))
-    _lib.check(_lib.load().colvo_depth_head_wgrad_reduce(_lib.ptr(partials), int(rows), _lib.ptr(dw), _lib.ptr(db), _lib.stream_ptr()),
-               "colvo_depth_head_wgrad_reduce")
+    _issue(_lib.CMD_HEAD_WGRAD_REDUCE, None, (partials, dw, db), (int(rows),))
 
 
 def conv_wgrad_scratch(d: ConvDesc, device) -> torch.Tensor:
@@ -181,21 +147,9 @@ def conv_wgrad(d: ConvDesc, x0, x1, dy, dw, db, scratch: Optional[torch.Tensor] 
     layers then store instead of adding (include/colvo.h colvo_conv_wgrad_clean)."""
     _need_cuda(x0, x1, dy, dw, db, scratch)
     nb = 0 if scratch is None else scratch.numel() * scratch.element_size()
-    rec = program.recording()
-    if rec is not None:
-        # (i[2] = "the arena is still zero": patched per replay by Program.set_flags, nn._ArenaModule._run_pass)
-        return rec.add(_lib.CMD_CONV_WGRAD, d, (x0, x1, dy, dw, db, scratch), (nb, 0, 0), flag_slot=2 if scratch is None else None)
-    lib = _lib.load()
-    if scratch is not None:
-        _lib.check(lib.colvo_conv_wgrad_det(C.byref(d), _lib.ptr(x0), _lib.ptr(x1), _lib.ptr(dy), _lib.ptr(dw), _lib.ptr(db),
-                                            _lib.ptr(scratch), nb, _lib.stream_ptr()), "colvo_conv_wgrad_det")
-        return
-    if arena_is_zero:
-        _lib.check(lib.colvo_conv_wgrad_clean(C.byref(d), _lib.ptr(x0), _lib.ptr(x1), _lib.ptr(dy), _lib.ptr(dw), _lib.ptr(db), 1,
-                                              _lib.stream_ptr()), "colvo_conv_wgrad_clean")
-        return
-    _lib.check(lib.colvo_conv_wgrad(C.byref(d), _lib.ptr(x0), _lib.ptr(x1), _lib.ptr(dy), _lib.ptr(dw),
-                                    _lib.ptr(db), _lib.stream_ptr()), "colvo_conv_wgrad")
+    # (i[2] = "the arena is still zero": recorded, it is patched per replay by Program.set_flags, nn._ArenaModule._run_pass)
+    _issue(_lib.CMD_CONV_WGRAD, d, (x0, x1, dy, dw, db, scratch), (nb, 0, int(arena_is_zero)),
+           flag_slot=2 if scratch is None else None)
 
 
 def conv_wgrad_splits(d: ConvDesc) -> int:
@@ -211,12 +165,7 @@ def conv_wgrad_slabs(d: ConvDesc, x0, x1, dy, scratch: torch.Tensor) -> None:
     slab of `scratch` (conv_wgrad_scratch); nothing is added to dw / db until wgrad_reduce_group."""
     _need_cuda(x0, x1, dy, scratch)
     nb = scratch.numel() * scratch.element_size()
-    rec = program.recording()
-    if rec is not None:
-        return rec.add(_lib.CMD_CONV_WGRAD, d, (x0, x1, dy, None, None, scratch), (nb, 1))
-    lib = _lib.load()
-    _lib.check(lib.colvo_conv_wgrad_slabs(C.byref(d), _lib.ptr(x0), _lib.ptr(x1), _lib.ptr(dy), _lib.ptr(scratch), nb,
-                                          _lib.stream_ptr()), "colvo_conv_wgrad_slabs")
+    _issue(_lib.CMD_CONV_WGRAD, d, (x0, x1, dy, None, None, scratch), (nb, 1))
 
 
 def wgrad_reduce_group(sets) -> None:
@@ -232,10 +181,7 @@ def wgrad_reduce_group(sets) -> None:
         arr[i].scratch, arr[i].dw, arr[i].db = scratch.data_ptr(), dw.data_ptr(), _lib.ptr(db)
         arr[i].nsplit, arr[i].Cout, arr[i].Ctot = int(nsplit), int(cout), int(ctot)
         keep += [scratch, dw, db]
-    rec = program.recording()
-    if rec is not None:
-        return rec.add(_lib.CMD_WGRAD_REDUCE_GROUP, None, (), (n,), raw=[(0, C.addressof(arr), (arr, keep))])
-    _lib.check(_lib.load().colvo_wgrad_reduce_group(arr, n, _lib.stream_ptr()), "colvo_wgrad_reduce_group")
+    _issue(_lib.CMD_WGRAD_REDUCE_GROUP, None, (), (n,), raw=[(0, C.addressof(arr), (arr, keep))])
 
 
 def pack_weights(w_master: torch.Tensor, dtype: torch.dtype, w_fwd: Optional[torch.Tensor],
@@ -261,21 +207,15 @@ def pack_nchw(srcs: Sequence[torch.Tensor], Cpad: int, dtype: torch.dtype, out: 
               ) -> torch.Tensor:
     """Concatenate NCHW fp32 tensors along channels into one NHWC feature map with Cpad channels."""
     _need_cuda(*srcs)
+    n = len(srcs)
+    if n > 4:                                            # (the command has four source slots)
+        raise RuntimeError(f"colvo_pack_nchw: {n} sources, at most 4")
     B, _, H, W = srcs[0].shape
     srcs = [s.contiguous() for s in srcs]
     if out is None:
         out = torch.empty(B, H, W, Cpad, device=srcs[0].device, dtype=dtype)
-    n = len(srcs)
-    rec = program.recording()
-    if rec is not None:
-        rec.add(_lib.CMD_PACK_NCHW, None, list(srcs) + [None] * (4 - n) + [out],
-                [dt_code(dtype)] + [s.shape[1] for s in srcs] + [0] * (4 - n) + [n, B, H, W, Cpad])
-        return out
-    ptrs = (C.c_void_p * n)(*[s.data_ptr() for s in srcs])
-    chans = (C.c_int32 * n)(*[s.shape[1] for s in srcs])
-    lib = _lib.load()
-    _lib.check(lib.colvo_pack_nchw(dt_code(dtype), ptrs, chans, n, B, H, W, Cpad, _lib.ptr(out), _lib.stream_ptr()),
-               "colvo_pack_nchw")
+    _issue(_lib.CMD_PACK_NCHW, None, list(srcs) + [None] * (4 - n) + [out],
+           [dt_code(dtype)] + [s.shape[1] for s in srcs] + [0] * (4 - n) + [n, B, H, W, Cpad])
     return out
 
 
@@ -286,13 +226,7 @@ def unpack_nhwc_grad(dsrc: torch.Tensor, c_begin: int, c_count: int, dst: torch.
     _need_cuda(dsrc, dst)
     B, H, W, Cpad = dsrc.shape
     flags = int(bool(accumulate)) | (2 if by_channel else 0)
-    rec = program.recording()
-    if rec is not None:
-        return rec.add(_lib.CMD_UNPACK_NHWC_GRAD, None, (dsrc, dst),
-                       (dt_code(dsrc.dtype), B, H, W, Cpad, c_begin, c_count, flags))
-    lib = _lib.load()
-    _lib.check(lib.colvo_unpack_nhwc_grad(dt_code(dsrc.dtype), _lib.ptr(dsrc), B, H, W, Cpad, c_begin, c_count,
-                                          _lib.ptr(dst), flags, _lib.stream_ptr()), "colvo_unpack_nhwc_grad")
+    _issue(_lib.CMD_UNPACK_NHWC_GRAD, None, (dsrc, dst), (dt_code(dsrc.dtype), B, H, W, Cpad, c_begin, c_count, flags))
 
 
 def relu_bwd_inplace(y: torch.Tensor, dy: torch.Tensor) -> None:
@@ -305,26 +239,14 @@ def relu_bwd_inplace(y: torch.Tensor, dy: torch.Tensor) -> None:
 def depth_head_fwd(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, depth: torch.Tensor) -> None:
     _need_cuda(x, w, bias, depth)
     B, H, W, Cc = x.shape
-    rec = program.recording()
-    if rec is not None:
-        return rec.add(_lib.CMD_DEPTH_HEAD_FWD, None, (x, w, bias, depth), (dt_code(x.dtype), B, H, W, Cc),
-                       (MIN_DEPTH, MAX_DEPTH))
-    lib = _lib.load()
-    _lib.check(lib.colvo_depth_head_fwd(dt_code(x.dtype), _lib.ptr(x), _lib.ptr(w), _lib.ptr(bias), B, H, W, Cc,
-                                        MIN_DEPTH, MAX_DEPTH, _lib.ptr(depth), _lib.stream_ptr()), "colvo_depth_head_fwd")
+    _issue(_lib.CMD_DEPTH_HEAD_FWD, None, (x, w, bias, depth), (dt_code(x.dtype), B, H, W, Cc), (MIN_DEPTH, MAX_DEPTH))
 
 
 def depth_head_bwd(x, w, depth, d_depth, scratch, dx, dw, db) -> None:
     _need_cuda(x, w, depth, d_depth, scratch, dx, dw, db)
     B, H, W, Cc = x.shape
-    rec = program.recording()
-    if rec is not None:
-        return rec.add(_lib.CMD_DEPTH_HEAD_BWD, None, (x, w, depth, d_depth, scratch, dx, dw, db),
-                       (dt_code(x.dtype), B, H, W, Cc), (MIN_DEPTH, MAX_DEPTH))
-    lib = _lib.load()
-    _lib.check(lib.colvo_depth_head_bwd(dt_code(x.dtype), _lib.ptr(x), _lib.ptr(w), _lib.ptr(depth), _lib.ptr(d_depth),
-                                        B, H, W, Cc, MIN_DEPTH, MAX_DEPTH, _lib.ptr(scratch), _lib.ptr(dx), _lib.ptr(dw),
-                                        _lib.ptr(db), _lib.stream_ptr()), "colvo_depth_head_bwd")
+    _issue(_lib.CMD_DEPTH_HEAD_BWD, None, (x, w, depth, d_depth, scratch, dx, dw, db), (dt_code(x.dtype), B, H, W, Cc),
+           (MIN_DEPTH, MAX_DEPTH))
 
 
 def depth_head_bwd_parts(x, w, depth, g_first, g_second, g_raw, scale_a, scale_b, scratch, dx, g_raw_second=None) -> None:
@@ -333,17 +255,8 @@ def depth_head_bwd_parts(x, w, depth, g_first, g_second, g_raw, scale_a, scale_b
     depth_head_wgrad."""
     _need_cuda(x, w, depth, g_first, g_second, g_raw, scale_a, scale_b, scratch, dx, g_raw_second)
     B, H, W, Cc = x.shape
-    rec = program.recording()
-    if rec is not None:
-        return rec.add(_lib.CMD_DEPTH_HEAD_BWD_PARTS, None,
-                       (x, w, depth, g_first, g_second, g_raw, scale_a, scale_b, scratch, dx, g_raw_second),
-                       (dt_code(x.dtype), B, H, W, Cc), (MIN_DEPTH, MAX_DEPTH))
-    lib = _lib.load()
-    _lib.check(lib.colvo_depth_head_bwd_parts(dt_code(x.dtype), _lib.ptr(x), _lib.ptr(w), _lib.ptr(depth), _lib.ptr(g_first),
-                                              _lib.ptr(g_second), _lib.ptr(g_raw), _lib.ptr(g_raw_second), _lib.ptr(scale_a),
-                                              _lib.ptr(scale_b),
-                                              B, H, W, Cc, MIN_DEPTH, MAX_DEPTH, _lib.ptr(scratch), _lib.ptr(dx), 0, 0,
-                                              _lib.stream_ptr()), "colvo_depth_head_bwd_parts")
+    _issue(_lib.CMD_DEPTH_HEAD_BWD_PARTS, None, (x, w, depth, g_first, g_second, g_raw, scale_a, scale_b, scratch, dx, g_raw_second),
+           (dt_code(x.dtype), B, H, W, Cc), (MIN_DEPTH, MAX_DEPTH))
 
 
 def zero_multi(tensors) -> None:
@@ -401,28 +314,14 @@ def depth_head_wgrad(x, dpre, dw, db, deterministic: bool = False) -> None:
             raise RuntimeError("deterministic depth-head weight gradient: only the 16-channel head is supported")
     if nb:
         scr = torch.empty((nb + 3) // 4, device=x.device, dtype=torch.float32)
-    rec = program.recording()
-    if rec is not None:
-        return rec.add(_lib.CMD_DEPTH_HEAD_WGRAD, None, (x, dpre, dw, db, scr), (dt_code(x.dtype), B, H, W, Cc, nb))
-    if scr is not None:
-        _lib.check(lib.colvo_depth_head_wgrad_det(dt_code(x.dtype), _lib.ptr(x), _lib.ptr(dpre), B, H, W, Cc, _lib.ptr(dw),
-                                                  _lib.ptr(db), _lib.ptr(scr), nb, _lib.stream_ptr()), "colvo_depth_head_wgrad_det")
-        return
-    _lib.check(lib.colvo_depth_head_wgrad(dt_code(x.dtype), _lib.ptr(x), _lib.ptr(dpre), B, H, W, Cc, _lib.ptr(dw),
-                                          _lib.ptr(db), _lib.stream_ptr()), "colvo_depth_head_wgrad")
+    _issue(_lib.CMD_DEPTH_HEAD_WGRAD, None, (x, dpre, dw, db, scr), (dt_code(x.dtype), B, H, W, Cc, nb))
 
 
 def pose_head_fwd(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, out: torch.Tensor) -> None:
     """out: 8*B floats, planar [pose Bx6 | lcc_a B | lcc_b B]."""
     _need_cuda(x, w, bias, out)
     B, H, W, Cc = x.shape
-    rec = program.recording()
-    if rec is not None:
-        return rec.add(_lib.CMD_POSE_HEAD_FWD, None, (x, w, bias, out), (dt_code(x.dtype), B, H * W, Cc),
-                       (POSE_SCALE, LCC_SCALE))
-    lib = _lib.load()
-    _lib.check(lib.colvo_pose_head_fwd(dt_code(x.dtype), _lib.ptr(x), _lib.ptr(w), _lib.ptr(bias), B, H * W, Cc,
-                                       POSE_SCALE, LCC_SCALE, _lib.ptr(out), _lib.stream_ptr()), "colvo_pose_head_fwd")
+    _issue(_lib.CMD_POSE_HEAD_FWD, None, (x, w, bias, out), (dt_code(x.dtype), B, H * W, Cc), (POSE_SCALE, LCC_SCALE))
 
 
 def pose_head_bwd(x, w, d_pose, d_a, d_b, dx, dw, db, scale_a=None, scale_b=None, deterministic: bool = False) -> None:
@@ -430,16 +329,8 @@ def pose_head_bwd(x, w, d_pose, d_a, d_b, dx, dw, db, scale_a=None, scale_b=None
     all three (None = 1).  deterministic: the atomics-free form (colvo_pose_head_bwd_det)."""
     _need_cuda(x, w, d_pose, d_a, d_b, dx, dw, db, scale_a, scale_b)
     B, H, W, Cc = x.shape
-    rec = program.recording()
-    if rec is not None:
-        return rec.add(_lib.CMD_POSE_HEAD_BWD, None, (x, w, d_pose, d_a, d_b, dx, dw, db, scale_a, scale_b),
-                       (dt_code(x.dtype), B, H * W, Cc, int(deterministic)), (POSE_SCALE, LCC_SCALE))
-    lib = _lib.load()
-    fn = lib.colvo_pose_head_bwd_det if deterministic else lib.colvo_pose_head_bwd
-    _lib.check(fn(dt_code(x.dtype), _lib.ptr(x), _lib.ptr(w), _lib.ptr(d_pose), _lib.ptr(d_a),
-                  _lib.ptr(d_b), _lib.ptr(scale_a), _lib.ptr(scale_b), B, H * W, Cc, POSE_SCALE,
-                  LCC_SCALE, _lib.ptr(dx), _lib.ptr(dw), _lib.ptr(db), _lib.stream_ptr()),
-               "colvo_pose_head_bwd")
+    _issue(_lib.CMD_POSE_HEAD_BWD, None, (x, w, d_pose, d_a, d_b, dx, dw, db, scale_a, scale_b),
+           (dt_code(x.dtype), B, H * W, Cc, int(deterministic)), (POSE_SCALE, LCC_SCALE))
 
 
 def adam_step_t(param, grad, exp_avg, exp_avg_sq, t: int, *, lr, beta1, beta2, eps, grad_scale=1.0) -> None:

@@ -1,9 +1,11 @@
-"""Recorded command lists: the host side of colvo_run_commands (include/colvo.h).
+"""Commands: the host side of colvo_run_commands / colvo_run_command (include/colvo.h).
 
-`ops.*` calls made while a Program is recording are appended to it instead of being launched.  The recorded list is then
-replayed with ONE C-ABI call per network pass.  All tensors a command refers to are kept alive by the Program (the
-activation buffers of a plan are therefore persistent); the few pointers that differ from call to call -- input images,
-the output, incoming gradients -- are registered as externals and patched before each replay.
+Every recordable `ops.*` call (the conv, feature-map packing and head ops) is encoded as one ColvoCmd (encode).  Outside a
+recording it runs at once as a single command (colvo_run_command); while a Program is recording it is appended to the
+Program instead, and the recorded list is replayed with ONE C-ABI call per network pass.  Both go through the library's one
+decoder.  All tensors a recorded command refers to are kept alive by the Program (the activation buffers of a plan are
+therefore persistent); the few pointers that differ from call to call -- input images, the output, incoming gradients --
+are registered as externals and patched before each replay.
 """
 from __future__ import annotations
 
@@ -19,6 +21,30 @@ _active: Optional["Program"] = None
 
 def recording() -> Optional["Program"]:
     return _active
+
+
+def encode(op: int, desc=None, p: Sequence[Optional[torch.Tensor]] = (), i: Sequence[int] = (), f: Sequence[float] = (),
+           raw: Sequence = ()) -> Tuple[_lib.Cmd, List[object]]:
+    """One command (slot layout: include/colvo.h COLVO_CMD_*) and the objects it refers to, which must outlive its last run.
+    p: tensors (None = NULL) for pointer slots 0, 1, ...; raw: [(slot, address, keepalive)] -- pointer slots that are not
+    tensors (a host-side table the command refers to)."""
+    c = _lib.Cmd()
+    c.op = op
+    if desc is not None:
+        c.desc = desc
+    keep = []
+    for slot, address, keepalive in raw:
+        c.p[slot] = address
+        keep.append(keepalive)
+    for k, t in enumerate(p):
+        if t is not None:
+            c.p[k] = t.data_ptr()
+            keep.append(t)
+    for k, v in enumerate(i):
+        c.i[k] = int(v)
+    for k, v in enumerate(f):
+        c.f[k] = float(v)
+    return c, keep
 
 
 class Program:
@@ -56,25 +82,13 @@ class Program:
 
     def add(self, op: int, desc=None, p: Sequence[Optional[torch.Tensor]] = (), i: Sequence[int] = (),
             f: Sequence[float] = (), raw: Sequence = (), flag_slot: Optional[int] = None) -> None:
-        """raw: [(slot, address, keepalive)] -- pointer slots that are not tensors (a host-side table the command refers to)."""
-        c = _lib.Cmd()
-        c.op, c.stream = op, self.stream
-        if desc is not None:
-            c.desc = desc
-        for slot, address, keepalive in raw:
-            c.p[slot] = address
-            self.keep.append(keepalive)
-        for k, t in enumerate(p):
-            if t is not None:
-                c.p[k] = t.data_ptr()
-                self.keep.append(t)
-        for k, v in enumerate(i):
-            c.i[k] = int(v)
-        for k, v in enumerate(f):
-            c.f[k] = float(v)
+        c, keep = encode(op, desc, p, i, f, raw)
+        c.stream = self.stream
+        self.keep += keep
         if self.stream:
             self.uses_side = True
         if flag_slot is not None:            # an integer argument the host sets before each replay (set_flags)
+            c.i[flag_slot] = self._flag_value    # (every flag slot holds the value set_flags last wrote: it skips equal values)
             self.flag_slots.append((len(self.cmds), flag_slot))
         self.cmds.append(c)
 

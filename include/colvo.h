@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define COLVO_ABI_VERSION 10
+#define COLVO_ABI_VERSION 11
 
 typedef void* colvo_stream_t; /* hipStream_t */
 
@@ -448,7 +448,9 @@ int colvo_read_npy_u8_frames(const char* const* paths, int n, int h, int w, uint
 /* ------------------------------------------------------------------------------------------- *
  * Command lists: ONE call enqueues a recorded sequence of the entry points above (a network's  *
  * forward or backward) on a main and a side stream -- the host's per-launch cost, not the GPU, *
- * bounded the batch-8 step when every layer was a separate host call.                          *
+ * bounded the batch-8 step when every layer was a separate host call.  The same encoding is    *
+ * the only way the Python ops reach these entry points: an op outside a recording is ONE       *
+ * command issued by colvo_run_command.                                                         *
  * ------------------------------------------------------------------------------------------- */
 enum {
     COLVO_CMD_CONV_FWD = 1,      /* p: x0 x1 w_fwd bias y */
@@ -490,6 +492,10 @@ typedef struct ColvoCmd {
 /* Enqueue cmds[0..n) in order; side_stream may be NULL when no command uses it.  FORK/JOIN use a small ring of
  * library-owned events (host objects; still no device allocation).  Stops at the first failing command. */
 int colvo_run_commands(const ColvoCmd* cmds, int n, colvo_stream_t main_stream, colvo_stream_t side_stream);
+/* One command on `stream`: the same call of its entry point that colvo_run_commands makes, and nothing else (no events, no
+ * capture handling: under stream capture its launches are plain nodes on the capturing stream).  Returns the entry point's
+ * code, with its own colvo_last_error() message.  cmd->stream must be 0; FORK, JOIN and SIDE_SYNC are rejected. */
+int colvo_run_command(const ColvoCmd* cmd, colvo_stream_t stream);
 /* colvo_run_commands spreads consecutive FORKs over the caller's side stream and up to n library-owned ones (default 1,
  * COLVO_SIDE_STREAMS - 1).  A process that drives MORE streams of its own beside the main and the side stream -- RCCL's
  * communicator stream in data-parallel training -- must set n = 0: with four or more hardware queues active and cross-queue

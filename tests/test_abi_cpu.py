@@ -190,6 +190,61 @@ def test_wgrad_plan_queries_have_no_side_effects(lib):
     assert n == 2 * 4 * (20 + 7)
 
 
+def test_every_command_reaches_its_entry_point(lib):
+    """colvo_run_command runs one command through the decoder that eager ops and recorded passes share (csrc/program.hip run_one).
+    Sent with NULL pointers, every recordable COLVO_CMD_* op, and every form of the ops that pick one from their slots, is refused
+    by the argument check of the entry point it must reach, before any launch.  Commands that order streams are refused."""
+    from coivo_amd import _lib, ops
+    buf = (C.c_float * 16)()
+    h = C.addressof(buf)                                 # non-NULL; no call below gets past its checks to dereference it
+    d = ops.conv_desc(torch.bfloat16, 2, 16, 16, 16, 16)
+
+    def refused(op, desc=d, p=(), i=(), stream=0):
+        c = _lib.Cmd()
+        c.op, c.stream, c.desc = op, stream, desc
+        for k, v in enumerate(p):
+            c.p[k] = v
+        for k, v in enumerate(i):
+            c.i[k] = v
+        assert lib.colvo_run_command(C.byref(c), 0) != 0, op
+        return lib.colvo_last_error().decode()
+
+    entry = {_lib.CMD_CONV_FWD: "colvo_conv_fwd", _lib.CMD_CONV_DGRAD: "colvo_conv_dgrad", _lib.CMD_CONV_WGRAD: "colvo_conv_wgrad",
+             _lib.CMD_PACK_NCHW: "colvo_pack_nchw", _lib.CMD_UNPACK_NHWC_GRAD: "colvo_unpack_nhwc_grad",
+             _lib.CMD_DEPTH_HEAD_FWD: "colvo_depth_head_fwd", _lib.CMD_DEPTH_HEAD_BWD: "colvo_depth_head_bwd",
+             _lib.CMD_DEPTH_HEAD_WGRAD: "colvo_depth_head_wgrad", _lib.CMD_POSE_HEAD_FWD: "colvo_pose_head_fwd",
+             _lib.CMD_POSE_HEAD_BWD: "colvo_pose_head_bwd", _lib.CMD_DEPTH_HEAD_BWD_PARTS: "colvo_depth_head_bwd_parts",
+             _lib.CMD_CONV_DGRAD_BOTH: "colvo_conv_dgrad_both", _lib.CMD_WGRAD_REDUCE_GROUP: "colvo_wgrad_reduce_group",
+             _lib.CMD_CONV_DGRAD_PLANES: "colvo_conv_dgrad_planes", _lib.CMD_CONV_BWD_FUSED: "colvo_conv_bwd_fused",
+             _lib.CMD_HEAD_WGRAD_REDUCE: "colvo_depth_head_wgrad_reduce", _lib.CMD_CONV_HEAD_FUSED: "colvo_conv_head_fused",
+             _lib.CMD_PACK_STEM_POSE: "colvo_pack_stem_pose", _lib.CMD_HEAD_WGRAD_MFMA: "colvo_depth_head_wgrad_mfma"}
+    control = {_lib.CMD_FORK, _lib.CMD_JOIN, _lib.CMD_SIDE_SYNC}
+    assert set(entry) | control == {v for k, v in vars(_lib).items() if k.startswith("CMD_")}
+    for op, name in entry.items():
+        msg = refused(op)
+        assert msg.startswith(name + ":"), (name, msg)
+
+    # the forms: colvo_conv_wgrad_clean (i[2]) and _det (p[5]) share colvo_conv_wgrad's pointer check; _slabs (p[5] and i[1]) ignores
+    # dw / db, so it is the one that gets to its own check -- a batch it would have to slice (512 MiB per image)
+    big = ops.conv_desc(torch.bfloat16, 2, 1024, 1024, 256, 256)
+    for form, cmd in (("colvo_conv_wgrad: null pointer", dict(i=(0, 0, 1))),
+                      ("colvo_conv_wgrad: null pointer", dict(p=(0, 0, 0, 0, 0, h), i=(64, 0, 0))),
+                      ("colvo_conv_wgrad_slabs: batch 2 would be sliced", dict(desc=big, p=(h, 0, h, 0, 0, h), i=(64, 1))),
+                      ("colvo_conv_wgrad: null pointer", dict(desc=big, p=(h, 0, h, 0, 0, h), i=(64, 0)))):
+        msg = refused(_lib.CMD_CONV_WGRAD, **cmd)
+        assert msg.startswith(form), (form, msg)
+    msg = refused(_lib.CMD_DEPTH_HEAD_WGRAD, p=(0, 0, 0, 0, h))                       # p[4]: scratch
+    assert msg.startswith("colvo_depth_head_wgrad_det:"), msg
+    msg = refused(_lib.CMD_POSE_HEAD_BWD, i=(0, 0, 0, 0, 1))                           # i[4]: det
+    assert msg.startswith("colvo_pose_head_bwd_det:"), msg
+
+    for op in control:
+        msg = refused(op)
+        assert msg.startswith("colvo_run_command:") and str(op) in msg, msg
+    msg = refused(_lib.CMD_CONV_FWD, stream=1)
+    assert msg.startswith("colvo_run_command:"), msg
+    assert lib.colvo_run_command(None, 0) != 0 and lib.colvo_last_error().startswith(b"colvo_run_command:")
+
 def test_every_kernel_form_has_a_distinct_name(lib):
     """colvo_form_counts / colvo_form_name: at most the 32 counters _lib.form_counts reads, every one named, no two alike, NULL beyond
     the last; the counters start at zero and a name lookup out of range does not crash."""
