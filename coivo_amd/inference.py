@@ -103,6 +103,21 @@ class Reconstruction(NamedTuple):
 
 
 @torch.no_grad()
+def run_networks(depth_net, pose_net, frames: torch.Tensor, *, chunk: int = 16):
+    """frames [N+1,3,H,W] of one sequence -> (depths [N+1,1,H,W], rel_poses [N,6]): DepthNet on every frame and PoseNet on every
+    consecutive pair (DCDP: PoseNet sees both depth maps), `chunk` frames or pairs per call."""
+    n = frames.shape[0]
+    depths = torch.cat([depth_net(frames[i:i + chunk].contiguous()) for i in range(0, n, chunk)])
+    poses = []
+    for i in range(0, n - 1, chunk):
+        j = min(i + chunk, n - 1)
+        pose, _, _ = pose_net(frames[i:j].contiguous(), frames[i + 1:j + 1].contiguous(),
+                              depths[i:j].contiguous(), depths[i + 1:j + 1].contiguous())
+        poses.append(pose)
+    return depths, torch.cat(poses)
+
+
+@torch.no_grad()
 def reconstruct_sequence(depth_net, pose_net, frames: torch.Tensor, K: torch.Tensor, *, stride: int = 4,
                          max_depth: float = MAX_DEPTH, chunk: int = 16) -> Reconstruction:
     """frames [N+1,3,H,W] of one sequence, K [3,3] or [N+1,3,3] -> depth of every frame, the pose of every consecutive
@@ -113,14 +128,7 @@ def reconstruct_sequence(depth_net, pose_net, frames: torch.Tensor, K: torch.Ten
     if K.dim() == 2:
         K = K.unsqueeze(0).expand(n, 3, 3)
     K = K.to(frames.device, torch.float32).contiguous()
-    depths = torch.cat([depth_net(frames[i:i + chunk].contiguous()) for i in range(0, n, chunk)])
-    poses = []
-    for i in range(0, n - 1, chunk):
-        j = min(i + chunk, n - 1)
-        pose, _, _ = pose_net(frames[i:j].contiguous(), frames[i + 1:j + 1].contiguous(),
-                              depths[i:j].contiguous(), depths[i + 1:j + 1].contiguous())
-        poses.append(pose)
-    rel = torch.cat(poses)
+    depths, rel = run_networks(depth_net, pose_net, frames, chunk=chunk)
     traj = integrate_trajectory(rel)
     cloud = stitch_point_cloud(depths, K, traj.to(frames.device, torch.float32), stride=stride, max_depth=max_depth)
     return Reconstruction(depths, rel, traj, cloud)

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define COLVO_ABI_VERSION 11
+#define COLVO_ABI_VERSION 12
 
 typedef void* colvo_stream_t; /* hipStream_t */
 
@@ -430,6 +430,20 @@ size_t colvo_stitch_workspace_ints(int N, int H, int W, int stride);
 int colvo_stitch_point_cloud(const float* depths, const float* K, const float* cam2world, int N, int H, int W,
                              int stride, float max_depth, int32_t* workspace, float* points, int32_t* n_points,
                              colvo_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------- *
+ * SURVEY.md §6  evaluation: depth error measures with per-image median scaling. *
+ * ------------------------------------------------------------------------------------------- */
+/* pred, gt [N,1,H,W] fp32; mask [N,1,H,W] uint8 or NULL.  A pixel is valid iff min_depth < gt < max_depth and mask != 0.
+ * Per image: s = med(gt) / med(pred) over the valid pixels (exact lower medians, rank (n-1)/2; s = 1 when median_scaling is 0),
+ * p = clamp(s * pred, min_depth, max_depth), and per_image[n][0..6] = abs_rel, sq_rel, rmse, rmse_log, a1, a2, a3 over the valid
+ * pixels; scale[n] = s, n_valid[n] = valid pixel count.  An image without a valid pixel gets NaN metrics and scale, n_valid 0.
+ * Deterministic (integer atomics only, fixed-order float reductions).  workspace: colvo_depth_metrics_workspace_bytes(N,H,W)
+ * bytes, 16-byte aligned (0 for a shape the call refuses).  N <= 65535, H*W < 2^30. */
+size_t colvo_depth_metrics_workspace_bytes(int N, int H, int W);
+int colvo_depth_metrics(const float* pred, const float* gt, const uint8_t* mask, int N, int H, int W, float min_depth,
+                        float max_depth, int median_scaling, void* workspace, double* per_image, float* scale,
+                        int32_t* n_valid, colvo_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------- *
  * SURVEY.md §8f-4  frames as a decoder delivers them -> the path's input format.                *
