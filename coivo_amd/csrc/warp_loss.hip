@@ -231,6 +231,7 @@ __device__ __forceinline__ SsimTerms ssim_terms(float sx, float sy, float sxx, f
 // of registers.  No LDS, no barriers, no redundant products; a 3-stage software pipeline keeps the
 // depth/target loads two rows ahead and the 12 tap gathers one row ahead of the arithmetic.
 constexpr int MCOLS = 62;
+constexpr int MROWS_MIN = 4;
 constexpr int MROWS_MAX = 64;
 
 // Rows per segment: the grid should fill the chip's resident-wave slots (256 CUs x 16 waves at 4 waves/SIMD) in
@@ -240,7 +241,7 @@ inline int pick_march_rows(int B, int H, int W, int cols = MCOLS, int halo_rows 
     const long cap = 256L * waves_per_cu;
     int best = 32;
     double best_cost = 1e30;
-    for (int r = 4; r <= MROWS_MAX; ++r) {
+    for (int r = MROWS_MIN; r <= MROWS_MAX; ++r) {
         const long waves = (long)B * ((H + r - 1) / r) * strips;
         const long rounds = (waves + cap - 1) / cap;
         const double cost = (double)rounds * (r + halo_rows + 2.0);      // steps per wave + ~2 steps of prologue / epilogue
@@ -255,7 +256,6 @@ __device__ __forceinline__ float dpp_from_left(float v) {    // lane i <- lane i
 __device__ __forceinline__ float dpp_from_right(float v) {   // lane i <- lane i+1 (0 into lane 63)
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x130, 0xf, 0xf, true));
 }
-__device__ __forceinline__ float hsum3(float v) { return v + dpp_from_left(v) + dpp_from_right(v); }
 
 // Horizontal 3-sums of N values in ONE asm statement: 2 N v_add_f32_dpp.  Written by hand because hipcc fused only a third
 // of the `v + dpp(v) + dpp(v)` forms into DPP adds and emitted v_mov_b32_dpp + v_add_f32 pairs for the rest (34 of the
@@ -430,25 +430,51 @@ __global__ __launch_bounds__(NT) void k_warp_loss_fwd_march(
     }
 }
 
-// deterministic two-stage reduction: fixed strided order, then an LDS tree
-__global__ __launch_bounds__(NT) void k_warp_loss_fwd_finalize(const float* __restrict__ partials, int nblk,
-                                                               float* __restrict__ loss_state) {
+// a 256-thread block's partial sums of NV per-thread values, fixed order (DPP inside each of the 4 waves, then the wave
+// pairs): thread k < NV writes out[k]
+template <int NV>
+__device__ __forceinline__ void block_partials(const float (&v)[NV], float* __restrict__ out) {
+    __shared__ float red[4][NV];
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+        const float t = wave_sum(v[k]);
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = t;
+    }
+    __syncthreads();
+    const int k = threadIdx.x;
+    if (k < NV) out[k] = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
+}
+
+// deterministic two-stage reduction of n value pairs (one 256-thread workgroup): fixed strided order, then an LDS tree.
+// The totals are valid in every thread.
+__device__ __forceinline__ void pair_sums(const float* __restrict__ partials, int n, float& a, float& c) {
     __shared__ float s0[NT], s1[NT];
-    float a = 0.0f, c = 0.0f;
-    for (int i = threadIdx.x; i < nblk; i += NT) { a += partials[2 * i]; c += partials[2 * i + 1]; }
+    a = 0.0f; c = 0.0f;
+    for (int i = threadIdx.x; i < n; i += NT) { a += partials[2 * i]; c += partials[2 * i + 1]; }
     s0[threadIdx.x] = a; s1[threadIdx.x] = c;
     __syncthreads();
     for (int o = NT / 2; o > 0; o >>= 1) {
         if ((int)threadIdx.x < o) { s0[threadIdx.x] += s0[threadIdx.x + o]; s1[threadIdx.x] += s1[threadIdx.x + o]; }
         __syncthreads();
     }
-    if (threadIdx.x == 0) {
-        const float denom = fmaxf(3.0f * s1[0], 1.0f);
-        loss_state[0] = s0[0] / denom;
-        loss_state[1] = 1.0f / denom;
-        loss_state[2] = s1[0];
-        loss_state[3] = s0[0];          // the masked sum itself: what a data-parallel caller adds up across ranks (colvo_warp_loss_rescale)
-    }
+    a = s0[0]; c = s1[0];
+}
+
+// loss_state of the photometric loss from its masked sum and valid-pixel count: loss, 1 / max(3 n, 1), n, and the masked sum
+// itself (what a data-parallel caller adds up across ranks, colvo_warp_loss_rescale)
+__device__ __forceinline__ void loss_state_store(float sum, float cnt, float* __restrict__ loss_state) {
+    const float denom = fmaxf(3.0f * cnt, 1.0f);
+    loss_state[0] = sum / denom;
+    loss_state[1] = 1.0f / denom;
+    loss_state[2] = cnt;
+    loss_state[3] = sum;
+}
+
+__global__ __launch_bounds__(NT) void k_warp_loss_fwd_finalize(const float* __restrict__ partials, int nblk,
+                                                               float* __restrict__ loss_state) {
+    float a, c;
+    pair_sums(partials, nblk, a, c);
+    if (threadIdx.x == 0) loss_state_store(a, c, loss_state);
 }
 
 constexpr int NPART = 14;                   // dt[3], dR[9], da, db
@@ -898,8 +924,6 @@ __global__ __launch_bounds__(NT, 2) void k_warp_loss_march_levels(MarchLevels ml
                                 item, live, b, seg, strip, lane, s_geo[wave]);
 }
 
-// fused forward, second kernel: blocks 0..B-1 fold the 14 gradient sums of one image (still unnormalised) into
-// gpart[b][14]; block B folds the loss sum and the valid count of ALL strips into loss_state.  Fixed orders: deterministic.
 // dR (row-major 3x3 gradient w.r.t. the rotation matrix) -> gradient w.r.t. the Euler angles (R = Rz Ry Rx)
 __device__ __forceinline__ void dR_to_euler(const float* dR, const float* p, float& drx, float& dry, float& drz) {
     const float sx = sinf(p[3]), cx = cosf(p[3]), sy = sinf(p[4]), cy = cosf(p[4]), sz = sinf(p[5]), cz = cosf(p[5]);
@@ -913,11 +937,22 @@ __device__ __forceinline__ void dR_to_euler(const float* dR, const float* p, flo
         + dR[3] * (cz * cy) + dR[4] * (cz * sy * sx - sz * cx) + dR[5] * (cz * sy * cx + sz * sx);
 }
 
+// The pose / LCC gradients of image b from its summed terms t (dt[3], dR[9], then da, db) in PoseNet's planar output layout:
+// d_pose[6b .. 6b+5] (translation, Euler angles), d_a[b] and d_b[b] when they are non-null (the geometric term has no LCC terms)
+__device__ __forceinline__ void pose_grad_store(const float* t, const float* pose, int b, float* __restrict__ d_pose,
+                                                float* __restrict__ d_a, float* __restrict__ d_b) {
+    float drx, dry, drz;
+    dR_to_euler(t + 3, pose + 6 * b, drx, dry, drz);
+    d_pose[6 * b + 0] = t[0]; d_pose[6 * b + 1] = t[1]; d_pose[6 * b + 2] = t[2];
+    d_pose[6 * b + 3] = drx; d_pose[6 * b + 4] = dry; d_pose[6 * b + 5] = drz;
+    if (d_a) d_a[b] = t[12];
+    if (d_b) d_b[b] = t[13];
+}
+
 // The finalize kernels run 1024 threads per workgroup: they are chains of dependent strided loads (one partial per strip
 // segment), so their duration is the number of sequential trips to L2 -- 7 -> 2 for the loss sums of BASELINE configs[1], 30 -> 8
 // at configs[2] -- not bandwidth.
 constexpr int FT = 1024;
-constexpr int FROWS = FT / NPART;           // 73 partial rows per pass
 
 // sums of NV per-thread values over the FT threads: DPP inside the wave, then thread 0 adds the 16 wave totals in order
 template <int NV>
@@ -939,22 +974,26 @@ __device__ __forceinline__ void block_sums(float (&v)[NV], float* sh) {
     }
 }
 
-// the 14 gradient sums of image b over its strip segments (partials of NPART_F floats each), fixed order; the result is
-// valid in threads 0..13 (and left in sh[0..13] after a barrier when `publish`)
+// the NV gradient sums of image b over its bpi partials (STRIDE floats each) with NTH threads, fixed order: NTH / NV partial
+// rows per pass, each a strided sum, then the rows in sequence.  The result is valid in threads 0 .. NV-1; sh holds NTH floats.
+template <int NTH, int NV, int STRIDE>
 __device__ __forceinline__ float image_sums(const float* __restrict__ pp, int b, int bpi, float* sh) {
-    const int tid = threadIdx.x, k = tid % NPART, r = tid / NPART;
+    constexpr int ROWS = NTH / NV;
+    const int tid = threadIdx.x, k = tid % NV, r = tid / NV;
     float acc = 0.0f;
-    if (r < FROWS) {
-        for (int i = r; i < bpi; i += FROWS) acc += pp[((size_t)b * bpi + i) * NPART_F + k];
-        sh[k * FROWS + r] = acc;
+    if (r < ROWS) {
+        for (int i = r; i < bpi; i += ROWS) acc += pp[((size_t)b * bpi + i) * STRIDE + k];
+        sh[k * ROWS + r] = acc;
     }
     __syncthreads();
     float t = 0.0f;
-    if (tid < NPART)
-        for (int i = 0; i < FROWS; ++i) t += sh[tid * FROWS + i];
+    if (tid < NV)
+        for (int i = 0; i < ROWS; ++i) t += sh[tid * ROWS + i];
     return t;
 }
 
+// fused forward, second kernel: blocks 0..B-1 fold the 14 gradient sums of one image (still unnormalised) into
+// gpart[b][14]; block B folds the loss sum and the valid count of ALL strips into loss_state.  Fixed orders: deterministic.
 // gunit (may be null): the pose / LCC gradients of every image, still UNNORMALISED, already converted to Euler angles, in
 // PoseNet's planar output layout [d_pose B x 6 | d_a B | d_b B] -- for consumers that apply dL/dloss / max(3 n, 1) themselves
 __global__ __launch_bounds__(FT) void k_warp_loss_fused_finalize(const float* __restrict__ partials, int blocks_per_image,
@@ -962,38 +1001,25 @@ __global__ __launch_bounds__(FT) void k_warp_loss_fused_finalize(const float* __
                                                                  float* __restrict__ gpart, float* __restrict__ gunit,
                                                                  float* __restrict__ loss_state) {
     __shared__ float sh[FT];
-    __shared__ float s1[NPART + 2];
+    __shared__ float s1[NPART];
     const int tid = threadIdx.x;
     if ((int)blockIdx.x == B) {
         const int n = B * blocks_per_image;
         float v[2] = {0.0f, 0.0f};
         for (int i = tid; i < n; i += FT) { v[0] += partials[(size_t)i * NPART_F + 14]; v[1] += partials[(size_t)i * NPART_F + 15]; }
         block_sums<2>(v, sh);
-        if (tid == 0) {
-            const float denom = fmaxf(3.0f * v[1], 1.0f);
-            loss_state[0] = v[0] / denom;
-            loss_state[1] = 1.0f / denom;
-            loss_state[2] = v[1];
-            loss_state[3] = v[0];       // the masked sum itself (colvo_warp_loss_rescale)
-        }
+        if (tid == 0) loss_state_store(v[0], v[1], loss_state);
         return;
     }
     const int b = blockIdx.x;
-    const float t = image_sums(partials, b, blocks_per_image, sh);
+    const float t = image_sums<FT, NPART, NPART_F>(partials, b, blocks_per_image, sh);
     if (tid < NPART) {
         gpart[b * NPART + tid] = t;
         s1[tid] = t;
     }
     if (gunit == nullptr) return;
     __syncthreads();
-    if (tid == 0) {
-        float drx, dry, drz;
-        dR_to_euler(s1 + 3, pose + 6 * b, drx, dry, drz);
-        gunit[6 * b + 0] = s1[0]; gunit[6 * b + 1] = s1[1]; gunit[6 * b + 2] = s1[2];
-        gunit[6 * b + 3] = drx; gunit[6 * b + 4] = dry; gunit[6 * b + 5] = drz;
-        gunit[6 * B + b] = s1[12];
-        gunit[7 * B + b] = s1[13];
-    }
+    if (tid == 0) pose_grad_store(s1, pose, b, gunit, gunit + 6 * B, gunit + 7 * B);
 }
 
 // fused backward: scale = dL/dloss / max(3 n_valid, 1).  Blocks 0..B-1: pose / LCC gradients of one image from gpart;
@@ -1013,21 +1039,7 @@ __global__ __launch_bounds__(NT) void k_warp_loss_fused_bwd(const float* __restr
         float tot[NPART];
 #pragma unroll
         for (int k = 0; k < NPART; ++k) tot[k] = scale * gpart[b * NPART + k];
-        const float* p = pose + 6 * b;
-        const float sx = sinf(p[3]), cx = cosf(p[3]), sy = sinf(p[4]), cy = cosf(p[4]), sz = sinf(p[5]), cz = cosf(p[5]);
-        const float* dR = tot + 3;  // row-major 3x3
-        const float drx = dR[1] * (cz * sy * cx + sz * sx) + dR[2] * (-cz * sy * sx + sz * cx)
-                        + dR[4] * (sz * sy * cx - cz * sx) + dR[5] * (-sz * sy * sx - cz * cx)
-                        + dR[7] * (cy * cx) + dR[8] * (-cy * sx);
-        const float dry = dR[0] * (-cz * sy) + dR[1] * (cz * cy * sx) + dR[2] * (cz * cy * cx)
-                        + dR[3] * (-sz * sy) + dR[4] * (sz * cy * sx) + dR[5] * (sz * cy * cx)
-                        + dR[6] * (-cy) + dR[7] * (-sy * sx) + dR[8] * (-sy * cx);
-        const float drz = dR[0] * (-sz * cy) + dR[1] * (-sz * sy * sx - cz * cx) + dR[2] * (-sz * sy * cx + cz * sx)
-                        + dR[3] * (cz * cy) + dR[4] * (cz * sy * sx - sz * cx) + dR[5] * (cz * sy * cx + sz * sx);
-        d_pose[6 * b + 0] = tot[0]; d_pose[6 * b + 1] = tot[1]; d_pose[6 * b + 2] = tot[2];
-        d_pose[6 * b + 3] = drx; d_pose[6 * b + 4] = dry; d_pose[6 * b + 5] = drz;
-        d_a[b] = tot[12];
-        d_b[b] = tot[13];
+        pose_grad_store(tot, pose, b, d_pose, d_a, d_b);
     }
 }
 
@@ -1044,63 +1056,21 @@ __global__ __launch_bounds__(64) void k_warp_loss_fused_bwd_params(const float* 
     float tot[NPART];
 #pragma unroll
     for (int k = 0; k < NPART; ++k) tot[k] = scale * gpart[b * NPART + k];
-    const float* p = pose + 6 * b;
-    const float sx = sinf(p[3]), cx = cosf(p[3]), sy = sinf(p[4]), cy = cosf(p[4]), sz = sinf(p[5]), cz = cosf(p[5]);
-    const float* dR = tot + 3;  // row-major 3x3
-    const float drx = dR[1] * (cz * sy * cx + sz * sx) + dR[2] * (-cz * sy * sx + sz * cx)
-                    + dR[4] * (sz * sy * cx - cz * sx) + dR[5] * (-sz * sy * sx - cz * cx)
-                    + dR[7] * (cy * cx) + dR[8] * (-cy * sx);
-    const float dry = dR[0] * (-cz * sy) + dR[1] * (cz * cy * sx) + dR[2] * (cz * cy * cx)
-                    + dR[3] * (-sz * sy) + dR[4] * (sz * cy * sx) + dR[5] * (sz * cy * cx)
-                    + dR[6] * (-cy) + dR[7] * (-sy * sx) + dR[8] * (-sy * cx);
-    const float drz = dR[0] * (-sz * cy) + dR[1] * (-sz * sy * sx - cz * cx) + dR[2] * (-sz * sy * cx + cz * sx)
-                    + dR[3] * (cz * cy) + dR[4] * (cz * sy * sx - sz * cx) + dR[5] * (cz * sy * cx + sz * sx);
-    d_pose[6 * b + 0] = tot[0]; d_pose[6 * b + 1] = tot[1]; d_pose[6 * b + 2] = tot[2];
-    d_pose[6 * b + 3] = drx; d_pose[6 * b + 4] = dry; d_pose[6 * b + 5] = drz;
-    d_a[b] = tot[12];
-    d_b[b] = tot[13];
+    pose_grad_store(tot, pose, b, d_pose, d_a, d_b);
 }
 
-// one workgroup per image: fixed-order sum of that image's tile partials, then dR -> d(euler)
+// one workgroup per image: fixed-order sum of that image's strip partials, then dR -> d(euler)
 __global__ __launch_bounds__(NT) void k_warp_loss_bwd_finalize(const float* __restrict__ partials, int blocks_per_image,
                                                                const float* __restrict__ pose,
                                                                float* __restrict__ d_pose, float* __restrict__ d_a,
                                                                float* __restrict__ d_b) {
-    __shared__ float s[NPART][NT / NPART + 1];
-    __shared__ float tot[NPART + 2];
+    __shared__ float sh[NT];
+    __shared__ float tot[NPART];
     const int b = blockIdx.x;
-    constexpr int ROWS = NT / NPART;  // 18 partial rows per pass
-    const int k = threadIdx.x % NPART, r = threadIdx.x / NPART;
-    float acc = 0.0f;
-    if (r < ROWS)
-        for (int i = r; i < blocks_per_image; i += ROWS)
-            acc += partials[((size_t)b * blocks_per_image + i) * NPART + k];
-    if (r < ROWS) s[k][r] = acc;
+    const float t = image_sums<NT, NPART, NPART>(partials, b, blocks_per_image, sh);   // 18 partial rows per pass
+    if (threadIdx.x < NPART) tot[threadIdx.x] = t;
     __syncthreads();
-    if (threadIdx.x < NPART) {
-        float t = 0.0f;
-        for (int i = 0; i < ROWS; ++i) t += s[threadIdx.x][i];
-        tot[threadIdx.x] = t;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const float* p = pose + 6 * b;
-        const float sx = sinf(p[3]), cx = cosf(p[3]), sy = sinf(p[4]), cy = cosf(p[4]), sz = sinf(p[5]), cz = cosf(p[5]);
-        const float* dR = tot + 3;  // row-major 3x3
-        // dR/d(rx, ry, rz), entry by entry (R = Rz Ry Rx)
-        const float drx = dR[1] * (cz * sy * cx + sz * sx) + dR[2] * (-cz * sy * sx + sz * cx)
-                        + dR[4] * (sz * sy * cx - cz * sx) + dR[5] * (-sz * sy * sx - cz * cx)
-                        + dR[7] * (cy * cx) + dR[8] * (-cy * sx);
-        const float dry = dR[0] * (-cz * sy) + dR[1] * (cz * cy * sx) + dR[2] * (cz * cy * cx)
-                        + dR[3] * (-sz * sy) + dR[4] * (sz * cy * sx) + dR[5] * (sz * cy * cx)
-                        + dR[6] * (-cy) + dR[7] * (-sy * sx) + dR[8] * (-sy * cx);
-        const float drz = dR[0] * (-sz * cy) + dR[1] * (-sz * sy * sx - cz * cx) + dR[2] * (-sz * sy * cx + cz * sx)
-                        + dR[3] * (cz * cy) + dR[4] * (cz * sy * sx - sz * cx) + dR[5] * (cz * sy * cx + sz * sx);
-        d_pose[6 * b + 0] = tot[0]; d_pose[6 * b + 1] = tot[1]; d_pose[6 * b + 2] = tot[2];
-        d_pose[6 * b + 3] = drx; d_pose[6 * b + 4] = dry; d_pose[6 * b + 5] = drz;
-        d_a[b] = tot[12];
-        d_b[b] = tot[13];
-    }
+    if (threadIdx.x == 0) pose_grad_store(tot, pose, b, d_pose, d_a, d_b);
 }
 
 // --------------------------------------------------------------------------------------------- //
@@ -1187,44 +1157,29 @@ __global__ __launch_bounds__(NT) void k_geo_loss_fwd(const float* __restrict__ d
                                                      const float* __restrict__ pose, const float* __restrict__ K, int H, int W,
                                                      float* __restrict__ partials) {
     __shared__ float s_geo[GEO_N + 4];
-    __shared__ float red[4][2];
     const int b = blockIdx.y;
     if (threadIdx.x == 0) geo_compute(pose, K, nullptr, nullptr, b, s_geo);
     __syncthreads();
     const Geo g = geo_load(s_geo);
     const size_t plane = (size_t)H * W;
     const size_t o = (size_t)blockIdx.x * NT + threadIdx.x;
-    float sd = 0.0f, sm = 0.0f;
+    float sum[2] = {0.0f, 0.0f};          // diff, mask
     if (o < plane) {
         const int v = (int)(o / W), u = (int)(o - (size_t)v * W);
         const GeoPix q = geo_pixel(g, depth_t + (size_t)b * plane, depth_r + (size_t)b * plane, u, v, H, W);
-        sd = q.diff; sm = q.m;
+        sum[0] = q.diff; sum[1] = q.m;
     }
-    sd = wave_sum(sd); sm = wave_sum(sm);
-    if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][0] = sd; red[threadIdx.x >> 6][1] = sm; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const size_t blk = (size_t)b * gridDim.x + blockIdx.x;
-        partials[2 * blk] = (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]);
-        partials[2 * blk + 1] = (red[0][1] + red[1][1]) + (red[2][1] + red[3][1]);
-    }
+    block_partials(sum, partials + 2 * ((size_t)b * gridDim.x + blockIdx.x));
 }
 
 __global__ __launch_bounds__(NT) void k_geo_loss_finalize(const float* __restrict__ partials, int nblk, float* __restrict__ loss_state) {
-    __shared__ float s0[NT], s1[NT];
-    float a = 0.0f, c = 0.0f;
-    for (int i = threadIdx.x; i < nblk; i += NT) { a += partials[2 * i]; c += partials[2 * i + 1]; }
-    s0[threadIdx.x] = a; s1[threadIdx.x] = c;
-    __syncthreads();
-    for (int o = NT / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) { s0[threadIdx.x] += s0[threadIdx.x + o]; s1[threadIdx.x] += s1[threadIdx.x + o]; }
-        __syncthreads();
-    }
+    float a, c;
+    pair_sums(partials, nblk, a, c);
     if (threadIdx.x == 0) {
-        const float denom = fmaxf(s1[0], 1.0f);
-        loss_state[0] = s0[0] / denom;
+        const float denom = fmaxf(c, 1.0f);
+        loss_state[0] = a / denom;
         loss_state[1] = 1.0f / denom;
-        loss_state[2] = s1[0];
+        loss_state[2] = c;
         loss_state[3] = 0.0f;
     }
 }
@@ -1237,7 +1192,6 @@ __global__ __launch_bounds__(NT) void k_geo_loss_bwd(const float* __restrict__ d
                                                      float* __restrict__ d_depth_t, float* __restrict__ d_depth_r,
                                                      float* __restrict__ partials) {
     __shared__ float s_geo[GEO_N + 4];
-    __shared__ float red[4][GEO_NP];
     const int b = blockIdx.y;
     if (threadIdx.x == 0) geo_compute(pose, K, nullptr, nullptr, b, s_geo);
     __syncthreads();
@@ -1278,43 +1232,19 @@ __global__ __launch_bounds__(NT) void k_geo_loss_bwd(const float* __restrict__ d
         part[6] = dPy * cX; part[7] = dPy * cY; part[8] = dPy * cZ;
         part[9] = dPz * cX; part[10] = dPz * cY; part[11] = dPz * cZ;
     }
-#pragma unroll
-    for (int k = 0; k < GEO_NP; ++k) {
-        const float t = wave_sum(part[k]);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = t;
-    }
-    __syncthreads();
-    if (threadIdx.x < GEO_NP) {
-        const size_t blk = (size_t)b * gridDim.x + blockIdx.x;
-        partials[blk * GEO_NP + threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
-    }
+    block_partials(part, partials + ((size_t)b * gridDim.x + blockIdx.x) * GEO_NP);
 }
 
 // one workgroup per image: fixed-order sum of the block partials, then dR -> d(euler)
 __global__ __launch_bounds__(NT) void k_geo_loss_bwd_finalize(const float* __restrict__ partials, int blocks_per_image,
                                                               const float* __restrict__ pose, float* __restrict__ d_pose) {
-    __shared__ float s[GEO_NP][NT / GEO_NP + 1];
+    __shared__ float sh[NT];
     __shared__ float tot[GEO_NP];
     const int b = blockIdx.x;
-    constexpr int ROWS = NT / GEO_NP;   // 21
-    const int k = threadIdx.x % GEO_NP, r = threadIdx.x / GEO_NP;
-    float acc = 0.0f;
-    if (r < ROWS)
-        for (int i = r; i < blocks_per_image; i += ROWS) acc += partials[((size_t)b * blocks_per_image + i) * GEO_NP + k];
-    if (r < ROWS) s[k][r] = acc;
+    const float t = image_sums<NT, GEO_NP, GEO_NP>(partials, b, blocks_per_image, sh);   // 21 partial rows per pass
+    if (threadIdx.x < GEO_NP) tot[threadIdx.x] = t;
     __syncthreads();
-    if (threadIdx.x < GEO_NP) {
-        float t = 0.0f;
-        for (int i = 0; i < ROWS; ++i) t += s[threadIdx.x][i];
-        tot[threadIdx.x] = t;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float drx, dry, drz;
-        dR_to_euler(tot + 3, pose + 6 * b, drx, dry, drz);
-        d_pose[6 * b + 0] = tot[0]; d_pose[6 * b + 1] = tot[1]; d_pose[6 * b + 2] = tot[2];
-        d_pose[6 * b + 3] = drx; d_pose[6 * b + 4] = dry; d_pose[6 * b + 5] = drz;
-    }
+    if (threadIdx.x == 0) pose_grad_store(tot, pose, b, d_pose, nullptr, nullptr);
 }
 
 // --------------------------------------------------------------------------------------------- //
@@ -1328,44 +1258,52 @@ __device__ __forceinline__ float edge_w(const float* __restrict__ img, size_t pl
 }
 __device__ __forceinline__ float sgnf(float x) { return (x > 0.0f) ? 1.0f : ((x < 0.0f) ? -1.0f : 0.0f); }
 
+// Pixel o of one image (dp: its depth, ip: its 3-channel image): the terms of the two neighbour pairs it owns (right: sx,
+// lower: sy) and the gradient of inv_nx Sx + inv_ny Sy w.r.t. its depth, gathered from its up to four incident pairs
+// (deterministic) and multiplied by g.  Unused parts are dropped by the compiler.
+struct SmoothPix { float sx, sy, gd; };
+__device__ __forceinline__ SmoothPix smooth_pixel(const float* __restrict__ dp, const float* __restrict__ ip, int H, int W,
+                                                  size_t o, float inv_nx, float inv_ny, float g) {
+    const size_t plane = (size_t)H * W;
+    const int v = (int)(o / W), u = (int)(o - (size_t)v * W);
+    const float d0 = 1.0f / dp[o];
+    SmoothPix s{0.0f, 0.0f, 0.0f};
+    float gd = 0.0f;                      // d loss / d disp[o]
+    if (u + 1 < W) {
+        const float dd = 1.0f / dp[o + 1] - d0, w = edge_w(ip, plane, o, o + 1);
+        s.sx = fabsf(dd) * w;
+        gd -= sgnf(dd) * w * inv_nx;
+    }
+    if (u >= 1) gd += sgnf(d0 - 1.0f / dp[o - 1]) * edge_w(ip, plane, o - 1, o) * inv_nx;
+    if (v + 1 < H) {
+        const float dd = 1.0f / dp[o + W] - d0, w = edge_w(ip, plane, o, o + W);
+        s.sy = fabsf(dd) * w;
+        gd -= sgnf(dd) * w * inv_ny;
+    }
+    if (v >= 1) gd += sgnf(d0 - 1.0f / dp[o - W]) * edge_w(ip, plane, o - W, o) * inv_ny;
+    s.gd = g * gd * (-d0 * d0);
+    return s;
+}
+
 // forward: every pixel owns its right and its lower neighbour pair; per-block partial {Sx, Sy}
 __global__ __launch_bounds__(NT) void k_smooth_fwd(const float* __restrict__ depth, const float* __restrict__ img, int H, int W,
                                                    float* __restrict__ partials) {
-    __shared__ float red[4][2];
     const int b = blockIdx.y;
     const size_t plane = (size_t)H * W;
     const size_t o = (size_t)blockIdx.x * NT + threadIdx.x;
-    float sx = 0.0f, sy = 0.0f;
+    float sum[2] = {0.0f, 0.0f};          // Sx, Sy
     if (o < plane) {
-        const int v = (int)(o / W), u = (int)(o - (size_t)v * W);
-        const float* dp = depth + (size_t)b * plane;
-        const float* ip = img + (size_t)b * 3 * plane;
-        const float d0 = 1.0f / dp[o];
-        if (u + 1 < W) sx = fabsf(1.0f / dp[o + 1] - d0) * edge_w(ip, plane, o, o + 1);
-        if (v + 1 < H) sy = fabsf(1.0f / dp[o + W] - d0) * edge_w(ip, plane, o, o + W);
+        const SmoothPix q = smooth_pixel(depth + (size_t)b * plane, img + (size_t)b * 3 * plane, H, W, o, 0.0f, 0.0f, 0.0f);
+        sum[0] = q.sx; sum[1] = q.sy;
     }
-    sx = wave_sum(sx); sy = wave_sum(sy);
-    if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][0] = sx; red[threadIdx.x >> 6][1] = sy; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const size_t blk = (size_t)b * gridDim.x + blockIdx.x;
-        partials[2 * blk] = (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]);
-        partials[2 * blk + 1] = (red[0][1] + red[1][1]) + (red[2][1] + red[3][1]);
-    }
+    block_partials(sum, partials + 2 * ((size_t)b * gridDim.x + blockIdx.x));
 }
 
 __global__ __launch_bounds__(NT) void k_smooth_finalize(const float* __restrict__ partials, int nblk, float inv_nx, float inv_ny,
                                                         float* __restrict__ loss) {
-    __shared__ float s0[NT], s1[NT];
-    float a = 0.0f, c = 0.0f;
-    for (int i = threadIdx.x; i < nblk; i += NT) { a += partials[2 * i]; c += partials[2 * i + 1]; }
-    s0[threadIdx.x] = a; s1[threadIdx.x] = c;
-    __syncthreads();
-    for (int o = NT / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) { s0[threadIdx.x] += s0[threadIdx.x + o]; s1[threadIdx.x] += s1[threadIdx.x + o]; }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) loss[0] = s0[0] * inv_nx + s1[0] * inv_ny;
+    float a, c;
+    pair_sums(partials, nblk, a, c);
+    if (threadIdx.x == 0) loss[0] = a * inv_nx + c * inv_ny;
 }
 
 // backward, gather form (deterministic): a pixel collects from its up to four incident pairs
@@ -1376,26 +1314,22 @@ __global__ __launch_bounds__(NT) void k_smooth_bwd(const float* __restrict__ dep
     const size_t plane = (size_t)H * W;
     const size_t o = (size_t)blockIdx.x * NT + threadIdx.x;
     if (o >= plane) return;
-    const int v = (int)(o / W), u = (int)(o - (size_t)v * W);
-    const float* dp = depth + (size_t)b * plane;
-    const float* ip = img + (size_t)b * 3 * plane;
-    const float dep = dp[o];
-    const float d0 = 1.0f / dep;
-    float gd = 0.0f;                      // d loss / d disp[o]
-    if (u + 1 < W) gd -= sgnf(1.0f / dp[o + 1] - d0) * edge_w(ip, plane, o, o + 1) * inv_nx;
-    if (u >= 1) gd += sgnf(d0 - 1.0f / dp[o - 1]) * edge_w(ip, plane, o - 1, o) * inv_nx;
-    if (v + 1 < H) gd -= sgnf(1.0f / dp[o + W] - d0) * edge_w(ip, plane, o, o + W) * inv_ny;
-    if (v >= 1) gd += sgnf(d0 - 1.0f / dp[o - W]) * edge_w(ip, plane, o - W, o) * inv_ny;
-    d_depth[(size_t)b * plane + o] = grad_loss[0] * gd * (-d0 * d0);
+    d_depth[(size_t)b * plane + o] =
+        smooth_pixel(depth + (size_t)b * plane, img + (size_t)b * 3 * plane, H, W, o, inv_nx, inv_ny, grad_loss[0]).gd;
+}
+
+// the 2x2 average of four values (top pair first), and of the cell whose top-left source pixel is xp (source row stride ws)
+__device__ __forceinline__ float avg4(float a, float b, float c, float d) { return 0.25f * ((a + b) + (c + d)); }
+__device__ __forceinline__ float avg2x2(const float* __restrict__ xp, size_t ws) {
+    const float2 r0 = *reinterpret_cast<const float2*>(xp), r1 = *reinterpret_cast<const float2*>(xp + ws);
+    return avg4(r0.x, r0.y, r1.x, r1.y);
 }
 
 __global__ __launch_bounds__(NT) void k_avgpool2_fwd(const float* __restrict__ x, int Ho, int Wo, float* __restrict__ y) {
     const size_t o = (size_t)blockIdx.x * NT + threadIdx.x;
     if (o >= (size_t)Ho * Wo) return;
     const int v = (int)(o / Wo), u = (int)(o - (size_t)v * Wo);
-    const float* xp = x + (size_t)blockIdx.y * 4 * Ho * Wo + (size_t)(2 * v) * (2 * Wo) + 2 * u;
-    const float2 r0 = *reinterpret_cast<const float2*>(xp), r1 = *reinterpret_cast<const float2*>(xp + 2 * Wo);
-    y[(size_t)blockIdx.y * Ho * Wo + o] = 0.25f * ((r0.x + r0.y) + (r1.x + r1.y));
+    y[(size_t)blockIdx.y * Ho * Wo + o] = avg2x2(x + (size_t)blockIdx.y * 4 * Ho * Wo + (size_t)(2 * v) * (2 * Wo) + 2 * u, 2 * Wo);
 }
 
 __global__ __launch_bounds__(NT) void k_avgpool2_bwd(const float* __restrict__ dy, int Ho, int Wo, float* __restrict__ dx) {
@@ -1426,9 +1360,7 @@ __global__ __launch_bounds__(NT) void k_pyramid_level(const float* __restrict__ 
     const float* x; float* y;
     if (p < 3 * B) { x = st; y = dt; } else if (p < 6 * B) { x = sr; y = dr; p -= 3 * B; } else { x = sd; y = dd; p -= 6 * B; }
     const int v = (int)(o / Wo), u = (int)(o - (size_t)v * Wo);
-    const float* xp = x + (size_t)p * 4 * Ho * Wo + (size_t)(2 * v) * (2 * Wo) + 2 * u;
-    const float2 r0 = *reinterpret_cast<const float2*>(xp), r1 = *reinterpret_cast<const float2*>(xp + 2 * Wo);
-    y[(size_t)p * Ho * Wo + o] = 0.25f * ((r0.x + r0.y) + (r1.x + r1.y));
+    y[(size_t)p * Ho * Wo + o] = avg2x2(x + (size_t)p * 4 * Ho * Wo + (size_t)(2 * v) * (2 * Wo) + 2 * u, 2 * Wo);
 }
 
 // 2x2-average pyramid cell of one plane: NL levels below the source in one go (NL = 2: a 4x4 block -> four level-1 pixels and
@@ -1437,19 +1369,17 @@ template <int NL>
 __device__ __forceinline__ void pyramid_cell(const float* __restrict__ src, int Hs, int Ws, int cy, int cx,
                                              float* __restrict__ d1, float* __restrict__ d2) {
     if constexpr (NL == 1) {
-        const float* xp = src + (size_t)(2 * cy) * Ws + 2 * cx;
-        const float2 r0 = *reinterpret_cast<const float2*>(xp), r1 = *reinterpret_cast<const float2*>(xp + Ws);
-        d1[(size_t)cy * (Ws >> 1) + cx] = 0.25f * ((r0.x + r0.y) + (r1.x + r1.y));
+        d1[(size_t)cy * (Ws >> 1) + cx] = avg2x2(src + (size_t)(2 * cy) * Ws + 2 * cx, Ws);
     } else {
         const float* xp = src + (size_t)(4 * cy) * Ws + 4 * cx;
         const float4 r0 = *reinterpret_cast<const float4*>(xp), r1 = *reinterpret_cast<const float4*>(xp + Ws);
         const float4 r2 = *reinterpret_cast<const float4*>(xp + 2 * (size_t)Ws), r3 = *reinterpret_cast<const float4*>(xp + 3 * (size_t)Ws);
-        const float a00 = 0.25f * ((r0.x + r0.y) + (r1.x + r1.y)), a01 = 0.25f * ((r0.z + r0.w) + (r1.z + r1.w));
-        const float a10 = 0.25f * ((r2.x + r2.y) + (r3.x + r3.y)), a11 = 0.25f * ((r2.z + r2.w) + (r3.z + r3.w));
+        const float a00 = avg4(r0.x, r0.y, r1.x, r1.y), a01 = avg4(r0.z, r0.w, r1.z, r1.w);
+        const float a10 = avg4(r2.x, r2.y, r3.x, r3.y), a11 = avg4(r2.z, r2.w, r3.z, r3.w);
         const int W1 = Ws >> 1;
         *reinterpret_cast<float2*>(d1 + (size_t)(2 * cy) * W1 + 2 * cx) = make_float2(a00, a01);
         *reinterpret_cast<float2*>(d1 + (size_t)(2 * cy + 1) * W1 + 2 * cx) = make_float2(a10, a11);
-        d2[(size_t)cy * (Ws >> 2) + cx] = 0.25f * ((a00 + a01) + (a10 + a11));
+        d2[(size_t)cy * (Ws >> 2) + cx] = avg4(a00, a01, a10, a11);
     }
 }
 
@@ -1486,40 +1416,18 @@ __global__ __launch_bounds__(NT) void k_full_prepare(PrepArgs a) {
         }
         return;
     }
-    __shared__ float red[4][2];
     const size_t plane = (size_t)H * W;
     const int nb = a.sm_blocks / B;
     const int b = blockIdx.x / nb;
     const size_t o = (size_t)(blockIdx.x - b * nb) * NT + threadIdx.x;
-    float sx = 0.0f, sy = 0.0f;
+    float sum[2] = {0.0f, 0.0f};          // Sx, Sy
     if (o < plane) {
-        const int v = (int)(o / W), u = (int)(o - (size_t)v * W);
-        const float* dp = a.depth + (size_t)b * plane;
-        const float* ip = a.tgt + (size_t)b * 3 * plane;
-        const float d0 = 1.0f / dp[o];
-        float gd = 0.0f;
-        if (u + 1 < W) {
-            const float dd = 1.0f / dp[o + 1] - d0, w = edge_w(ip, plane, o, o + 1);
-            sx = fabsf(dd) * w;
-            gd -= sgnf(dd) * w * a.inv_nx;
-        }
-        if (u >= 1) gd += sgnf(d0 - 1.0f / dp[o - 1]) * edge_w(ip, plane, o - 1, o) * a.inv_nx;
-        if (v + 1 < H) {
-            const float dd = 1.0f / dp[o + W] - d0, w = edge_w(ip, plane, o, o + W);
-            sy = fabsf(dd) * w;
-            gd -= sgnf(dd) * w * a.inv_ny;
-        }
-        if (v >= 1) gd += sgnf(d0 - 1.0f / dp[o - W]) * edge_w(ip, plane, o - W, o) * a.inv_ny;
-        a.sd_raw[(size_t)b * plane + o] = gd * (-d0 * d0);
+        const SmoothPix q = smooth_pixel(a.depth + (size_t)b * plane, a.tgt + (size_t)b * 3 * plane, H, W, o, a.inv_nx, a.inv_ny, 1.0f);
+        sum[0] = q.sx; sum[1] = q.sy;
+        a.sd_raw[(size_t)b * plane + o] = q.gd;
         if (a.zero_acc) a.zero_acc[(size_t)b * plane + o] = 0ull;
     }
-    sx = wave_sum(sx); sy = wave_sum(sy);
-    if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][0] = sx; red[threadIdx.x >> 6][1] = sy; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        a.sm_partials[2 * (size_t)blockIdx.x] = (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]);
-        a.sm_partials[2 * (size_t)blockIdx.x + 1] = (red[0][1] + red[1][1]) + (red[2][1] + red[3][1]);
-    }
+    block_partials(sum, a.sm_partials + 2 * (size_t)blockIdx.x);
 }
 
 struct FullLevels {
@@ -1578,7 +1486,7 @@ __global__ __launch_bounds__(FT) void k_full_finalize(FullLevels lv, const float
         return;
     }
     const int s = blockIdx.x / B, b = blockIdx.x - s * B;
-    const float t = image_sums(lv.partials[s], b, lv.items_per_image[s], sh);
+    const float t = image_sums<FT, NPART, NPART_F>(lv.partials[s], b, lv.items_per_image[s], sh);
     if (tid < NPART) gpart[((size_t)s * B + b) * NPART + tid] = t;
 }
 
@@ -1618,7 +1526,7 @@ __global__ __launch_bounds__(NT) void k_full_combine(FullLevels lv, const float*
         return;
     }
     if ((int)blockIdx.x >= B) return;
-    __shared__ float tot[NPART + 2];
+    __shared__ float tot[NPART];
     const int b = blockIdx.x;
     if (threadIdx.x < NPART) {
         float t = 0.0f;
@@ -1628,20 +1536,35 @@ __global__ __launch_bounds__(NT) void k_full_combine(FullLevels lv, const float*
         tot[threadIdx.x] = t;
     }
     __syncthreads();
-    if (threadIdx.x == 0) {
-        float drx, dry, drz;
-        dR_to_euler(tot + 3, pose + 6 * b, drx, dry, drz);
-        d_pose[6 * b + 0] = tot[0]; d_pose[6 * b + 1] = tot[1]; d_pose[6 * b + 2] = tot[2];
-        d_pose[6 * b + 3] = drx; d_pose[6 * b + 4] = dry; d_pose[6 * b + 5] = drz;
-        d_a[b] = tot[12];
-        d_b[b] = tot[13];
-    }
+    if (threadIdx.x == 0) pose_grad_store(tot, pose, b, d_pose, d_a, d_b);
+}
+
+// The geometry of one march launch, decided on the host without any HIP call: one wave per (image, row segment, strip),
+// strip fastest, 4 waves per workgroup.  one_pass: the one-pass / backward march (BCOLS-column strips, 4 halo rows, 2 waves per
+// SIMD); otherwise the forward-only march (MCOLS-column strips).  The TUNE knobs override the row count.
+struct MarchPlan {
+    int seg_rows, strips_x, nseg;
+    long long nitems, grid;      // strip segments (one wave each), workgroups
+};
+
+inline MarchPlan march_plan(int B, int H, int W, bool one_pass) {
+    MarchPlan m;
+    const int cols = one_pass ? BCOLS : MCOLS;
+    m.seg_rows = one_pass ? pick_march_rows(B, H, W, BCOLS, 4, 8) : pick_march_rows(B, H, W);
+    const long knob = one_pass ? TUNE(march_rows_bwd) : TUNE(march_rows_fwd);
+    if (knob > 0) m.seg_rows = std::max(MROWS_MIN, std::min(MROWS_MAX, (int)knob));
+    m.strips_x = (W + cols - 1) / cols;
+    m.nseg = (H + m.seg_rows - 1) / m.seg_rows;
+    m.nitems = (long long)B * m.nseg * m.strips_x;
+    m.grid = (m.nitems + 3) / 4;
+    return m;
 }
 
 // where everything lives in the caller's workspace (fp32 units; the 64-bit accumulators come first)
 struct FullPlan {
     int S;
-    int h[FULL_MAX_LEVELS], w[FULL_MAX_LEVELS], seg_rows[FULL_MAX_LEVELS], strips[FULL_MAX_LEVELS], nseg[FULL_MAX_LEVELS];
+    int h[FULL_MAX_LEVELS], w[FULL_MAX_LEVELS];
+    MarchPlan march[FULL_MAX_LEVELS];
     size_t tgt[FULL_MAX_LEVELS], ref[FULL_MAX_LEVELS], dep[FULL_MAX_LEVELS], raw[FULL_MAX_LEVELS], part[FULL_MAX_LEVELS];
     size_t acc, geo_part, geo_raw, sd, sm_part, gpart, state, total;
     int sm_nblk;
@@ -1656,17 +1579,13 @@ inline FullPlan full_plan(int B, int H, int W, int S) {
     for (int s = 0; s < S; ++s) {
         const int h = H >> s, w = W >> s;
         p.h[s] = h; p.w[s] = w;
-        int rows = pick_march_rows(B, h, w, BCOLS, 4, 8);
-        if (TUNE(march_rows_bwd) > 0) rows = std::max(4, std::min(MROWS_MAX, (int)TUNE(march_rows_bwd)));
-        p.seg_rows[s] = rows;
-        p.strips[s] = (w + BCOLS - 1) / BCOLS;
-        p.nseg[s] = (h + rows - 1) / rows;
+        p.march[s] = march_plan(B, h, w, true);
         const size_t px = (size_t)B * h * w;
         if (s > 0) { p.tgt[s] = take(3 * px); p.ref[s] = take(3 * px); p.dep[s] = take(px); }
         p.raw[s] = take(px);
-        p.part[s] = take((size_t)B * p.nseg[s] * p.strips[s] * NPART_F);
+        p.part[s] = take((size_t)p.march[s].nitems * NPART_F);
     }
-    p.geo_part = take((size_t)B * p.nseg[0] * p.strips[0]);
+    p.geo_part = take((size_t)p.march[0].nitems);
     p.geo_raw = take((size_t)B * H * W);
     p.sd = take((size_t)B * H * W);
     p.sm_nblk = B * (int)(((size_t)H * W + NT - 1) / NT);
@@ -1677,11 +1596,32 @@ inline FullPlan full_plan(int B, int H, int W, int S) {
     return p;
 }
 
+// the per-level views of the workspace that k_full_finalize and k_full_combine read
+inline FullLevels full_levels(const FullPlan& p, int B, const float* workspace) {
+    FullLevels lv{};
+    lv.S = p.S; lv.B = B;
+    for (int l = 0; l < p.S; ++l) {
+        lv.items_per_image[l] = p.march[l].nseg * p.march[l].strips_x;
+        lv.partials[l] = workspace + p.part[l];
+        lv.raw[l] = workspace + p.raw[l];
+    }
+    return lv;
+}
+
 inline bool full_shape_ok(int B, int H, int W, int S) {
     return B >= 1 && B <= 9000 && S >= 1 && S <= FULL_MAX_LEVELS && (H >> (S - 1)) >= 2 && (W >> (S - 1)) >= 2
            && H % (1 << (S - 1)) == 0 && W % (1 << (S - 1)) == 0 && (size_t)H * W < (1u << 28);
 }
 
+// the checks every photometric entry point shares (who: its name): the seven inputs and `outputs` (its other pointers) non-null,
+// 1 <= B <= max_b, H, W >= 2, H W < 2^30
+inline int photometric_args(const char* who, const float* tgt, const float* ref, const float* depth, const float* pose,
+                            const float* K, const float* lcc_a, const float* lcc_b, bool outputs, int B, int H, int W, int max_b) {
+    COLVO_CHECK_ARG(tgt && ref && depth && pose && K && lcc_a && lcc_b && outputs, "%s: null pointer argument", who);
+    COLVO_CHECK_ARG(B >= 1 && H >= 2 && W >= 2 && B <= max_b, "%s: bad shape B=%d H=%d W=%d", who, B, H, W);
+    COLVO_CHECK_ARG((size_t)H * W < (1u << 30), "%s: image too large", who);
+    return 0;
+}
 
 }  // namespace
 }  // namespace colvo
@@ -1690,30 +1630,26 @@ using namespace colvo;
 
 extern "C" size_t colvo_warp_loss_workspace_floats(int B, int H, int W) {
     if (B <= 0 || H <= 0 || W <= 0) return 0;
-    const size_t bwd = (size_t)B * ((W + BCOLS - 1) / BCOLS) * ((H + 3) / 4) * NPART_F; // <= 16 per strip segment (>= 4 rows)
-    const size_t fwd = (size_t)B * ((W + MCOLS - 1) / MCOLS) * ((H + 3) / 4) * 2;   // 2 per strip segment (>= 4 rows each)
+    // an upper bound of every march_plan's partials: no segment is shorter than MROWS_MIN rows
+    const size_t nseg = (H + MROWS_MIN - 1) / MROWS_MIN;
+    const size_t bwd = (size_t)B * ((W + BCOLS - 1) / BCOLS) * nseg * NPART_F;   // <= 16 per strip segment
+    const size_t fwd = (size_t)B * ((W + MCOLS - 1) / MCOLS) * nseg * 2;         // forward: loss sum and count per strip segment
     return bwd > fwd ? bwd : fwd;
 }
 
 extern "C" int colvo_warp_loss_fwd(const float* tgt, const float* ref, const float* depth, const float* pose,
                                    const float* K, const float* lcc_a, const float* lcc_b, int B, int H, int W,
                                    float ssim_weight, float* workspace, float* loss_state, colvo_stream_t stream) {
-    COLVO_CHECK_ARG(tgt && ref && depth && pose && K && lcc_a && lcc_b && workspace && loss_state,
-                    "colvo_warp_loss_fwd: null pointer argument");
-    COLVO_CHECK_ARG(B >= 1 && H >= 2 && W >= 2 && B <= 65535, "colvo_warp_loss_fwd: bad shape B=%d H=%d W=%d", B, H, W);
-    COLVO_CHECK_ARG((size_t)H * W < (1u << 30), "colvo_warp_loss_fwd: image too large");
+    if (int e = photometric_args("colvo_warp_loss_fwd", tgt, ref, depth, pose, K, lcc_a, lcc_b, workspace && loss_state, B, H, W, 65535))
+        return e;
     hipStream_t s = (hipStream_t)stream;
-    // marching-wave forward: one wave per (image, 32-row segment, 62-column strip)
-    int seg_rows = pick_march_rows(B, H, W);
-    if (TUNE(march_rows_fwd) > 0) seg_rows = std::max(4, std::min(MROWS_MAX, (int)TUNE(march_rows_fwd)));   // tuning knob
-    const int strips_x = (W + MCOLS - 1) / MCOLS, nseg = (H + seg_rows - 1) / seg_rows;
-    const long long nitems = (long long)B * nseg * strips_x;
-    COLVO_CHECK_ARG(nitems < (1ll << 30), "colvo_warp_loss_fwd: too many strips");
-    const int nblk = (int)nitems;
-    colvo::launch(k_warp_loss_fwd_march, dim3((unsigned)((nitems + 3) / 4)), dim3(NT), 0, s, tgt, ref, depth, pose, K,
-                       lcc_a, lcc_b, B, H, W, strips_x, nseg, seg_rows, ssim_weight, workspace);
+    // marching-wave forward: one wave per (image, row segment, 62-column strip)
+    const MarchPlan m = march_plan(B, H, W, false);
+    COLVO_CHECK_ARG(m.nitems < (1ll << 30), "colvo_warp_loss_fwd: too many strips");
+    colvo::launch(k_warp_loss_fwd_march, dim3((unsigned)m.grid), dim3(NT), 0, s, tgt, ref, depth, pose, K,
+                       lcc_a, lcc_b, B, H, W, m.strips_x, m.nseg, m.seg_rows, ssim_weight, workspace);
     COLVO_CHECK_LAUNCH("k_warp_loss_fwd_march");
-    colvo::launch(k_warp_loss_fwd_finalize, dim3(1), dim3(NT), 0, s, workspace, nblk, loss_state);
+    colvo::launch(k_warp_loss_fwd_finalize, dim3(1), dim3(NT), 0, s, workspace, (int)m.nitems, loss_state);
     COLVO_CHECK_LAUNCH("k_warp_loss_fwd_finalize");
     return 0;
 }
@@ -1723,22 +1659,18 @@ extern "C" int colvo_warp_loss_bwd(const float* tgt, const float* ref, const flo
                                    float ssim_weight, const float* loss_state, const float* grad_loss,
                                    float* workspace, float* d_depth, float* d_pose, float* d_a, float* d_b,
                                    colvo_stream_t stream) {
-    COLVO_CHECK_ARG(tgt && ref && depth && pose && K && lcc_a && lcc_b && workspace && loss_state && grad_loss
-                        && d_depth && d_pose && d_a && d_b,
-                    "colvo_warp_loss_bwd: null pointer argument");
-    COLVO_CHECK_ARG(B >= 1 && H >= 2 && W >= 2 && B <= 65535, "colvo_warp_loss_bwd: bad shape B=%d H=%d W=%d", B, H, W);
-    COLVO_CHECK_ARG((size_t)H * W < (1u << 30), "colvo_warp_loss_bwd: image too large");
+    if (int e = photometric_args("colvo_warp_loss_bwd", tgt, ref, depth, pose, K, lcc_a, lcc_b,
+                                 workspace && loss_state && grad_loss && d_depth && d_pose && d_a && d_b, B, H, W, 65535))
+        return e;
     hipStream_t s = (hipStream_t)stream;
     // marching-wave backward: one wave per (image, row segment, 60-column strip)
-    int seg_rows = pick_march_rows(B, H, W, BCOLS, 4, 8);
-    if (TUNE(march_rows_bwd) > 0) seg_rows = std::max(4, std::min(MROWS_MAX, (int)TUNE(march_rows_bwd)));   // tuning knob
-    const int strips_x = (W + BCOLS - 1) / BCOLS, nseg = (H + seg_rows - 1) / seg_rows;
-    const long long nitems = (long long)B * nseg * strips_x;
-    COLVO_CHECK_ARG(nitems < (1ll << 30), "colvo_warp_loss_bwd: too many strips");
-    colvo::launch((k_warp_loss_bwd_march<false>), dim3((unsigned)((nitems + 3) / 4)), dim3(NT), 0, s, tgt, ref, depth, pose, K,
-                       lcc_a, lcc_b, B, H, W, strips_x, nseg, seg_rows, ssim_weight, loss_state, grad_loss, d_depth, workspace, 0, GeoArgs{});
+    const MarchPlan m = march_plan(B, H, W, true);
+    COLVO_CHECK_ARG(m.nitems < (1ll << 30), "colvo_warp_loss_bwd: too many strips");
+    colvo::launch((k_warp_loss_bwd_march<false>), dim3((unsigned)m.grid), dim3(NT), 0, s, tgt, ref, depth, pose, K,
+                       lcc_a, lcc_b, B, H, W, m.strips_x, m.nseg, m.seg_rows, ssim_weight, loss_state, grad_loss, d_depth, workspace, 0,
+                       GeoArgs{});
     COLVO_CHECK_LAUNCH("k_warp_loss_bwd_march");
-    colvo::launch(k_warp_loss_bwd_finalize, dim3(B), dim3(NT), 0, s, workspace, nseg * strips_x, pose,
+    colvo::launch(k_warp_loss_bwd_finalize, dim3(B), dim3(NT), 0, s, workspace, m.nseg * m.strips_x, pose,
                        d_pose, d_a, d_b);
     COLVO_CHECK_LAUNCH("k_warp_loss_bwd_finalize");
     return 0;
@@ -1750,21 +1682,17 @@ extern "C" int colvo_warp_loss_fused(const float* tgt, const float* ref, const f
                                      const float* K, const float* lcc_a, const float* lcc_b, int B, int H, int W,
                                      float ssim_weight, float* workspace, float* loss_state, float* d_depth_raw,
                                      float* grad_partials, float* grad_unit, colvo_stream_t stream) {
-    COLVO_CHECK_ARG(tgt && ref && depth && pose && K && lcc_a && lcc_b && workspace && loss_state && d_depth_raw && grad_partials,
-                    "colvo_warp_loss_fused: null pointer argument");
-    COLVO_CHECK_ARG(B >= 1 && H >= 2 && W >= 2 && B <= 65534, "colvo_warp_loss_fused: bad shape B=%d H=%d W=%d", B, H, W);
-    COLVO_CHECK_ARG((size_t)H * W < (1u << 30), "colvo_warp_loss_fused: image too large");
+    if (int e = photometric_args("colvo_warp_loss_fused", tgt, ref, depth, pose, K, lcc_a, lcc_b,
+                                 workspace && loss_state && d_depth_raw && grad_partials, B, H, W, 65534))
+        return e;
     hipStream_t s = (hipStream_t)stream;
-    int seg_rows = pick_march_rows(B, H, W, BCOLS, 4, 8);
-    if (TUNE(march_rows_bwd) > 0) seg_rows = std::max(4, std::min(MROWS_MAX, (int)TUNE(march_rows_bwd)));   // tuning knob
-    const int strips_x = (W + BCOLS - 1) / BCOLS, nseg = (H + seg_rows - 1) / seg_rows;
-    const long long nitems = (long long)B * nseg * strips_x;
-    COLVO_CHECK_ARG(nitems < (1ll << 30), "colvo_warp_loss_fused: too many strips");
-    colvo::launch((k_warp_loss_bwd_march<true>), dim3((unsigned)((nitems + 3) / 4)), dim3(NT), 0, s, tgt, ref, depth, pose,
-                       K, lcc_a, lcc_b, B, H, W, strips_x, nseg, seg_rows, ssim_weight, (const float*)nullptr,
+    const MarchPlan m = march_plan(B, H, W, true);
+    COLVO_CHECK_ARG(m.nitems < (1ll << 30), "colvo_warp_loss_fused: too many strips");
+    colvo::launch((k_warp_loss_bwd_march<true>), dim3((unsigned)m.grid), dim3(NT), 0, s, tgt, ref, depth, pose,
+                       K, lcc_a, lcc_b, B, H, W, m.strips_x, m.nseg, m.seg_rows, ssim_weight, (const float*)nullptr,
                        (const float*)nullptr, d_depth_raw, workspace, 0, GeoArgs{});
     COLVO_CHECK_LAUNCH("k_warp_loss_bwd_march<fused>");
-    colvo::launch(k_warp_loss_fused_finalize, dim3(B + 1), dim3(FT), 0, s, workspace, nseg * strips_x, B, pose,
+    colvo::launch(k_warp_loss_fused_finalize, dim3(B + 1), dim3(FT), 0, s, workspace, m.nseg * m.strips_x, B, pose,
                        grad_partials, grad_unit, loss_state);
     COLVO_CHECK_LAUNCH("k_warp_loss_fused_finalize");
     return 0;
@@ -1974,22 +1902,18 @@ extern "C" int colvo_full_objective_fwd(const float* tgt, const float* ref, cons
         }
     }
     // (2) one launch: the one-pass photometric loss + gradients of every level; level 0 carries the geometric term
-    FullLevels lv{};
-    lv.S = num_scales; lv.B = B;
+    const FullLevels lv = full_levels(p, B, workspace);
     MarchLevels ml{};
     ml.S = num_scales;
     unsigned grid = 0;
     for (int l = 0; l < num_scales; ++l) {
-        const long long nitems = (long long)B * p.nseg[l] * p.strips[l];
-        COLVO_CHECK_ARG(nitems < (1ll << 28), "colvo_full_objective_fwd: too many strips");
-        lv.items_per_image[l] = p.nseg[l] * p.strips[l];
-        lv.partials[l] = workspace + p.part[l];
-        lv.raw[l] = workspace + p.raw[l];
+        const MarchPlan& m = p.march[l];
+        COLVO_CHECK_ARG(m.nitems < (1ll << 28), "colvo_full_objective_fwd: too many strips");
         MarchLevel& L = ml.lv[l];
         L.tgt = l ? workspace + p.tgt[l] : tgt; L.ref = l ? workspace + p.ref[l] : ref; L.depth = l ? workspace + p.dep[l] : depth_t;
         L.d_depth = workspace + p.raw[l]; L.partials = workspace + p.part[l];
-        L.H = p.h[l]; L.W = p.w[l]; L.strips_x = p.strips[l]; L.nseg = p.nseg[l]; L.seg_rows = p.seg_rows[l];
-        L.wg8 = (int)(((nitems + 3) / 4 + 7) / 8);
+        L.H = p.h[l]; L.W = p.w[l]; L.strips_x = m.strips_x; L.nseg = m.nseg; L.seg_rows = m.seg_rows;
+        L.wg8 = (int)((m.grid + 7) / 8);
         grid += 8u * (unsigned)L.wg8;
     }
     if (geo) {
@@ -2024,13 +1948,7 @@ extern "C" int colvo_full_objective_bwd(const float* workspace, const float* gra
     COLVO_CHECK_ARG(geo_weight == 0.0f || d_depth_r, "colvo_full_objective_bwd: the geometric term needs d_depth_r");
     COLVO_CHECK_ARG(full_shape_ok(B, H, W, num_scales), "colvo_full_objective_bwd: bad shape");
     const FullPlan p = full_plan(B, H, W, num_scales);
-    FullLevels lv{};
-    lv.S = num_scales; lv.B = B;
-    for (int l = 0; l < num_scales; ++l) {
-        lv.items_per_image[l] = p.nseg[l] * p.strips[l];
-        lv.partials[l] = workspace + p.part[l];
-        lv.raw[l] = workspace + p.raw[l];
-    }
+    const FullLevels lv = full_levels(p, B, workspace);
     const bool geo = geo_weight != 0.0f, smooth = smooth_weight != 0.0f;
     unsigned nbx = (unsigned)(((size_t)H * W + NT - 1) / NT);
     if (nbx < (unsigned)B) nbx = (unsigned)B;
