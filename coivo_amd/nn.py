@@ -826,8 +826,10 @@ class DepthNet(_ArenaModule):
             # 3.732 at the configs[3] shape; developer switch COLVO_BWD16_HEADW=1)
             fuse_headw = fuse_head and _lib.dev_env("COLVO_BWD16_HEADW") is not None
             if not fuse_headw:
-                if self.compute_dtype == torch.bfloat16 and _lib.dev_env("COLVO_NO_HEAD_WGRAD_MFMA") is None:
-                    # the head's weight gradient by MFMA (partial rows + table reduction: reproducible in every mode)
+                if (self.compute_dtype == torch.bfloat16 and ops.depth_head_wgrad_mfma_ok(B, H, W) and
+                        _lib.dev_env("COLVO_NO_HEAD_WGRAD_MFMA") is None):
+                    # the head's weight gradient by MFMA (partial rows + table reduction: reproducible in every mode); from 2^25
+                    # pixels on the table form of the VALU kernel below, reproducible as well
                     self._run_wgrad(self.head, lambda: ops.depth_head_wgrad_mfma(x1, scratch, self.head.g_master, self.head.g_bias),
                                     x1, scratch)
                 else:

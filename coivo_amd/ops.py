@@ -111,6 +111,11 @@ def conv_bwd_fused_head_rows(d: ConvDesc) -> int:
     return int(_lib.load().colvo_conv_bwd_fused_head_rows(C.byref(d)))
 
 
+def depth_head_wgrad_mfma_ok(B: int, H: int, W: int) -> bool:
+    """Whether colvo_depth_head_wgrad_mfma takes B images of H x W (its y and d(pre) offsets are 32-bit: below 2^25 pixels)."""
+    return _lib.load().colvo_depth_head_wgrad_mfma_rows(B, H, W) > 0
+
+
 def depth_head_wgrad_mfma(y, dpre, dw, db) -> None:
     """The 16-channel bf16 depth head's weight / bias gradient by MFMA: partial rows + the table reduction (two launches on the current
     stream; include/colvo.h colvo_depth_head_wgrad_mfma)."""
