@@ -105,7 +105,17 @@ namespace tune {
     X(march_rows_fwd, 0, "rows per strip segment of the fused-loss forward march (0: chosen to fill the wave slots in whole rounds)") \
     X(march_rows_bwd, 0, "... of the one-pass loss + gradient march")                                                               \
     X(fork_stop_event, 1, "a FORK waits on the producing kernel's own completion (hipExtLaunchKernel stopEvent) instead of a recorded marker") \
-    X(side_streams, 2, "weight-gradient streams colvo_run_commands alternates between (the caller's + library-owned ones)")
+    X(side_streams, 2, "weight-gradient streams colvo_run_commands alternates between (the caller's + library-owned ones)")                 \
+    /* ---- voxel fusion (fuse.hip) ---- */                                                                                          \
+    X(fuse_agg_rounds, 64, "lanes of a wave that hit the same voxel add once, through the first of them; up to this many distinct voxels "  \
+                           "per wave are matched (64: all), lanes left over issue their own sample; 0: no matching.  512 frames of 256x320, "  \
+                           "2 cm voxels (1.47 samples per distinct voxel of a wave), accumulate pass: 0 -> 1654 us, 8 -> 1517, 16 -> 1387, "    \
+                           "32 -> 1241, 48 -> 1242, 64 -> 1244 (tools/bench_fuse.py)")                                                        \
+    X(fuse_row_adds, 1, "a record's four 64-bit words are added by four adjacent lanes of one instruction (16 records, 32 contiguous "   \
+                        "bytes each), compacted through LDS; 0: every issuing lane adds its record's words in four instructions "            \
+                        "(same shape: 5784 us against 1517 at 8 rounds, 4084 against 1244 at 64: the memory side works in requests)")       \
+    X(fuse_count_limit, 16777216, "a voxel with this many samples raises the overflow flag (2^24: 255 * 2^24 < 2^32, the 32-bit sums "  \
+                                  "cannot have wrapped below it; the tests lower it)")
 
 struct Table {
 #define X(name, dflt, doc) double name = dflt;

@@ -1,14 +1,17 @@
-"""Inference side of the path: depth maps + relative poses -> trajectory -> stitched point cloud.
+"""Inference side of the path: depth maps + relative poses -> trajectory -> stitched point cloud, and
+the coloured, voxel-averaged cloud fused from it.
 
 Reference: README.md:9 ("complete 3D reconstruction of the intestine"), README.md:29 ("stitching together the dense depth
 maps of each frame using the colonoscopic trajectory").  Spec: oracle/colvo_spec.py integrate_trajectory / backproject /
 stitch_point_cloud (oracle/SPEC.md §6c).  The per-pixel work runs in csrc/reconstruct.hip; the trajectory integration is N
-products of 4x4 matrices and is done on the host in float64 (it is control flow, not a kernel).
+products of 4x4 matrices and is done on the host in float64 (it is control flow, not a kernel).  The fusion runs in
+csrc/fuse.hip.
 """
 from __future__ import annotations
 
 import math
-from typing import NamedTuple, Optional
+import struct
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 
@@ -95,11 +98,157 @@ def stitch_point_cloud(depths: torch.Tensor, K: torch.Tensor, cam2world: torch.T
     return points[: int(count.item())]
 
 
+class FusedCloud(NamedTuple):
+    points: torch.Tensor            # [M,3] float32: mean position of the samples of each voxel
+    colors: Optional[torch.Tensor]  # [M,3] float32 in [0,1]: their mean colour (None without colours)
+    counts: torch.Tensor            # [M]   int32: how many samples
+    voxels: torch.Tensor            # [M,3] int32: (ix, iy, iz) in the grid
+    origin: Tuple[float, float, float]   # lower corner of the grid (float32 values)
+    dims: Tuple[int, int, int]      # voxels per axis
+    voxel_size: float               # as float32
+    n_input: int                    # samples with 0 < depth < max_depth
+    n_outside: int                  # ... of which outside the grid
+    n_bricks: int                   # 8x8x8 bricks holding a sample
+    n_voxels: int                   # occupied voxels (M of them have at least min_obs samples)
+
+
+def _f32(x) -> float:
+    """x rounded to float32, as a Python float (what the C ABI's `float` arguments receive)."""
+    return struct.unpack("f", struct.pack("f", float(x)))[0]
+
+
+def fusion_grid(K: torch.Tensor, cam2world: torch.Tensor, H: int, W: int, voxel_size: float, max_depth: float = MAX_DEPTH):
+    """A grid that holds every sample of depth < max_depth seen from the given cameras: (origin, dims).  Host, float64.
+    A sample at z-depth d lies d * |ray| from its camera, |ray| = sqrt(1 + ((u-cx)/fx)^2 + ((v-cy)/fy)^2), largest at an
+    image corner; the box is the camera centres -/+ max_depth * (largest corner ray of any frame) -/+ one voxel, snapped
+    outward to whole bricks (multiples of 8 voxels).  Loose is cheap -- 4 bytes per brick."""
+    Kd = K.detach().to("cpu", torch.float64).reshape(-1, 3, 3)
+    Md = cam2world.detach().to("cpu", torch.float64).reshape(-1, 4, 4)
+    vs = _f32(voxel_size)
+    if not (vs > 0.0 and math.isfinite(vs)) or not (max_depth > 0.0 and math.isfinite(max_depth)):
+        raise ValueError("fusion_grid: voxel_size and max_depth must be finite and positive")
+    ray = 0.0
+    for u in (0.0, float(W - 1)):
+        for v in (0.0, float(H - 1)):
+            x = (u - Kd[:, 0, 2]) / Kd[:, 0, 0]
+            y = (v - Kd[:, 1, 2]) / Kd[:, 1, 1]
+            ray = max(ray, float(torch.sqrt(1.0 + x * x + y * y).max()))
+    reach = float(max_depth) * ray + vs
+    centres = Md[:, :3, 3]
+    brick = 8.0 * vs
+    lo = [math.floor((float(centres[:, a].min()) - reach) / brick) for a in range(3)]
+    hi = [math.ceil((float(centres[:, a].max()) + reach) / brick) for a in range(3)]
+    origin = tuple(_f32(l * brick) for l in lo)
+    dims = tuple(8 * max(1, h - l) for l, h in zip(lo, hi))
+    return origin, dims
+
+
+def fuse_point_cloud(depths: torch.Tensor, K: torch.Tensor, cam2world: torch.Tensor, *, voxel_size: float,
+                     colors: Optional[torch.Tensor] = None, stride: int = 1, max_depth: float = MAX_DEPTH, min_obs: int = 1,
+                     origin=None, dims=None) -> FusedCloud:
+    """Every `stride`-th pixel of every frame with 0 < depth < max_depth, gathered into the voxels of a regular grid: one
+    point per voxel seen at least `min_obs` times, carrying the mean position, the mean colour (colors [N,3,H,W] in
+    [0,1]) and the count of its samples, in ascending (8x8x8 brick, voxel in brick) order.  Integer sums: the result is
+    bit-identical between calls, streams and frame orders (contract: include/colvo.h).  origin / dims
+    default to fusion_grid's; samples outside the grid are counted in n_outside.  Reads two counts back (4 bytes each,
+    after the plan and after the count) to size the voxel pool and the result."""
+    lib = _lib.load()
+    if not isinstance(depths, torch.Tensor) or depths.dim() != 4:
+        raise ValueError("fuse_point_cloud: depths must be [N,1,H,W]")
+    N, _, H, W = depths.shape
+    if stride < 1 or min_obs < 1:
+        raise ValueError("fuse_point_cloud: stride and min_obs must be >= 1")
+    depths = _chk(depths, "depths", (N, 1, H, W))
+    K = _chk(K, "K", (N, 3, 3))
+    cam2world = _chk(cam2world, "cam2world", (N, 4, 4))
+    if colors is not None:
+        colors = _chk(colors, "colors", (N, 3, H, W))
+    vs = _f32(voxel_size)
+    if not (vs > 0.0 and math.isfinite(vs)):
+        raise ValueError("fuse_point_cloud: voxel_size must be finite and positive")
+    if (origin is None) != (dims is None):
+        raise ValueError("fuse_point_cloud: give origin and dims together, or neither")
+    if origin is None:
+        origin, dims = fusion_grid(K, cam2world, H, W, vs, max_depth)
+    origin = tuple(_f32(o) for o in origin)
+    dims = tuple(int(d) for d in dims)
+    if len(origin) != 3 or len(dims) != 3 or any(d <= 0 or d % 8 for d in dims):
+        raise ValueError(f"fuse_point_cloud: dims must be three positive multiples of 8, got {dims}")
+    dev = depths.device
+    geom = (N, H, W, int(stride), float(max_depth), *origin, vs, *dims)
+    ws_bytes = int(lib.colvo_fuse_plan_workspace_bytes(N, H, W, int(stride), *dims))
+    if ws_bytes == 0:
+        raise ValueError(f"fuse_point_cloud: shape N={N} H={H} W={W} stride={stride} or grid {dims} beyond the kernels' limits")
+    ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
+    stats = torch.empty(3, device=dev, dtype=torch.int32)
+    stream = _lib.stream_ptr()
+    _lib.check(lib.colvo_fuse_plan(_lib.ptr(depths), _lib.ptr(K), _lib.ptr(cam2world), *geom, _lib.ptr(ws), _lib.ptr(stats),
+                                   stream), "colvo_fuse_plan")
+    n_input, n_outside, n_bricks = (int(v) for v in stats.tolist())
+    n_voxels = m = 0
+    if n_bricks > 0:
+        pool_bytes = int(lib.colvo_fuse_pool_bytes(n_bricks))
+        if pool_bytes == 0:
+            raise RuntimeError(f"fuse_point_cloud: {n_bricks} occupied bricks, the limit is 2^22 - 1: use a larger voxel_size")
+        pool = torch.empty(pool_bytes, device=dev, dtype=torch.uint8)
+        _lib.check(lib.colvo_fuse_accumulate(_lib.ptr(depths), _lib.ptr(colors), _lib.ptr(K), _lib.ptr(cam2world), *geom,
+                                             _lib.ptr(ws), n_bricks, _lib.ptr(pool), stream), "colvo_fuse_accumulate")
+        ews = torch.empty(int(lib.colvo_fuse_extract_workspace_bytes(n_bricks)), device=dev, dtype=torch.uint8)
+        stats2 = torch.empty(3, device=dev, dtype=torch.int32)
+        _lib.check(lib.colvo_fuse_count(_lib.ptr(pool), n_bricks, int(min_obs), _lib.ptr(ews), _lib.ptr(stats2), stream),
+                   "colvo_fuse_count")
+        n_voxels, m, overflow = (int(v) for v in stats2.tolist())
+        if overflow:
+            raise RuntimeError("fuse_point_cloud: overflow: a voxel received 2^24 or more samples (its 32-bit sums may have "
+                               "wrapped); use a smaller voxel_size, a larger stride or fewer frames per call")
+    points = torch.empty(m, 3, device=dev, dtype=torch.float32)
+    out_colors = torch.empty(m, 3, device=dev, dtype=torch.float32) if colors is not None else None
+    counts = torch.empty(m, device=dev, dtype=torch.int32)
+    voxels = torch.empty(m, 3, device=dev, dtype=torch.int32)
+    if m > 0:
+        _lib.check(lib.colvo_fuse_write(_lib.ptr(ws), _lib.ptr(pool), n_bricks, int(min_obs), *origin, vs, *dims, _lib.ptr(ews),
+                                        m, _lib.ptr(points), _lib.ptr(out_colors), _lib.ptr(counts), _lib.ptr(voxels), stream),
+                   "colvo_fuse_write")
+    return FusedCloud(points, out_colors, counts, voxels, origin, dims, vs, n_input, n_outside, n_bricks, n_voxels)
+
+
+def write_ply(path, points: torch.Tensor, colors: Optional[torch.Tensor] = None) -> None:
+    """Binary little-endian PLY: `float x y z` per vertex and, with colours [M,3] in [0,1], `uchar red green blue`
+    (rint(c * 255), clamped).  Host code; one device -> host copy."""
+    import numpy as np
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError("write_ply: points must be [M,3]")
+    if colors is not None and tuple(colors.shape) != tuple(points.shape):
+        raise ValueError("write_ply: colors must have the shape of points")
+    both = points.detach().to(torch.float32) if colors is None else torch.cat(
+        [points.detach().to(torch.float32), colors.detach().to(points.device, torch.float32)], dim=1)
+    host = both.cpu().numpy()
+    m = host.shape[0]
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    header = ["ply", "format binary_little_endian 1.0", f"element vertex {m}", "property float x", "property float y",
+              "property float z"]
+    if colors is not None:
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+        header += ["property uchar red", "property uchar green", "property uchar blue"]
+    header.append("end_header")
+    rows = np.empty(m, dtype=np.dtype(fields))
+    for a, name in enumerate("xyz"):
+        rows[name] = host[:, a]
+    if colors is not None:
+        q = np.clip(np.rint(np.nan_to_num(host[:, 3:6], nan=0.0) * 255.0), 0, 255).astype(np.uint8)
+        for k, name in enumerate(("red", "green", "blue")):
+            rows[name] = q[:, k]
+    with open(path, "wb") as f:
+        f.write(("\n".join(header) + "\n").encode("ascii"))
+        f.write(rows.tobytes())
+
+
 class Reconstruction(NamedTuple):
     depths: torch.Tensor        # [N+1,1,H,W]
     rel_poses: torch.Tensor     # [N,6]    frame k -> frame k+1
     cam2world: torch.Tensor     # [N+1,4,4] float64, CPU
     points: torch.Tensor        # [M,3]    world frame (camera 0)
+    fused: Optional[FusedCloud] = None   # with voxel_size: the coloured, voxel-averaged cloud
 
 
 @torch.no_grad()
@@ -119,9 +268,11 @@ def run_networks(depth_net, pose_net, frames: torch.Tensor, *, chunk: int = 16):
 
 @torch.no_grad()
 def reconstruct_sequence(depth_net, pose_net, frames: torch.Tensor, K: torch.Tensor, *, stride: int = 4,
-                         max_depth: float = MAX_DEPTH, chunk: int = 16) -> Reconstruction:
+                         max_depth: float = MAX_DEPTH, chunk: int = 16, voxel_size: Optional[float] = None,
+                         min_obs: int = 1) -> Reconstruction:
     """frames [N+1,3,H,W] of one sequence, K [3,3] or [N+1,3,3] -> depth of every frame, the pose of every consecutive
-    pair (DCDP: PoseNet sees both depth maps), the integrated trajectory and the stitched cloud."""
+    pair (DCDP: PoseNet sees both depth maps), the integrated trajectory and the stitched cloud.  With a voxel_size also
+    the fused cloud of the same samples, coloured by the frames (fuse_point_cloud; `fused`, else None)."""
     n = frames.shape[0]
     if n < 2:
         raise ValueError("reconstruct_sequence: need at least two frames")
@@ -130,5 +281,10 @@ def reconstruct_sequence(depth_net, pose_net, frames: torch.Tensor, K: torch.Ten
     K = K.to(frames.device, torch.float32).contiguous()
     depths, rel = run_networks(depth_net, pose_net, frames, chunk=chunk)
     traj = integrate_trajectory(rel)
-    cloud = stitch_point_cloud(depths, K, traj.to(frames.device, torch.float32), stride=stride, max_depth=max_depth)
-    return Reconstruction(depths, rel, traj, cloud)
+    traj32 = traj.to(frames.device, torch.float32)
+    cloud = stitch_point_cloud(depths, K, traj32, stride=stride, max_depth=max_depth)
+    fused = None
+    if voxel_size is not None:
+        fused = fuse_point_cloud(depths, K, traj32, voxel_size=voxel_size, colors=frames.to(torch.float32).contiguous(),
+                                 stride=stride, max_depth=max_depth, min_obs=min_obs)
+    return Reconstruction(depths, rel, traj, cloud, fused)

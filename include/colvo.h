@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define COLVO_ABI_VERSION 12
+#define COLVO_ABI_VERSION 13
 
 typedef void* colvo_stream_t; /* hipStream_t */
 
@@ -430,6 +430,41 @@ size_t colvo_stitch_workspace_ints(int N, int H, int W, int stride);
 int colvo_stitch_point_cloud(const float* depths, const float* K, const float* cam2world, int N, int H, int W,
                              int stride, float max_depth, int32_t* workspace, float* points, int32_t* n_points,
                              colvo_stream_t stream);
+
+/* Fusion of N depth maps into one point per occupied voxel: mean position, mean colour and observation count of
+ * the samples that fell into each voxel of a regular grid (lower corner ox, oy, oz; nx * ny * nz voxels of edge voxel_size, each
+ * extent a positive multiple of 8; brick = 8x8x8 voxels).  Samples are the pixels colvo_stitch_point_cloud walks with
+ * 0 < depth < max_depth; the world point is float32 with every operation individually rounded (no FMA contraction) in the order
+ * px = ((u - cx) / fx) * d, X_a = ((r_a0 * px + r_a1 * py) + r_a2 * d) + t_a; g_a = (X_a - o_a) * (1.0f / voxel_size); inside iff
+ * 0 <= g_a < n_a; voxel floor(g_a); sub-voxel quantum floor(frac(g_a) * 256); colour quantum clamp(rint(c * 255), 0, 255), NaN -> 0.
+ * Per voxel the count and the sums of the quanta are kept as unsigned integers (integer atomics only: bit-identical between calls,
+ * streams and frame orders).  Rows come out in ascending (brick index (bz * nby + by) * nbx + bx, local index (lz * 8 + ly) * 8 + lx).
+ * Four phases; the caller reads n_bricks back after the plan and M after the count to size the pool and the outputs:
+ *   plan        marks the bricks that hold a sample and numbers them in ascending order.  stats (device int32[3]): kept samples,
+ *               kept samples outside the grid, occupied bricks.  workspace: colvo_fuse_plan_workspace_bytes bytes.
+ *   accumulate  clears the pool (colvo_fuse_pool_bytes(n_bricks) bytes = n_bricks * 512 records of 32 bytes) and adds every inside
+ *               sample to its record.  colors [N,3,H,W] in [0,1], or NULL (no colour sums).
+ *   count       rows per brick with count >= min_obs, scanned.  stats2 (device int32[3]): occupied voxels, rows M, overflow flag
+ *               (a voxel with 2^24 or more samples: its 32-bit sums may have wrapped).  extract_ws:
+ *               colvo_fuse_extract_workspace_bytes(n_bricks) bytes.
+ *   write       points[m][a] = float(double(o_a) + (double(i_a) + (double(sum q_a) + 0.5 * n) / (256.0 * n)) * double(voxel_size)),
+ *               colors[m][k] = float(double(sum c_k) / (255.0 * n)) (NULL: not written), counts[m] = n, voxels[m] = (ix, iy, iz).
+ *               min_obs as given to the count; n_rows = M, the rows the outputs hold (no row beyond it is written).
+ * Limits: N <= 65535, H*W < 2^30, fewer than 2^31 samples, fewer than 2^28 bricks in the grid, n_bricks < 2^22, voxel_size finite
+ * and positive, workspaces, pool 16-byte aligned.  The size functions return 0 for what the calls refuse. */
+size_t colvo_fuse_plan_workspace_bytes(int N, int H, int W, int stride, int nx, int ny, int nz);
+int colvo_fuse_plan(const float* depths, const float* K, const float* cam2world, int N, int H, int W, int stride, float max_depth,
+                    float ox, float oy, float oz, float voxel_size, int nx, int ny, int nz, void* workspace, int32_t* stats,
+                    colvo_stream_t stream);
+size_t colvo_fuse_pool_bytes(int n_bricks);
+int colvo_fuse_accumulate(const float* depths, const float* colors, const float* K, const float* cam2world, int N, int H, int W,
+                          int stride, float max_depth, float ox, float oy, float oz, float voxel_size, int nx, int ny, int nz,
+                          const void* workspace, int n_bricks, void* pool, colvo_stream_t stream);
+size_t colvo_fuse_extract_workspace_bytes(int n_bricks);
+int colvo_fuse_count(const void* pool, int n_bricks, int min_obs, void* extract_ws, int32_t* stats2, colvo_stream_t stream);
+int colvo_fuse_write(const void* workspace, const void* pool, int n_bricks, int min_obs, float ox, float oy, float oz,
+                     float voxel_size, int nx, int ny, int nz, const void* extract_ws, int n_rows, float* points, float* colors,
+                     int32_t* counts, int32_t* voxels, colvo_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------- *
  * SURVEY.md §6  evaluation: depth error measures with per-image median scaling. *
