@@ -73,16 +73,39 @@ struct ConvPlan {
 bool conv_rt_plan(ConvK& k, int B, int dtype, ConvPlan& p);
 int conv_rt_launch(const ConvK& k, const ConvPlan& p, int dtype, hipStream_t s);
 
-// wgrad_rt.hip: register-tiled weight gradient (bf16, stride 1).  wgrad.hip asks for a plan (false: the layer does not qualify), sets up
-// the way out that the plan's split count calls for (atomics / slabs / sole writer), launches, and runs its own second launch if any.
+// Where a weight-gradient kernel puts its sums: part of the kernel argument of all three kernels (k_wgrad3x3, k_wgrad_up2, k_wgrad_rt),
+// filled once per launch by wgrad.hip's wgrad_resolve.  Device pointers and flags only.
+//   slabs != null  every pixel-range split STORES its sums into a slab of its own; k_wgrad_reduce or colvo_wgrad_reduce_group adds the
+//                  slabs to dw / db in split order (the kernel touches neither: they may be null; `way` stays SINK_ATOMIC)
+//   otherwise `way` says how dw / db are written:
+//   SINK_ATOMIC    one fp32 atomic per element
+//   SINK_RMW       ONE split, deterministic form: the sole writer of an element adds with a plain read-modify-write (no slab)
+//   SINK_STORE     ONE split and dw / db known to be zero: the sole writer stores
+// The layout is part of the kernels' code generation: the 3x3 kernels run at the SGPR limit and spill scalars into VGPR lanes, so
+// their VGPR counts follow the offsets the kernel argument is loaded from.  Measured over the 47 instantiations (hipcc 7.2,
+// -Rpass-analysis=kernel-resource-usage): with dw, Ctot, db in this order behind WgradK's Cout every count is what it was before the
+// sink existed; Ctot beside Cout changes 8 of them, the flag as an `int` 3 to 7 depending on where it sits.
+enum { SINK_ATOMIC, SINK_RMW, SINK_STORE };
+struct WgradSink {
+    float* dw;                // [Cout][9][Ctot]
+    int Ctot;
+    float* db;                // [Cout]
+    int way;
+    bool bias;                // compute the bias sums (a caller without db has none; the slab form always does)
+    float* slabs;             // [nsplit][Cout * 9 * Ctot]
+    float* db_slabs;          // [nsplit][Cout]
+};
+
+// wgrad_rt.hip: register-tiled weight gradient (bf16, stride 1).  wgrad.hip asks for a plan (false: the layer does not qualify), resolves
+// the sink that the plan's split count calls for, launches, and runs its own second launch if any.
 struct WgradRtPlan {
     int ni, toh, tow, pwl, pimg, ksteps, xinstr;
     int tiles_x, tiles_y, ntiles, tiles_per_split, nsplit;
     int nci0, nci, nco;
 };
 bool wgrad_rt_plan(const ColvoConvDesc* d, WgradRtPlan& p);
-int wgrad_rt_launch(const WgradRtPlan& p, const ColvoConvDesc* d, const void* x0, const void* x1, const void* dy, float* dw, float* db,
-                    float* slabs, float* db_slabs, int det, hipStream_t s);
+int wgrad_rt_launch(const WgradRtPlan& p, const ColvoConvDesc* d, const void* x0, const void* x1, const void* dy, const WgradSink& out,
+                    hipStream_t s);
 
 namespace {
 
@@ -135,34 +158,56 @@ inline int wgrad_row_pitch(int pw, int tow) { return (tow % 8 == 0) ? pw : pw + 
 #define TRACE(slot) do {} while (0)
 #endif
 
+// The argument of k_wgrad3x3 / k_wgrad_up2: what the kernels read, nothing else.  wgrad.hip's planner fills the geometry, tile and grid
+// (no pointer needed), the launch path the operand pointers and the sink.
 struct WgradK {
     Gather g;
     int Ho, Wo, B;
     const char* dy;           // [B][Ho][Wo][Cout]
     int Cout;
-    float* dw;                // [Cout][9][Ctot]
-    int Ctot;
-    float* db;
+    WgradSink out;
     int toh, tow, tiles_x, tiles_y, ntiles, tiles_per_split;
     uint32_t m_pw, m_tow;     // see ConvK
     int nsplit, cot, xcd;     // 1-D grid: (co tile, chunk) fastest, pixel-range split slowest; XCD remap on/off
     int pwl;                  // LDS pitch of a patch row, in pixels (wgrad_row_pitch)
-    int det;                  // ONE split: 1 = deterministic form, plain read-modify-write instead of atomics (no slab); 2 = the arena is
-                              // known to be zero: plain stores
-    int slabs_only;           // host side: colvo_conv_wgrad_slabs -- always slabs (a single split too), no second launch
-    int clean;                // host side: the caller vouches that dw / db are zero (colvo_conv_wgrad_clean)
-    // Deterministic form (colvo_conv_wgrad_det): every pixel-range split STORES its sums into a slab of its own instead of
-    // adding them to dw / db with float atomics; k_wgrad_reduce then adds the slabs in split order.  null: atomics.
-    float* slabs;             // [nsplit][Cout * 9 * Ctot]
-    float* db_slabs;          // [nsplit][Cout]
-    // host side only
-    const char* scratch;
-    long long scratch_bytes;
-    int* plan_out;            // non-null: write the number of splits the launch WOULD use and do not launch
 #ifdef COLVO_WTRACE
     long long* trace;         // developer build only (tools/wtrace_wgrad.sh): [workgroup][8] shader-clock stamps of the kernel phases
 #endif
 };
+
+// A lane's four weight rows e0, e0 + erow, ... (the first nrow of them inside the tensor; <= 0: none) of pixel-range split `bsplit`, by
+// the sink's way out (k_wgrad_up2, k_wgrad_rt; k_wgrad3x3 walks its fragments in an order of its own).  The read-modify-write has all
+// its loads in flight before the first store.
+__device__ __forceinline__ void wgrad_put_rows(const WgradSink& o, int bsplit, size_t wsize, size_t e0, size_t erow, int nrow, f32x4 v) {
+    if (o.slabs) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            if (r < nrow) o.slabs[(size_t)bsplit * wsize + e0 + r * erow] = v[r];
+    } else if (o.way == SINK_STORE) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            if (r < nrow) o.dw[e0 + r * erow] = v[r];
+    } else if (o.way == SINK_RMW) {
+        float old[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) old[r] = r < nrow ? o.dw[e0 + r * erow] : 0.0f;
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            if (r < nrow) o.dw[e0 + r * erow] = old[r] + v[r];
+    } else {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            if (r < nrow) atomicAdd(o.dw + e0 + r * erow, v[r]);
+    }
+}
+
+// ... and the bias sum of output channel co0 + c (two arguments: the slab index is summed in the order the kernels summed it)
+__device__ __forceinline__ void wgrad_put_bias(const WgradSink& o, int bsplit, int Cout, int co0, int c, float t) {
+    if (o.slabs) o.db_slabs[(size_t)bsplit * Cout + co0 + c] = t;
+    else if (o.way == SINK_STORE) o.db[co0 + c] = t;
+    else if (o.way == SINK_RMW) o.db[co0 + c] += t;
+    else atomicAdd(o.db + co0 + c, t);
+}
 
 // Workgroups are dealt round-robin over the 8 XCDs (private L2s): give each XCD a CONTIGUOUS range of the logical work ids,
 // so that the workgroups that share operands -- the output-channel tiles of one pixel tile (same input patch), the

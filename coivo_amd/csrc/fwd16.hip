@@ -49,7 +49,7 @@ struct Fwd16K {
 
 __global__ __launch_bounds__(NT, 4) void k_fwd16_head(const Fwd16K a) {
     __shared__ __attribute__((aligned(16))) char sU[NU * PIXB];
-    __shared__ __attribute__((aligned(16))) char sY[(NY + 12) * PIXB];        // (+ 12: the dummy positions 180 .. 191 of the last fragment)
+    __shared__ __attribute__((aligned(16))) char sY[(NY + 12) * PIXB];        // (+ 12: the padding positions 180 .. 191 of the last fragment)
     // head weights as an MFMA operand, [16 rows][10 taps][16 c] bf16, row pitch 352 B (conflict-free ds_read_b128 of 16 rows): read per
     // tile inside the head's pipeline -- resident they cost the 20 registers the second tile of loads in flight needs
     __shared__ __attribute__((aligned(16))) char sWh[16 * WROWB];
@@ -137,11 +137,11 @@ __global__ __launch_bounds__(NT, 4) void k_fwd16_head(const Fwd16K a) {
     int u_base[3], y_lds[3], pos_y[3], pos_x[3];
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
-        int pp = 16 * (3 * wave + j) + l15;                       // position index in the 10 x 18 grid (>= 180: dummy)
+        int pp = 16 * (3 * wave + j) + l15;                       // position index in the 10 x 18 grid (>= 180: padding)
         y_lds[j] = pp * PIXB + kg * 8;
         if (pp >= NY) pp = 0;
         const int py = pp / YW, px = pp - py * YW;
-        pos_y[j] = (16 * (3 * wave + j) + l15 < NY) ? py : -100;  // dummy positions fail every bounds test below
+        pos_y[j] = (16 * (3 * wave + j) + l15 < NY) ? py : -100;  // padding positions fail every bounds test below
         pos_x[j] = px;
         u_base[j] = (py * UW + px) * PIXB + (kg & 1) * 16;        // input patch pixel of tap (0, 0)
     }

@@ -102,7 +102,7 @@ __global__ __launch_bounds__(NT * KS) void k_wgrad3x3(const WgradK a) {
         const int c = ncol_addr - (ncol_addr / CK) * CK;
         boff[fi] = ((tap / 3) * PWL + (tap % 3)) * PIXP + c * ES;
         const int ncol = 16 * f + l15;
-        ocol[fi] = (f < NFR && ncol < NCOL) ? ((ncol / CK) * a.Ctot + (ncol % CK)) : -1;
+        ocol[fi] = (f < NFR && ncol < NCOL) ? ((ncol / CK) * a.out.Ctot + (ncol % CK)) : -1;
     }
 
     f32x4 acc[MT][FPW];
@@ -251,7 +251,7 @@ __global__ __launch_bounds__(NT * KS) void k_wgrad3x3(const WgradK a) {
         for (int q = 0; q < KS; ++q) tile_next(cur);
         if (t + KS < t_end) { const bool live = t + KS + team < t_end; load_dy(cur, live); load_p(cur, live); }   // in flight during the MFMAs below
 
-        if (bchunk == 0 && a.db) {
+        if (bchunk == 0 && a.out.bias) {
             float s0 = 0.0f, s1 = 0.0f;
 #pragma unroll 4
             for (int p = db_ph; p < BM; p += 2 * NPH) {   // rows beyond the tile hold zeros
@@ -383,17 +383,19 @@ __global__ __launch_bounds__(NT * KS) void k_wgrad3x3(const WgradK a) {
         }
     }
     if (team == 0) {
-        // D rows = co (4*kg + r), cols = (tap, c).  Three ways out: one fp32 atomic per element (a.det == 0); deterministic form with
+        // D rows = co (4*kg + r), cols = (tap, c).  Three ways out: one fp32 atomic per element (SINK_ATOMIC); deterministic form with
         // several splits: this split's own slab; deterministic form with ONE split = this workgroup is the only writer of its
         // elements: plain read-modify-write, all loads in flight before the first store (40 dependent load -> store round trips
         // otherwise) -- no slab, no second launch.  (Against the atomics the read-modify-write measured 1 us SLOWER, enc5b 25.6 ->
         // 26.7 us: the loads miss the XCD's L2, the atomics are fire-and-forget; so it serves the deterministic form only.)
+        // (`!slabs &&` says nothing new -- a sink with slabs is SINK_ATOMIC -- but without it eight instantiations allocate other
+        // VGPR counts: conv_common.h WgradSink.)
         auto elem = [&](int mi, int fi, int r, size_t& e) -> bool {
             const int co = co0 + 16 * mi + 4 * kg + r;
-            e = (size_t)co * 9 * a.Ctot + wc0 + ocol[fi];
+            e = (size_t)co * 9 * a.out.Ctot + wc0 + ocol[fi];
             return ocol[fi] >= 0 && co < a.Cout;
         };
-        if (!a.slabs && a.det == 2) {
+        if (!a.out.slabs && a.out.way == SINK_STORE) {
             // ONE split and a gradient arena known to be zero (colvo_conv_wgrad_clean): this workgroup is the first and only writer
             // of its elements in this step -- plain stores, neither atomics (6-7.7 us of a workgroup's life, profiles/r4_wgrad_phases.md)
             // nor the loads of the read-modify-write
@@ -402,21 +404,21 @@ __global__ __launch_bounds__(NT * KS) void k_wgrad3x3(const WgradK a) {
 #pragma unroll
                 for (int fi = 0; fi < FPW; ++fi)
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) { size_t e; if (elem(mi, fi, r, e)) a.dw[e] = acc[mi][fi][r]; }
-        } else if (!a.slabs && a.det) {
+                    for (int r = 0; r < 4; ++r) { size_t e; if (elem(mi, fi, r, e)) a.out.dw[e] = acc[mi][fi][r]; }
+        } else if (!a.out.slabs && a.out.way == SINK_RMW) {
             float old[MT][FPW][4];
 #pragma unroll
             for (int mi = 0; mi < MT; ++mi)
 #pragma unroll
                 for (int fi = 0; fi < FPW; ++fi)
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) { size_t e; old[mi][fi][r] = elem(mi, fi, r, e) ? a.dw[e] : 0.0f; }
+                    for (int r = 0; r < 4; ++r) { size_t e; old[mi][fi][r] = elem(mi, fi, r, e) ? a.out.dw[e] : 0.0f; }
 #pragma unroll
             for (int mi = 0; mi < MT; ++mi)
 #pragma unroll
                 for (int fi = 0; fi < FPW; ++fi)
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) { size_t e; if (elem(mi, fi, r, e)) a.dw[e] = old[mi][fi][r] + acc[mi][fi][r]; }
+                    for (int r = 0; r < 4; ++r) { size_t e; if (elem(mi, fi, r, e)) a.out.dw[e] = old[mi][fi][r] + acc[mi][fi][r]; }
         } else {
 #pragma unroll
             for (int mi = 0; mi < MT; ++mi)
@@ -426,12 +428,12 @@ __global__ __launch_bounds__(NT * KS) void k_wgrad3x3(const WgradK a) {
                     for (int r = 0; r < 4; ++r) {
                         size_t e;
                         if (!elem(mi, fi, r, e)) continue;
-                        if (a.slabs) a.slabs[(size_t)bsplit * a.Cout * 9 * a.Ctot + e] = acc[mi][fi][r];   // this split's own slab
-                        else atomicAdd(a.dw + e, acc[mi][fi][r]);
+                        if (a.out.slabs) a.out.slabs[(size_t)bsplit * a.Cout * 9 * a.out.Ctot + e] = acc[mi][fi][r];   // this split's own slab
+                        else atomicAdd(a.out.dw + e, acc[mi][fi][r]);
                     }
         }
     }
-    if (bchunk == 0 && a.db) {                           // fold the NPH pixel phases (of every team) in LDS: one atomic per channel
+    if (bchunk == 0 && a.out.bias) {                     // fold the NPH pixel phases (of every team) in LDS: one sum per channel
         __syncthreads();
         sdb[threadIdx.x] = dbacc;
         __syncthreads();
@@ -439,10 +441,7 @@ __global__ __launch_bounds__(NT * KS) void k_wgrad3x3(const WgradK a) {
             float t = 0.0f;
 #pragma unroll
             for (int ph = 0; ph < NPH * KS; ++ph) t += sdb[ph * 16 * MT + tid];
-            if (a.db_slabs) a.db_slabs[(size_t)bsplit * a.Cout + co0 + tid] = t;
-            else if (a.det == 2) a.db[co0 + tid] = t;
-            else if (a.det) a.db[co0 + tid] += t;
-            else atomicAdd(a.db + co0 + tid, t);
+            wgrad_put_bias(a.out, bsplit, a.Cout, co0, tid, t);
         }
     }
 #ifdef COLVO_WTRACE
@@ -545,12 +544,13 @@ __global__ __launch_bounds__(NT) void k_wgrad_reduce_group(const ReduceGroup g) 
 // developer build (tools/wtrace_wgrad.sh): per-workgroup phase stamps of k_wgrad3x3, printed as means over the workgroups
 static long long* g_wtrace = nullptr;
 static int g_wtrace_calls = 0;
-inline void wtrace_begin(WgradK& k, unsigned nwg, hipStream_t s) {
+inline WgradK wtrace_begin(WgradK k, unsigned nwg, hipStream_t s) {      // k with the stamp buffer attached
     k.trace = nullptr;
-    if (!getenv("COLVO_WTRACE") || nwg > (1u << 14)) return;
+    if (!getenv("COLVO_WTRACE") || nwg > (1u << 14)) return k;
     if (!g_wtrace) (void)hipMalloc(&g_wtrace, (size_t)(1u << 14) * 16 * sizeof(long long));
     (void)hipMemsetAsync(g_wtrace, 0, (size_t)nwg * 16 * sizeof(long long), s);
     k.trace = g_wtrace;
+    return k;
 }
 inline void wtrace_end(const WgradK& k, unsigned nwg, int MT, int NG, bool tail, int ks, hipStream_t s) {
     if (!k.trace || (++g_wtrace_calls % atoi(getenv("COLVO_WTRACE"))) != 0) return;
@@ -568,44 +568,60 @@ inline void wtrace_end(const WgradK& k, unsigned nwg, int MT, int NG, bool tail,
     fprintf(stderr, "[wtrace] MT=%d NG=%d tail=%d KS=%d S=%d Cout=%d Ctot=%d %dx%d tile %dx%d grid=%u nsplit=%d tiles/wg %.1f | clock %.0f MHz | "
             "mean wg (us): life %.2f = setup+first-load %.2f + store %.2f + compute %.2f + flush %.2f | per tile: store %.3f compute %.3f = "
             "load issue %.3f + MFMA phase %.3f + barrier wait %.3f\n",
-            MT, NG, (int)tail, ks, k.g.stride, k.Cout, k.Ctot, k.Ho, k.Wo, k.toh, k.tow, nwg, k.nsplit, m[7], cyc_per_us,
+            MT, NG, (int)tail, ks, k.g.stride, k.Cout, k.out.Ctot, k.Ho, k.Wo, k.toh, k.tow, nwg, k.nsplit, m[7], cyc_per_us,
             m[5] / cyc_per_us, m[1] / cyc_per_us, m[2] / cyc_per_us, m[3] / cyc_per_us, m[4] / cyc_per_us, m[2] / cyc_per_us / nt,
             m[3] / cyc_per_us / nt, m[8] / cyc_per_us / nt, m[9] / cyc_per_us / nt, (m[3] - m[8] - m[9]) / cyc_per_us / nt);
 }
+#else
+inline const WgradK& wtrace_begin(const WgradK& k, unsigned, hipStream_t) { return k; }
+inline void wtrace_end(const WgradK&, unsigned, int, int, bool, int, hipStream_t) {}
 #endif
 
-// plan-only calls report the split count; deterministic calls point the kernel at the caller's scratch.  Returns 1 when the
-// caller has nothing more to do (plan written), 0 to go on, < 0 never; errors are reported through *err.
-inline bool wgrad_prepare(WgradK& k, int nsplit, int* err) {
-    *err = 0;
-    if (k.plan_out) { *k.plan_out = nsplit; return true; }
-    k.slabs = nullptr; k.db_slabs = nullptr;
-    // deterministic form with one split: every weight element has exactly one writer, which adds to dw / db with a plain
-    // read-modify-write -- reproducible without slabs or a second launch
-    k.det = (k.scratch && nsplit == 1 && !k.slabs_only) ? 1 : 0;
-    // ... and when the caller vouches that dw / db are still zero (colvo_conv_wgrad_clean) the sole writer just stores
-    if (k.clean && nsplit == 1 && !k.slabs_only && TUNE(wgrad_store_clean)) k.det = 2;
-    if (k.scratch && (nsplit > 1 || k.slabs_only)) {
-        const long long wsize = (long long)k.Cout * 9 * k.Ctot;
-        const long long need = (long long)nsplit * (wsize + k.Cout) * 4;
-        if (need > k.scratch_bytes) {
-            set_error("colvo_conv_wgrad_det: scratch of %lld bytes, %lld needed (colvo_conv_wgrad_scratch_bytes)", k.scratch_bytes, need);
-            *err = (int)hipErrorInvalidValue;
-            return true;
-        }
-        k.slabs = (float*)const_cast<char*>(k.scratch);
-        k.db_slabs = k.slabs + (size_t)nsplit * wsize;
+// What a caller asks of a weight-gradient call: the five extern "C" entries fill it in, wgrad_resolve turns it into a launch's sink.
+//   REQ_PLAIN  colvo_conv_wgrad: add to dw / db
+//   REQ_CLEAN  colvo_conv_wgrad_clean: ... and the caller vouches that dw / db are still zero
+//   REQ_DET    colvo_conv_wgrad_det: add to dw / db, bitwise repeatable (scratch for the slabs of a launch of several splits)
+//   REQ_SLABS  colvo_conv_wgrad_slabs: always slabs (a single split too), left in scratch: colvo_wgrad_reduce_group adds them later
+enum WgradMode { REQ_PLAIN, REQ_CLEAN, REQ_DET, REQ_SLABS };
+struct WgradRequest {
+    float *dw, *db;
+    void* scratch;
+    size_t scratch_bytes;
+    WgradMode mode;
+};
+
+// The way out of one launch of `nsplit` pixel-range splits into o (whose Ctot the planner has set), decided here and nowhere else;
+// `reduce`: k_wgrad_reduce has to follow.
+inline int wgrad_resolve(const WgradRequest& r, int Cout, int nsplit, WgradSink& o, bool& reduce) {
+    o.dw = r.dw; o.db = r.db;
+    o.bias = r.db != nullptr || r.mode == REQ_SLABS;
+    o.slabs = o.db_slabs = nullptr;
+    o.way = SINK_ATOMIC;
+    reduce = false;
+    if (r.mode == REQ_SLABS || (r.mode == REQ_DET && nsplit > 1)) {
+        const long long wsize = (long long)Cout * 9 * o.Ctot;
+        const long long need = (long long)nsplit * (wsize + Cout) * 4;
+        COLVO_CHECK_ARG(need <= (long long)r.scratch_bytes, "colvo_conv_wgrad_det: scratch of %lld bytes, %lld needed (colvo_conv_wgrad_scratch_bytes)",
+                        (long long)r.scratch_bytes, need);
+        o.slabs = (float*)r.scratch;
+        o.db_slabs = o.slabs + (size_t)nsplit * wsize;
+        reduce = r.mode == REQ_DET;
+        return 0;
     }
-    return false;
+    // one split: every weight element has exactly one writer, which stores when the caller vouches that dw / db are still zero ...
+    if (r.mode == REQ_CLEAN && nsplit == 1 && TUNE(wgrad_store_clean)) o.way = SINK_STORE;
+    // ... and in the deterministic form adds with a plain read-modify-write -- reproducible without slabs or a second launch
+    else if (r.mode == REQ_DET) o.way = SINK_RMW;
+    return 0;
 }
 
-inline int wgrad_finish(const WgradK& k, int nsplit, hipStream_t s) {
-    if (!k.slabs || k.slabs_only) return 0;          // (slabs_only: colvo_wgrad_reduce_group adds them later)
-    const size_t wsize = (size_t)k.Cout * 9 * k.Ctot;
+// the second launch of a launch into slabs that are not left to the caller
+inline int wgrad_reduce(const WgradSink& o, int Cout, int nsplit, hipStream_t s) {
+    const size_t wsize = (size_t)Cout * 9 * o.Ctot;
     const unsigned blocks = (unsigned)std::min<size_t>((wsize + NT - 1) / NT, 2048);
-    const unsigned bblocks = k.db ? (unsigned)((k.Cout + NT - 1) / NT) : 0;
-    colvo::launch(k_wgrad_reduce, dim3(blocks + bblocks), dim3(NT), 0, s, (const float*)k.slabs, nsplit, wsize, k.dw, blocks,
-                       (const float*)k.db_slabs, (size_t)k.Cout, k.db);
+    const unsigned bblocks = o.bias ? (unsigned)((Cout + NT - 1) / NT) : 0;
+    colvo::launch(k_wgrad_reduce, dim3(blocks + bblocks), dim3(NT), 0, s, (const float*)o.slabs, nsplit, wsize, o.dw, blocks,
+                       (const float*)o.db_slabs, (size_t)Cout, o.db);
     COLVO_CHECK_LAUNCH("k_wgrad_reduce");
     return 0;
 }
@@ -743,7 +759,7 @@ __global__ __launch_bounds__(NT) void k_wgrad_up2(const WgradK a) {
         tile_next(cur);
         if (t + 1 < t_end) load_tile(cur);             // in flight during the MFMAs below
 
-        if (bchunk == 0 && a.db) {                     // bias gradient: all four class planes (rows beyond the tile hold zeros)
+        if (bchunk == 0 && a.out.bias) {               // bias gradient: all four class planes (rows beyond the tile hold zeros)
             float s0 = 0.0f;
 #pragma unroll 4
             for (int p = db_ph; p < 4 * BM; p += NPH) {
@@ -857,31 +873,12 @@ __global__ __launch_bounds__(NT) void k_wgrad_up2(const WgradK a) {
             const int r = py == 0 ? (ky >= 1) : (ky >= 2), c = px == 0 ? (kx >= 1) : (kx >= 2);
             sum += sEx[(((size_t)c4 * 4 + (r * 2 + c)) * MT + mi) * NCF * 64 + f * 64 + lane];
         }
-        const size_t e0 = (size_t)(co0 + 16 * mi + 4 * kg) * 9 * a.Ctot + (size_t)tap * a.Ctot + c0 + 16 * f + l15;
-        const size_t erow = (size_t)9 * a.Ctot;
+        const size_t e0 = (size_t)(co0 + 16 * mi + 4 * kg) * 9 * a.out.Ctot + (size_t)tap * a.out.Ctot + c0 + 16 * f + l15;
+        const size_t erow = (size_t)9 * a.out.Ctot;
         const int nrow = min(4, a.Cout - (co0 + 16 * mi + 4 * kg));       // rows of this lane inside the tensor (<= 0: none)
-        if (a.slabs) {
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr)
-                if (rr < nrow) a.slabs[(size_t)bsplit * a.Cout * 9 * a.Ctot + e0 + rr * erow] = sum[rr];
-        } else if (a.det == 2) {            // one split, arena known to be zero: plain stores (see k_wgrad3x3)
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr)
-                if (rr < nrow) a.dw[e0 + rr * erow] = sum[rr];
-        } else if (a.det) {                 // deterministic form, one split = sole writer: plain read-modify-write, loads first
-            float old[4];
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) old[rr] = rr < nrow ? a.dw[e0 + rr * erow] : 0.0f;
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr)
-                if (rr < nrow) a.dw[e0 + rr * erow] = old[rr] + sum[rr];
-        } else {
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr)
-                if (rr < nrow) atomicAdd(a.dw + e0 + rr * erow, sum[rr]);
-        }
+        wgrad_put_rows(a.out, bsplit, (size_t)a.Cout * 9 * a.out.Ctot, e0, erow, nrow, sum);
     }
-    if (bchunk == 0 && a.db) {
+    if (bchunk == 0 && a.out.bias) {
         __syncthreads();
         float* sdb = reinterpret_cast<float*>(smem);
         sdb[tid] = dbacc;
@@ -890,10 +887,7 @@ __global__ __launch_bounds__(NT) void k_wgrad_up2(const WgradK a) {
             float t = 0.0f;
 #pragma unroll
             for (int ph = 0; ph < NPH; ++ph) t += sdb[ph * 16 * MT + tid];
-            if (a.db_slabs) a.db_slabs[(size_t)bsplit * a.Cout + co0 + tid] = t;
-            else if (a.det == 2) a.db[co0 + tid] = t;
-            else if (a.det) a.db[co0 + tid] += t;
-            else atomicAdd(a.db + co0 + tid, t);
+            wgrad_put_bias(a.out, bsplit, a.Cout, co0, tid, t);
         }
     }
 }
@@ -919,7 +913,7 @@ static inline GridFloor wgrad_grid_floor(int base, int ntiles, int per_split) {
 // of atomics), so cap the atomic traffic at ~3 MB per launch (re-tuned for the 32-wide co tile: 12 MB 592 us, 6 MB 575, 3 MB 566),
 // but keep at least ~256 workgroups in flight and at most ~1024.
 static inline int wgrad_atomic_splits(const WgradK& k, int per_split, bool& halved) {
-    const double wbytes = (double)k.Cout * 9.0 * k.Ctot * 4.0;
+    const double wbytes = (double)k.Cout * 9.0 * k.out.Ctot * 4.0;
     const GridFloor lo_wgs = wgrad_grid_floor((int)TUNE(wgrad_wg_lo), k.ntiles, per_split);
     halved = lo_wgs.halved;
     int nsplit = (int)(TUNE_F(wgrad_atomic_mb) * 1e6 / wbytes);
@@ -929,7 +923,8 @@ static inline int wgrad_atomic_splits(const WgradK& k, int per_split, bool& halv
     return nsplit;
 }
 
-// Everything a weight-gradient launch needs, decided by wgrad_plan before any HIP call (plan-only calls stop after it)
+// Everything a weight-gradient launch needs but its pointers and its sink, decided by wgrad_plan before any HIP call (the plan queries
+// colvo_conv_wgrad_splits / colvo_conv_wgrad_scratch_bytes stop after it)
 enum { WGRAD_RT, WGRAD_UP2, WGRAD_TEAMS, WGRAD_TAIL };
 struct WgradPlan {
     int form;
@@ -938,7 +933,7 @@ struct WgradPlan {
     size_t lds;
     int nsplit;
     unsigned nwg;
-    bool halved;              // the grid floor was halved (wgrad_grid_floor)
+    uint32_t forms;           // form_bit of every FORM_* the launch counts: the form, the 64-wide co tile, halved / full grid floor
     WgradRtPlan rt;           // WGRAD_RT: the register-tiled form's own plan (wgrad_rt.hip)
 };
 
@@ -965,13 +960,16 @@ int dy_pitch_of(int mt) { return mt == 4 ? dy_pitch<T, 4>() : mt == 2 ? dy_pitch
 
 // The form, instantiation, tile, splits and LDS of a launch; sets k's tile and grid fields.  Reads the tuning table, calls no HIP.
 template <typename T>
-int wgrad_plan(const ColvoConvDesc* d, WgradK& k, WgradPlan& p) {
+int wgrad_plan_t(const ColvoConvDesc* d, WgradK& k, WgradPlan& p) {
     constexpr int G = TT<T>::G;
+    bool halved = false;
+    auto grid_forms = [&](int form) { return form_bit(form) | form_bit(halved ? FORM_WGRAD_HALVED_GRID : FORM_WGRAD_FULL_GRID); };
     // single up-sampled source in whole 32-channel (bf16) / 16-channel (f32) chunks: the four-class form over source positions
     const bool up2_form = TUNE(wgrad_up2) && d->up0 && d->C1 == 0 && d->stride == 1 && d->C0 % (4 * G) == 0 && d->Cout >= 16;
     // bf16 stride-1 layers: the register-tiled form (csrc/wgrad_rt.hip); its ways out are set up exactly as for the kernels below
     if ((!up2_form || TUNE(wgrad_rt_over_up2)) && wgrad_rt_plan(d, p.rt)) {
         p.form = WGRAD_RT;
+        p.forms = form_bit(FORM_WGRAD_RT);
         p.nsplit = p.rt.nsplit;
         return 0;
     }
@@ -989,7 +987,8 @@ int wgrad_plan(const ColvoConvDesc* d, WgradK& k, WgradPlan& p) {
                              (size_t)16 * p.mt * (CK / 16) * 64 * 16) + 64;
             COLVO_CHECK_ARG(p.lds <= 160 * 1024, "wgrad (up-sampled source): tile needs %zu bytes of LDS", p.lds);
             const int chunks = k.g.C[0] / CK, cot = (k.Cout + 16 * p.mt - 1) / (16 * p.mt);
-            set_wgrad_grid(k, p, wgrad_atomic_splits(k, chunks * cot, p.halved), cot, chunks);
+            set_wgrad_grid(k, p, wgrad_atomic_splits(k, chunks * cot, halved), cot, chunks);
+            p.forms = grid_forms(FORM_WGRAD_UP2);
             return 0;
         }
     }
@@ -1039,28 +1038,53 @@ int wgrad_plan(const ColvoConvDesc* d, WgradK& k, WgradPlan& p) {
         COLVO_CHECK_ARG(p.lds <= 160 * 1024, "wgrad: %d teams need %zu bytes of LDS", KS, p.lds);
         // one workgroup per CU (KS * 4 waves fill its SIMDs): as many pixel-range splits as keep the grid within 256
         const GridFloor target = wgrad_grid_floor((int)TUNE(wgrad_team_wgs), k.ntiles, chunks * cot);
-        p.halved = target.halved;
+        halved = target.halved;
         set_wgrad_grid(k, p, std::max(1, target.wgs / (chunks * cot)), cot, chunks);
+        p.forms = grid_forms(FORM_WGRAD_TEAMS);
         return 0;
     }
     p.form = WGRAD_TAIL;
     p.lds = (size_t)BM * DYP + (size_t)PH * PW * PIXP + 64;
     COLVO_CHECK_ARG(p.lds <= 160 * 1024, "wgrad: tile needs %zu bytes of LDS", p.lds);
-    set_wgrad_grid(k, p, wgrad_atomic_splits(k, chunks * cot, p.halved), cot, chunks);
+    set_wgrad_grid(k, p, wgrad_atomic_splits(k, chunks * cot, halved), cot, chunks);
+    p.forms = grid_forms(FORM_WGRAD_TAIL) | (p.mt == 4 ? form_bit(FORM_WGRAD_MT4) : 0);
+    return 0;
+}
+
+// k's geometry, tile and grid and the plan of a launch over d (a whole call or one image slice of it).  No pointer, no HIP call.
+inline int wgrad_plan(const ColvoConvDesc* d, WgradK& k, WgradPlan& p) {
+    k = WgradK{}; p = WgradPlan{};
+    fill_gather(d, nullptr, nullptr, k.g);
+    k.g.C[1] = d->C1;                              // (fill_gather: a source without a pointer has no channels)
+    k.Ho = d->Ho; k.Wo = d->Wo; k.B = d->B; k.Cout = d->Cout; k.out.Ctot = d->C0 + d->C1;
+    return d->dtype == COLVO_F32 ? wgrad_plan_t<float>(d, k, p) : wgrad_plan_t<bf16_t>(d, k, p);
+}
+
+// How a call walks its batch.  The kernels address dY and the sources with 32-bit buffer offsets (< 1 GiB per tensor): larger batches
+// are processed in slices of bmax images -- the gradient accumulates into dw / db anyway.
+struct WgradSlicing {
+    int bmax;
+    long long e0, e1, ey;     // bytes per image of x0, x1, dy
+};
+inline int wgrad_slicing(const ColvoConvDesc* d, WgradSlicing& sl) {
+    const long long es = d->dtype == COLVO_F32 ? 4 : 2;
+    const long long cmax = d->C0 > d->C1 ? d->C0 : d->C1;
+    const long long per_img = std::max((long long)d->Ho * d->Wo * d->Cout, (long long)d->Hi * d->Wi * cmax) * es;
+    COLVO_CHECK_ARG(per_img < 0x40000000LL, "colvo_conv_wgrad: a single image of %lld bytes is not supported", per_img);
+    sl.bmax = (int)std::max(1LL, (0x40000000LL - 1) / per_img);
+    sl.e0 = (long long)(d->up0 ? (d->Hi / 2) * (d->Wi / 2) : d->Hi * d->Wi) * d->C0 * es;
+    sl.e1 = (long long)(d->up1 ? (d->Hi / 2) * (d->Wi / 2) : d->Hi * d->Wi) * d->C1 * es;
+    sl.ey = (long long)d->Ho * d->Wo * d->Cout * es;
     return 0;
 }
 
 template <typename T, int MT, int NG, bool TAIL, int KS = 1>
-int launch_wgrad3x3(WgradK& k, const WgradPlan& p, hipStream_t s) {
+int launch_wgrad3x3(const WgradK& k0, const WgradPlan& p, hipStream_t s) {
     if (int e = allow_dynamic_lds<k_wgrad3x3<T, MT, NG, TAIL, KS>>(p.lds, 160 * 1024, "wgrad")) return e;
-#ifdef COLVO_WTRACE
-    wtrace_begin(k, p.nwg, s);
-#endif
+    const WgradK& k = wtrace_begin(k0, p.nwg, s);
     colvo::launch((k_wgrad3x3<T, MT, NG, TAIL, KS>), dim3(p.nwg), dim3(NT * KS), p.lds, s, k);
     COLVO_CHECK_LAUNCH(KS > 1 ? "k_wgrad3x3 (teams)" : "k_wgrad3x3");
-#ifdef COLVO_WTRACE
     wtrace_end(k, p.nwg, MT, NG, TAIL, KS, s);
-#endif
     return 0;
 }
 
@@ -1073,7 +1097,7 @@ int launch_wgrad_up2(const WgradK& k, const WgradPlan& p, hipStream_t s) {
 }
 
 template <typename T, int MT>
-int launch_wgrad_ng(WgradK& k, const WgradPlan& p, hipStream_t s) {
+int launch_wgrad_ng(const WgradK& k, const WgradPlan& p, hipStream_t s) {
     switch (p.ng) {
         case 4: return p.tail ? launch_wgrad3x3<T, MT, 4, true>(k, p, s) : launch_wgrad3x3<T, MT, 4, false>(k, p, s);
         case 2: return p.tail ? launch_wgrad3x3<T, MT, 2, true>(k, p, s) : launch_wgrad3x3<T, MT, 2, false>(k, p, s);
@@ -1083,7 +1107,7 @@ int launch_wgrad_ng(WgradK& k, const WgradPlan& p, hipStream_t s) {
 
 // the kernel launch of a plan other than WGRAD_RT
 template <typename T>
-int launch_wgrad_t(WgradK& k, const WgradPlan& p, hipStream_t s) {
+int launch_wgrad_t(const WgradK& k, const WgradPlan& p, hipStream_t s) {
     if (p.form == WGRAD_UP2) return p.mt == 2 ? launch_wgrad_up2<T, 2>(k, p, s) : launch_wgrad_up2<T, 1>(k, p, s);
     if (p.form == WGRAD_TEAMS) {
         switch (p.ng) {
@@ -1104,39 +1128,83 @@ int launch_wgrad_t(WgradK& k, const WgradPlan& p, hipStream_t s) {
 
 using namespace colvo;
 
-static int wgrad_impl(const ColvoConvDesc* d, const void* x0, const void* x1, const void* dy, float* dw, float* db,
-                      void* scratch, size_t scratch_bytes, int* plan_out, colvo_stream_t stream, int slabs_only = 0, int clean = 0);
+// One weight-gradient call: per image slice plan -> resolve -> launch -> second launch, every slice adding to the same dw / db (and
+// re-using the same scratch).
+static int wgrad_impl(const ColvoConvDesc* d, const void* x0, const void* x1, const void* dy, const WgradRequest& r, colvo_stream_t stream) {
+    if (int e = check_desc(d, "colvo_conv_wgrad")) return e;
+    COLVO_CHECK_ARG(x0 && dy && (r.dw || r.mode == REQ_SLABS) && (d->C1 == 0 || x1), "colvo_conv_wgrad: null pointer argument");
+    WgradSlicing sl;
+    if (int e = wgrad_slicing(d, sl)) return e;
+    const bool sliced = d->B > sl.bmax;
+    COLVO_CHECK_ARG(!sliced || r.mode != REQ_SLABS, "colvo_conv_wgrad_slabs: batch %d would be sliced (tensors >= 1 GiB); use colvo_conv_wgrad_det", d->B);
+    const hipStream_t s = (hipStream_t)stream;
+    for (int b0 = 0; b0 < d->B; b0 += sl.bmax) {
+        ColvoConvDesc sub = *d;
+        sub.B = std::min(sl.bmax, d->B - b0);
+        WgradK k;
+        WgradPlan p;
+        if (int e = wgrad_plan(&sub, k, p)) return e;
+        WgradRequest rs = r;
+        if (b0 > 0 && r.mode == REQ_CLEAN) rs.mode = REQ_PLAIN;          // (only the first slice finds the arena clean)
+        bool reduce;
+        if (int e = wgrad_resolve(rs, k.Cout, p.nsplit, k.out, reduce)) return e;
+        k.g.src[0] = (const char*)x0 + b0 * sl.e0;
+        k.g.src[1] = d->C1 ? (const char*)x1 + b0 * sl.e1 : nullptr;
+        k.dy = (const char*)dy + b0 * sl.ey;
+        // (the register-tiled form does not count its stores into a clean arena)
+        form_hits(p.forms | (k.out.way == SINK_STORE && p.form != WGRAD_RT ? form_bit(FORM_WGRAD_STORE_CLEAN) : 0) |
+                  (sliced && b0 == 0 ? form_bit(FORM_WGRAD_SLICED) : 0));
+        if (p.form == WGRAD_RT) {
+            if (int e = wgrad_rt_launch(p.rt, &sub, k.g.src[0], k.g.src[1], k.dy, k.out, s)) return e;
+        } else {
+            if (int e = sub.dtype == COLVO_F32 ? launch_wgrad_t<float>(k, p, s) : launch_wgrad_t<bf16_t>(k, p, s)) return e;
+        }
+        if (reduce)
+            if (int e = wgrad_reduce(k.out, k.Cout, p.nsplit, s)) return e;
+    }
+    return 0;
+}
+
+// The most pixel-range splits any slice of a call over d takes (0: the call would be refused).  The planner alone: no pointer, no HIP
+// call, nothing counted.
+static int wgrad_max_splits(const ColvoConvDesc* d, const char* who) {
+    WgradSlicing sl;
+    if (!d || check_desc(d, who) || wgrad_slicing(d, sl)) return 0;
+    int nsplit = 0;
+    for (int b0 = 0; b0 < d->B; b0 += sl.bmax) {
+        ColvoConvDesc sub = *d;
+        sub.B = std::min(sl.bmax, d->B - b0);
+        WgradK k;
+        WgradPlan p;
+        if (wgrad_plan(&sub, k, p)) return 0;
+        nsplit = std::max(nsplit, p.nsplit);
+    }
+    return nsplit;
+}
 
 extern "C" int colvo_conv_wgrad(const ColvoConvDesc* d, const void* x0, const void* x1, const void* dy, float* dw,
                                 float* db, colvo_stream_t stream) {
-    return wgrad_impl(d, x0, x1, dy, dw, db, nullptr, 0, nullptr, stream);
+    return wgrad_impl(d, x0, x1, dy, WgradRequest{dw, db, nullptr, 0, REQ_PLAIN}, stream);
 }
 
 extern "C" int colvo_conv_wgrad_clean(const ColvoConvDesc* d, const void* x0, const void* x1, const void* dy, float* dw,
                                       float* db, int arena_is_zero, colvo_stream_t stream) {
-    return wgrad_impl(d, x0, x1, dy, dw, db, nullptr, 0, nullptr, stream, 0, arena_is_zero ? 1 : 0);
+    return wgrad_impl(d, x0, x1, dy, WgradRequest{dw, db, nullptr, 0, arena_is_zero ? REQ_CLEAN : REQ_PLAIN}, stream);
 }
 
 extern "C" int colvo_conv_wgrad_det(const ColvoConvDesc* d, const void* x0, const void* x1, const void* dy, float* dw,
                                     float* db, void* scratch, size_t scratch_bytes, colvo_stream_t stream) {
     COLVO_CHECK_ARG(scratch, "colvo_conv_wgrad_det: null scratch");
-    return wgrad_impl(d, x0, x1, dy, dw, db, scratch, scratch_bytes, nullptr, stream);
+    return wgrad_impl(d, x0, x1, dy, WgradRequest{dw, db, scratch, scratch_bytes, REQ_DET}, stream);
 }
 
 extern "C" int colvo_conv_wgrad_slabs(const ColvoConvDesc* d, const void* x0, const void* x1, const void* dy, void* scratch,
                                       size_t scratch_bytes, colvo_stream_t stream) {
     COLVO_CHECK_ARG(scratch, "colvo_conv_wgrad_slabs: null scratch");
-    static const float dummy = 0.0f;            // dw / db are not touched in this form (the kernel only needs db != NULL for the bias sums)
-    return wgrad_impl(d, x0, x1, dy, const_cast<float*>(&dummy), const_cast<float*>(&dummy), scratch, scratch_bytes, nullptr, stream, 1);
+    return wgrad_impl(d, x0, x1, dy, WgradRequest{nullptr, nullptr, scratch, scratch_bytes, REQ_SLABS}, stream);      // (dw / db are not touched)
 }
 
-extern "C" int colvo_conv_wgrad_splits(const ColvoConvDesc* d) {
-    if (!d || check_desc(d, "colvo_conv_wgrad_splits")) return 0;
-    int nsplit = 0;
-    static const char dummy = 0;
-    if (wgrad_impl(d, &dummy, d->C1 ? &dummy : nullptr, &dummy, (float*)&dummy, nullptr, nullptr, 0, &nsplit, nullptr)) return 0;
-    return nsplit;
-}
+extern "C" int colvo_conv_wgrad_splits(const ColvoConvDesc* d) { return wgrad_max_splits(d, "colvo_conv_wgrad_splits"); }
 
 extern "C" int colvo_wgrad_reduce_group(const ColvoWgradSlabs* sets, int n, colvo_stream_t stream) {
     COLVO_CHECK_ARG(sets && n >= 1 && n <= COLVO_WGRAD_GROUP_MAX, "colvo_wgrad_reduce_group: 1..%d sets", COLVO_WGRAD_GROUP_MAX);
@@ -1169,66 +1237,7 @@ extern "C" int colvo_wgrad_reduce_group(const ColvoWgradSlabs* sets, int n, colv
 }
 
 extern "C" size_t colvo_conv_wgrad_scratch_bytes(const ColvoConvDesc* d) {
-    if (!d || check_desc(d, "colvo_conv_wgrad_scratch_bytes")) return 0;
-    // the launch planner itself, in plan-only mode (no HIP call, no pointer is dereferenced); a batch the call would slice
-    // (tensors >= 1 GiB) is planned per slice, every slice re-using the same scratch
-    int nsplit = 0;
-    static const char dummy = 0;
-    if (wgrad_impl(d, &dummy, d->C1 ? &dummy : nullptr, &dummy, (float*)&dummy, nullptr, nullptr, 0, &nsplit, nullptr)) return 0;
-    return (size_t)nsplit * ((size_t)d->Cout * 9 * (d->C0 + d->C1) + d->Cout) * 4;
-}
-
-static int wgrad_impl(const ColvoConvDesc* d, const void* x0, const void* x1, const void* dy, float* dw, float* db,
-                      void* scratch, size_t scratch_bytes, int* plan_out, colvo_stream_t stream, int slabs_only, int clean) {
-    if (int e = check_desc(d, "colvo_conv_wgrad")) return e;
-    COLVO_CHECK_ARG(x0 && dy && dw && (d->C1 == 0 || x1), "colvo_conv_wgrad: null pointer argument");
-    // The kernel addresses dY and the sources with 32-bit buffer offsets (< 1 GiB per tensor): larger batches are
-    // processed in image slices -- the gradient accumulates into dw / db anyway.
-    {
-        const long long es = d->dtype == COLVO_F32 ? 4 : 2;
-        const long long cmax = d->C0 > d->C1 ? d->C0 : d->C1;
-        const long long per_img = std::max((long long)d->Ho * d->Wo * d->Cout, (long long)d->Hi * d->Wi * cmax) * es;
-        COLVO_CHECK_ARG(per_img < 0x40000000LL, "colvo_conv_wgrad: a single image of %lld bytes is not supported", per_img);
-        const int bmax = (int)std::max(1LL, (0x40000000LL - 1) / per_img);
-        if (d->B > bmax) {
-            if (!plan_out) form_hit(FORM_WGRAD_SLICED);
-            COLVO_CHECK_ARG(!slabs_only, "colvo_conv_wgrad_slabs: batch %d would be sliced (tensors >= 1 GiB); use colvo_conv_wgrad_det", d->B);
-            const long long e0 = (long long)(d->up0 ? (d->Hi / 2) * (d->Wi / 2) : d->Hi * d->Wi) * d->C0 * es;
-            const long long e1 = (long long)(d->up1 ? (d->Hi / 2) * (d->Wi / 2) : d->Hi * d->Wi) * d->C1 * es;
-            const long long ey = (long long)d->Ho * d->Wo * d->Cout * es;
-            for (int b0 = 0; b0 < d->B; b0 += bmax) {
-                ColvoConvDesc sub = *d;
-                sub.B = std::min(bmax, d->B - b0);
-                int plan = 0;
-                if (int e = wgrad_impl(&sub, (const char*)x0 + b0 * e0, x1 ? (const char*)x1 + b0 * e1 : nullptr,
-                                       (const char*)dy + b0 * ey, dw, db, scratch, scratch_bytes, plan_out ? &plan : nullptr, stream, 0,
-                                       b0 == 0 ? clean : 0))        // (only the first slice finds the arena clean)
-                    return e;
-                if (plan_out) *plan_out = std::max(*plan_out, plan);
-            }
-            return 0;
-        }
-    }
-    WgradK k{};
-    fill_gather(d, x0, d->C1 ? x1 : nullptr, k.g);
-    k.Ho = d->Ho; k.Wo = d->Wo; k.B = d->B;
-    k.dy = (const char*)dy; k.Cout = d->Cout; k.dw = dw; k.Ctot = d->C0 + d->C1; k.db = db;
-    k.scratch = (const char*)scratch; k.scratch_bytes = scratch ? (long long)scratch_bytes : 0; k.plan_out = plan_out;
-    k.slabs_only = slabs_only;
-    k.clean = clean;
-    WgradPlan p{};
-    if (int e = d->dtype == COLVO_F32 ? wgrad_plan<float>(d, k, p) : wgrad_plan<bf16_t>(d, k, p)) return e;
-    { int err; if (wgrad_prepare(k, p.nsplit, &err)) return err; }
-    const hipStream_t s = (hipStream_t)stream;
-    if (p.form == WGRAD_RT) {
-        form_hit(FORM_WGRAD_RT);
-        if (int e = wgrad_rt_launch(p.rt, d, x0, d->C1 ? x1 : nullptr, dy, dw, db, k.slabs, k.db_slabs, k.det, s)) return e;
-    } else {
-        form_hit(p.form == WGRAD_UP2 ? FORM_WGRAD_UP2 : p.form == WGRAD_TEAMS ? FORM_WGRAD_TEAMS : FORM_WGRAD_TAIL);
-        if (p.form == WGRAD_TAIL && p.mt == 4) form_hit(FORM_WGRAD_MT4);
-        form_hit(p.halved ? FORM_WGRAD_HALVED_GRID : FORM_WGRAD_FULL_GRID);
-        if (k.det == 2) form_hit(FORM_WGRAD_STORE_CLEAN);
-        if (int e = d->dtype == COLVO_F32 ? launch_wgrad_t<float>(k, p, s) : launch_wgrad_t<bf16_t>(k, p, s)) return e;
-    }
-    return wgrad_finish(k, p.nsplit, s);
+    // a batch the call would slice (tensors >= 1 GiB) is planned per slice, every slice re-using the same scratch
+    const int nsplit = wgrad_max_splits(d, "colvo_conv_wgrad_scratch_bytes");
+    return nsplit ? (size_t)nsplit * ((size_t)d->Cout * 9 * (d->C0 + d->C1) + d->Cout) * 4 : 0;
 }

@@ -63,11 +63,8 @@ constexpr int WR_TAB_BYTES = 4096;                            // K-step address 
 struct WgradRtK {
     const char* dy;           // [B][Ho][Wo][Cout] bf16
     const char* src[2];       // stored sources, bf16 NHWC
-    float* dw;                // [Cout][9][Ctot]
-    float* db;
-    float* slabs;             // deterministic form: [nsplit][Cout * 9 * Ctot]; null: atomics / det
-    float* db_slabs;
-    int B, Ho, Wo, Cout, Ctot;
+    WgradSink out;            // dw [Cout][9][Ctot] / db, as for k_wgrad3x3
+    int B, Ho, Wo, Cout;
     int C[2], Hs[2], Ws[2], sh[2];     // per source: channels, stored extent, 1 = stored at half size (nearest-2x up-sampled)
     int nci0, nci, nco;                // 32-channel ci tiles of source 0 / of both sources, co tiles
     int ni, toh, tow;                  // tile = ni whole images (ni > 1: toh x tow is the image) or toh x tow pixels of one image
@@ -75,7 +72,6 @@ struct WgradRtK {
     int pwl, pimg, xinstr;             // LDS patch row pitch / image pitch in pixels, DMA instructions of the patch
     int tiles_x, tiles_y, ntiles, tiles_per_split, nsplit;
     uint32_t m_tow, m_npix1, m_pwl, m_pimg;
-    int det;                           // as WgradK.det
     int xcd;
     int buf_bytes;                     // one staging buffer: (ksteps + xinstr) KiB
     int tab_off;                       // LDS offset of the K-step address table (behind the two staging buffers)
@@ -173,7 +169,7 @@ __global__ __launch_bounds__(WR_NT) void k_wgrad_rt(const WgradRtK a) {
     float dbacc = 0.0f;                                    // consumer lane (co = lane & 31, K half h): sum of its dY fragment elements
     // bias gradient: by the consumers of the workgroups of ci tile 0, from the dY fragments they hold anyway (v_dot2c_f32_bf16 with
     // a pair of ones: four instructions per K-step)
-    const bool db_on = a.db != nullptr && bci == 0 && !(COLVO_RT_VARIANT & 8);
+    const bool db_on = a.out.bias && bci == 0 && !(COLVO_RT_VARIANT & 8);
 
     // ---- ring of a.nbuf staging buffers: tile t is computed from buffer (t - t_begin) mod nbuf while the DMA of the next nbuf - 1 tiles
     // is in flight.  Every loader issues the same number of DMA instructions per tile, in tile order, so "my share of tile t has
@@ -416,7 +412,7 @@ __global__ __launch_bounds__(WR_NT) void k_wgrad_rt(const WgradRtK a) {
     // rows co = (c & 3) * 8 + 4 h + e, column ci = lane & 31), lane-major 16-byte stores; then wave w -- loaders too -- sums the four
     // copies of the chunks w, w + 8, ... in a fixed order and flushes them: one register = two 128-byte row segments of dw
     f32x4* sEx = reinterpret_cast<f32x4*>(smem);
-    const size_t wsize = (size_t)a.Cout * 9 * a.Ctot;
+    const size_t wsize = (size_t)a.Cout * 9 * a.out.Ctot;
     const int ci = lane & 31;
     const bool civ = c0 + ci < Cs;
     __syncthreads();                                       // the staging buffers are free
@@ -437,32 +433,13 @@ __global__ __launch_bounds__(WR_NT) void k_wgrad_rt(const WgradRtK a) {
         for (int w = 1; w < WR_CONS; ++w) t += v[w];
         const int tap = c >> 2, qd = c & 3;
         const int corow = co0 + 8 * qd + 4 * h;
-        const size_t e0 = ((size_t)corow * 9 + tap) * a.Ctot + wc0 + ci;
-        const size_t erow = (size_t)9 * a.Ctot;
+        const size_t e0 = ((size_t)corow * 9 + tap) * a.out.Ctot + wc0 + ci;
+        const size_t erow = (size_t)9 * a.out.Ctot;
         const int nrow = civ ? min(4, a.Cout - corow) : 0;                 // rows of this lane inside the tensor (<= 0: none)
-        if (a.slabs) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (e < nrow) a.slabs[(size_t)bsplit * wsize + e0 + e * erow] = t[e];
-        } else if (a.det == 2) {                           // one split, arena known to be zero: plain stores
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (e < nrow) a.dw[e0 + e * erow] = t[e];
-        } else if (a.det) {                                // one split = sole writer: plain read-modify-write, loads first
-            float old[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) old[e] = e < nrow ? a.dw[e0 + e * erow] : 0.0f;
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (e < nrow) a.dw[e0 + e * erow] = old[e] + t[e];
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (e < nrow) atomicAdd(a.dw + e0 + e * erow, t[e]);
-        }
+        wgrad_put_rows(a.out, bsplit, wsize, e0, erow, nrow, t);
     }
     WT(wt_ex);
-    if (a.db != nullptr && bci == 0) {                     // (wave-uniform: bci is the workgroup's)
+    if (a.out.bias && bci == 0) {                          // (wave-uniform: bci is the workgroup's)
         __syncthreads();
         float* sdb = reinterpret_cast<float*>(smem);
         if (!loader) sdb[tid] = dbacc;                     // [consumer][K half][co]
@@ -471,10 +448,7 @@ __global__ __launch_bounds__(WR_NT) void k_wgrad_rt(const WgradRtK a) {
             float t = 0.0f;
 #pragma unroll
             for (int j = 0; j < 2 * WR_CONS; ++j) t += sdb[j * 32 + tid];
-            if (a.db_slabs) a.db_slabs[(size_t)bsplit * a.Cout + co0 + tid] = t;
-            else if (a.det == 2) a.db[co0 + tid] = t;
-            else if (a.det) a.db[co0 + tid] += t;
-            else atomicAdd(a.db + co0 + tid, t);
+            wgrad_put_bias(a.out, bsplit, a.Cout, co0, tid, t);
         }
     }
 #ifdef COLVO_WTRACE
@@ -570,12 +544,12 @@ bool wgrad_rt_plan(const ColvoConvDesc* d, WgradRtPlan& p) {
     return true;
 }
 
-int wgrad_rt_launch(const WgradRtPlan& p, const ColvoConvDesc* d, const void* x0, const void* x1, const void* dy, float* dw, float* db,
-                    float* slabs, float* db_slabs, int det, hipStream_t s) {
+int wgrad_rt_launch(const WgradRtPlan& p, const ColvoConvDesc* d, const void* x0, const void* x1, const void* dy, const WgradSink& out,
+                    hipStream_t s) {
     WgradRtK k{};
     k.dy = (const char*)dy; k.src[0] = (const char*)x0; k.src[1] = d->C1 ? (const char*)x1 : nullptr;
-    k.dw = dw; k.db = db; k.slabs = slabs; k.db_slabs = db_slabs;
-    k.B = d->B; k.Ho = d->Ho; k.Wo = d->Wo; k.Cout = d->Cout; k.Ctot = d->C0 + d->C1;
+    k.out = out;
+    k.B = d->B; k.Ho = d->Ho; k.Wo = d->Wo; k.Cout = d->Cout;
     k.C[0] = d->C0; k.C[1] = d->C1;
     k.sh[0] = d->up0 ? 1 : 0; k.sh[1] = d->up1 ? 1 : 0;
     k.Hs[0] = d->up0 ? d->Hi / 2 : d->Hi; k.Ws[0] = d->up0 ? d->Wi / 2 : d->Wi;
@@ -585,7 +559,7 @@ int wgrad_rt_launch(const WgradRtPlan& p, const ColvoConvDesc* d, const void* x0
     k.pwl = p.pwl; k.pimg = p.pimg; k.xinstr = p.xinstr;
     k.tiles_x = p.tiles_x; k.tiles_y = p.tiles_y; k.ntiles = p.ntiles; k.tiles_per_split = p.tiles_per_split; k.nsplit = p.nsplit;
     k.m_tow = mdiv20_magic(p.tow); k.m_npix1 = mdiv20_magic(std::max(2, k.npix1)); k.m_pwl = mdiv20_magic(p.pwl); k.m_pimg = mdiv20_magic(p.pimg);
-    k.det = det; k.xcd = (int)TUNE(xcd_remap);
+    k.xcd = (int)TUNE(xcd_remap);
     k.buf_bytes = (p.ksteps + p.xinstr) * 1024;
     k.tab_off = 2 * k.buf_bytes;
     COLVO_CHECK_ARG(p.ksteps <= WR_LOAD * WR_MAXY && p.xinstr <= WR_LOAD * WR_MAXX && p.tow >= 2, "wgrad_rt: bad tile plan");

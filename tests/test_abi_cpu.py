@@ -188,6 +188,24 @@ def test_wgrad_plan_queries_have_no_side_effects(lib):
         assert _lib.form_counts() == before, name
         n += 1
     assert n == 2 * 4 * (20 + 7)
+    # a batch the call would process in image slices (a tensor of 1 GiB or more): the query is the largest of the slices' own
+    # queries -- every slice re-uses the same scratch -- and still counts nothing, not even wgrad_sliced
+    from coivo_amd import ops
+    for dt, es in ((torch.float32, 4), (torch.bfloat16, 2)):
+        per_img = 256 * 320 * 32 * es                       # enc1b at 256x320
+        bmax = (2 ** 30 - 1) // per_img
+        d = ops.conv_desc(dt, 2 * bmax + 3, 256, 320, 32, 32)
+        assert d.B * per_img >= 2 ** 30
+        before = _lib.form_counts()
+        splits = lib.colvo_conv_wgrad_splits(C.byref(d))
+        scratch = lib.colvo_conv_wgrad_scratch_bytes(C.byref(d))
+        assert _lib.form_counts() == before, dt
+        per_slice = []
+        for b in (bmax, bmax, 3):                           # the sub-batches the call walks
+            sub = ops.conv_desc(dt, b, 256, 320, 32, 32)
+            per_slice.append(lib.colvo_conv_wgrad_splits(C.byref(sub)))
+        assert min(per_slice) >= 1 and splits == max(per_slice), (dt, splits, per_slice)
+        assert scratch == splits * (d.Cout * 9 * (d.C0 + d.C1) + d.Cout) * 4, dt
 
 
 def test_every_command_reaches_its_entry_point(lib):
