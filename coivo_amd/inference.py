@@ -243,12 +243,27 @@ def write_ply(path, points: torch.Tensor, colors: Optional[torch.Tensor] = None)
         f.write(rows.tobytes())
 
 
-class Reconstruction(NamedTuple):
+class _ReconstructionFields(NamedTuple):
     depths: torch.Tensor        # [N+1,1,H,W]
     rel_poses: torch.Tensor     # [N,6]    frame k -> frame k+1
     cam2world: torch.Tensor     # [N+1,4,4] float64, CPU
     points: torch.Tensor        # [M,3]    world frame (camera 0)
     fused: Optional[FusedCloud] = None   # with voxel_size: the coloured, voxel-averaged cloud
+
+
+class Reconstruction(_ReconstructionFields):
+    """The five fields above -- it still unpacks into five -- and, behind them, `polyps`: with labels the PolypLocalization
+    of the same depths and trajectory (coivo_amd.localize), else None."""
+    polyps = None               # Optional[PolypLocalization]
+
+    def __new__(cls, depths, rel_poses, cam2world, points, fused=None, polyps=None):
+        self = super().__new__(cls, depths, rel_poses, cam2world, points, fused)
+        self.polyps = polyps
+        return self
+
+    def _replace(self, **kw):
+        polyps = kw.pop("polyps", self.polyps)
+        return type(self)(*super()._replace(**kw), polyps=polyps)
 
 
 @torch.no_grad()
@@ -269,13 +284,18 @@ def run_networks(depth_net, pose_net, frames: torch.Tensor, *, chunk: int = 16):
 @torch.no_grad()
 def reconstruct_sequence(depth_net, pose_net, frames: torch.Tensor, K: torch.Tensor, *, stride: int = 4,
                          max_depth: float = MAX_DEPTH, chunk: int = 16, voxel_size: Optional[float] = None,
-                         min_obs: int = 1) -> Reconstruction:
+                         min_obs: int = 1, labels: Optional[torch.Tensor] = None,
+                         num_labels: Optional[int] = None) -> Reconstruction:
     """frames [N+1,3,H,W] of one sequence, K [3,3] or [N+1,3,3] -> depth of every frame, the pose of every consecutive
     pair (DCDP: PoseNet sees both depth maps), the integrated trajectory and the stitched cloud.  With a voxel_size also
-    the fused cloud of the same samples, coloured by the frames (fuse_point_cloud; `fused`, else None)."""
+    the fused cloud of the same samples, coloured by the frames (fuse_point_cloud; `fused`, else None).  With labels
+    [N+1,1,H,W] uint8 and num_labels also the polyps they mark, localised from the same depths, K, trajectory and max_depth at
+    stride 1 (localize.localize_polyps; `polyps`, else None)."""
     n = frames.shape[0]
     if n < 2:
         raise ValueError("reconstruct_sequence: need at least two frames")
+    if labels is not None and num_labels is None:
+        raise ValueError("reconstruct_sequence: labels need num_labels")
     if K.dim() == 2:
         K = K.unsqueeze(0).expand(n, 3, 3)
     K = K.to(frames.device, torch.float32).contiguous()
@@ -287,4 +307,8 @@ def reconstruct_sequence(depth_net, pose_net, frames: torch.Tensor, K: torch.Ten
     if voxel_size is not None:
         fused = fuse_point_cloud(depths, K, traj32, voxel_size=voxel_size, colors=frames.to(torch.float32).contiguous(),
                                  stride=stride, max_depth=max_depth, min_obs=min_obs)
-    return Reconstruction(depths, rel, traj, cloud, fused)
+    polyps = None
+    if labels is not None:
+        from . import localize                       # (localize imports this module)
+        polyps = localize.localize_polyps(depths, labels, K, traj32, num_labels=num_labels, stride=1, max_depth=max_depth)
+    return Reconstruction(depths, rel, traj, cloud, fused, polyps)

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define COLVO_ABI_VERSION 13
+#define COLVO_ABI_VERSION 14
 
 typedef void* colvo_stream_t; /* hipStream_t */
 
@@ -465,6 +465,50 @@ int colvo_fuse_count(const void* pool, int n_bricks, int min_obs, void* extract_
 int colvo_fuse_write(const void* workspace, const void* pool, int n_bricks, int min_obs, float ox, float oy, float oz,
                      float voxel_size, int nx, int ny, int nz, const void* extract_ws, int n_rows, float* points, float* colors,
                      int32_t* counts, int32_t* voxels, colvo_stream_t stream);
+
+/* Polyp localisation: labelled pixels + depth maps + trajectory -> where each polyp lies, in the camera frame of
+ * every frame that shows it and in the world frame, and how large it is.  labels [N,1,H,W] uint8: 0 background, 1..num_labels a
+ * polyp id (the same polyp in every frame: association is the detector's or tracker's job), anything above num_labels is ignored
+ * and counted.  The walked pixels are colvo_stitch_point_cloud's: (u, v) = (i * stride, j * stride).  A labelled pixel of (n, l) is
+ * a walked pixel of frame n carrying label l; a sample is a labelled pixel with 0 < d < max_depth (NaN falls out) that, with clip
+ * bounds, also passes the clip test below.
+ * Pinned arithmetic, float32, every operation individually rounded (no FMA contraction):
+ *   px = ((u - cx) / fx) * d, py = ((v - cy) / fy) * d, pz = d;  q_a = (int32) rintf(p_a * 4096.0f).
+ * A record (128 bytes, 16 words of 64 bits) per (n, l), integers only: labelled pixels, samples, sum u, sum v over the samples,
+ * sum q_x, q_y, q_z (signed), sum q_a q_b in the order xx, xy, xz, yy, yz, zz (signed), the inclusive bounding box of the
+ * labelled pixels.  Added with 64-bit integer adds and 32-bit integer max: bit-identical between calls and streams.  The caller
+ * guarantees |p_a| * 4096 < 2^31 and (|p_a| * 4096)^2 * ceil(H/stride) * ceil(W/stride) < 2^62 (localize.py checks both from K and
+ * max_depth before any launch).
+ *   workspace   colvo_localize_workspace_bytes(N, num_labels) bytes: the records [N][num_labels], then one ignored-pixel count per
+ *               frame.  0 for what the calls refuse.
+ *   accumulate  clears the workspace and adds every labelled pixel and sample.  clip_bounds: NULL, or [N][num_labels][2] doubles
+ *               (mean_z, limit) from colvo_localize_bounds: a sample must then satisfy, in float64,
+ *               (double(q_z) / 4096.0 - mean_z)^2 <= limit.  Labelled-pixel counts and boxes do not depend on the clip.
+ *   bounds      per (n, l) with n = samples >= 2: mean_z = double(sum q_z) / (4096.0 * double(n)),
+ *               var_z = max(0, double(sum q_z q_z) / (16777216.0 * double(n)) - mean_z * mean_z),
+ *               limit = (double(clip_sigma) * double(clip_sigma)) * var_z; with n < 2: mean_z = 0, limit = +inf (nothing is clipped).
+ *   finish      per (n, l), float64, n = n_samples[n][l], everything NaN where n = 0:
+ *                 bbox = (u0, v0, u1, v1), -1 where n_pixels = 0;  pixel = (double(sum u) / double(n), double(sum v) / double(n));
+ *                 m_a = center_cam[a] = double(sum q_a) / (4096.0 * double(n));
+ *                 cov_cam[ab] = double(sum q_a q_b) / (16777216.0 * double(n)) - m_a * m_b   (order xx, xy, xz, yy, yz, zz);
+ *                 center_world[a] = ((r_a0 * m_x + r_a1 * m_y) + r_a2 * m_z) + t_a   (cam2world's float32 entries widened).
+ *               per label l, over the frames with n >= min_samples in ascending frame order (a frame below it is skipped), with
+ *               C the symmetric cov_cam, c = center_world, T_ab = (r_a0 * C_0b + r_a1 * C_1b) + r_a2 * C_2b,
+ *               S_ab = ((T_a0 * r_b0 + T_a1 * r_b1) + T_a2 * r_b2) + c_a * c_b:
+ *                 n_frames, n_samples_total = sum n (integers), first_frame, last_frame (-1 if never seen);
+ *                 position[a] = p_a = (sum_n double(n) * c_a) / double(n_samples_total);
+ *                 cov_world[ab] = (sum_n double(n) * S_ab) / double(n_samples_total) - p_a * p_b;  NaN if never seen.
+ *               stats (device int64[2]): labelled pixels, ignored pixels (label above num_labels), over all frames.
+ * Limits: N <= 65535, H*W < 2^30, num_labels in 1..255, stride >= 1, max_depth finite and positive, clip_sigma finite and not
+ * negative, min_samples >= 1; records and clip_bounds 16-byte aligned. */
+size_t colvo_localize_workspace_bytes(int N, int num_labels);
+int colvo_localize_accumulate(const float* depths, const uint8_t* labels, const float* K, int N, int H, int W, int stride,
+                              float max_depth, int num_labels, const double* clip_bounds, void* records, colvo_stream_t stream);
+int colvo_localize_bounds(const void* records, int N, int num_labels, float clip_sigma, double* clip_bounds, colvo_stream_t stream);
+int colvo_localize_finish(const void* records, const float* cam2world, int N, int num_labels, int min_samples, int32_t* n_pixels,
+                          int32_t* n_samples, int32_t* bbox, double* pixel, double* center_cam, double* cov_cam,
+                          double* center_world, int32_t* n_frames, int64_t* n_samples_total, int32_t* first_frame,
+                          int32_t* last_frame, double* position, double* cov_world, int64_t* stats, colvo_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------- *
  * SURVEY.md §6  evaluation: depth error measures with per-image median scaling. *
