@@ -13,18 +13,10 @@ atomic flush or a fork that lets a weight gradient read its dy early moves a lay
 (bench.py times its networks with deterministic weight gradients, so that two runs compute the same thing; the form held here is
 the library's default, the one a train loop runs.)"""
 import pytest
-import torch
 
-from coivo_amd import synth
-from tests.gpu_util import bf16_rounded_state, hip_relu_masks, oracle_step_bf16, to_dev
+from tests.gpu_util import K_NOISE, assert_bf16_step_at_the_noise_level, bf16_hip_step  # noqa: F401  (K_NOISE: the bar's factor)
 
 pytestmark = pytest.mark.gpu
-
-K_NOISE = 3.0
-
-
-def _rel(a, b):
-    return (a - b).norm().item() / max(b.norm().item(), 1e-30)
 
 
 # (8, 256, 320) = BASELINE configs[1]; (32, 256, 320) = the per-GPU shape of configs[3], where the forms that are selected by GRID SIZE
@@ -33,23 +25,9 @@ def _rel(a, b):
 # none of them is reached; at these shapes it was judged by cosines and a 1e-2 depth bar).
 @pytest.mark.parametrize("B,H,W,seed", [(2, 64, 96, 71), (1, 96, 128, 72), (8, 256, 320, 73), (32, 256, 320, 74)])
 def test_benchmarked_bf16_backward_against_the_oracle_at_the_bf16_noise_level(B, H, W, seed):
-    from coivo_amd import _lib, nn as hnn
-    from oracle import colvo_spec as S
-    b = synth.make_batch(B, H, W, seed=seed)
-    d = to_dev(b)
-    dn_o, pn_o = S.make_models(seed)
-    dn, pn = hnn.DepthNet(compute_dtype=torch.bfloat16), hnn.PoseNet(compute_dtype=torch.bfloat16)
-    dn.load_state_dict(bf16_rounded_state(dn_o))
-    pn.load_state_dict(bf16_rounded_state(pn_o))
-    dn.deterministic = pn.deterministic = False            # the default form (float atomics), whatever COLVO_DETERMINISTIC says
-    dn.zero_grad(); pn.zero_grad()
-    _lib.form_counts(reset=True)
-    loss, d_t, d_r, pose, a, bb = hnn.dcdp_forward(dn, pn, d["tgt"], d["ref"], d["K"])     # the fast path of bench.py
-    loss.backward()
-    dn.join_side(); pn.join_side()
-    torch.cuda.synchronize()
-    forms = _lib.form_counts()
-    print(f"kernel forms of this step: {forms}")
+    from coivo_amd import _lib
+    step = bf16_hip_step(B, H, W, seed)
+    forms, ops_recorded = step["forms"], step["ops_recorded"]
     # what the dispatchers chose (include/colvo.h colvo_form_counts): production thresholds, nothing lowered for the test
     assert forms["wgrad_rt"] == 0
     if B >= 8:
@@ -59,47 +37,14 @@ def test_benchmarked_bf16_backward_against_the_oracle_at_the_bf16_noise_level(B,
         assert forms["wgrad_store_clean"] == 4 and forms["conv_res_s2"] >= 1, forms
     if B == 32:             # configs[3] per GPU: the register-tiled kernel on seven launches, ten full weight-gradient grids beside sixteen halved
         assert forms["conv_rt"] >= 7 and forms["wgrad_full_grid"] >= 10 and forms["wgrad_halved_grid"] >= 1, forms
-    # this IS the benchmarked backward: the fused full-resolution kernel in its HEAD form and recorded forks
-    bwd = [pr for which, (pr, _) in next(iter(dn._insts.values()))[-1].passes.items() if which.startswith("bwd")]
-    assert len(bwd) == 1
-    ops_recorded = [bwd[0]._arr[i].op for i in range(len(bwd[0]))]
     assert _lib.CMD_CONV_BWD_FUSED in ops_recorded and _lib.CMD_FORK in ops_recorded, ops_recorded
     assert _lib.tune_get("fork_stop_event") == 1
 
-    masks = hip_relu_masks(dn, pn)
-    o = oracle_step_bf16(seed, b, masks)                   # the target: fp32 oracle, bf16-rounded weights, HIP's ReLU decisions
-    e = oracle_step_bf16(seed, b, masks, emulate=True)     # ... with the bf16 storage points emulated: the noise scale
-    hip = [("depth." + n, p.grad) for n, p in dn.named_parameters()] + [("pose." + n, p.grad) for n, p in pn.named_parameters()]
-    # One emulated run is ONE realisation of the noise.  PoseNet's tensors all carry the error of the same eight numbers (d pose,
-    # d a, d b: sums over the image in which a handful of validity flips at the border weigh in), so their distance is one shared
-    # random factor -- seen at B=1 96x128: 2.3-3.2e-2 on every PoseNet tensor against 0.5-0.8e-2 in the emulated run and 1.2-2e-2
-    # on DepthNet's tensors of both.  The scale is therefore the tensor's own emulated distance or the step's typical one (the
-    # median over all 58 tensors), whichever is larger.
-    rows = [(n, _rel(gh.detach().float().cpu(), go), _rel(ge, go)) for (n, gh), (_, go), (_, ge) in zip(hip, o["grads"], e["grads"])]
-    typical = sorted(le for _, _, le in rows)[len(rows) // 2]
-    bad, worst = [], 0.0
-    for n, lh, le in rows:
-        scale = max(le, typical)
-        worst = max(worst, lh / scale)
-        if lh > K_NOISE * scale:
-            bad.append(f"{n}: relL2 hip {lh:.3e} vs emulated bf16 data path {le:.3e} (typical {typical:.3e})")
-    print(f"bf16 backward vs oracle: worst hip / noise ratio {worst:.2f} over {len(hip)} tensors")
+    # (tests/gpu_util.py: the body this test had, shared with tests/test_step_shapes_gpu.py; here the oracle stays on the CPU, whole)
     import os
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     if os.path.isdir(os.path.join(root, "gpurun_out")):
         with open(os.path.join(root, "gpurun_out", f"bf16_step_parity_b{B}_{H}x{W}.txt"), "w") as f:
-            f.write("param relL2_hip_vs_oracle relL2_emulated_bf16_vs_oracle\n")
-            for (n, gh), (_, go), (_, ge) in zip(hip, o["grads"], e["grads"]):
-                f.write(f"{n} {_rel(gh.detach().float().cpu(), go):.3e} {_rel(ge, go):.3e}\n")
-            f.write(f"loss hip {loss.item():.7f} oracle {o['loss']:.7f} emulated {e['loss']:.7f}\n")
-    assert len(hip) == 58 and not bad, "\n".join(bad)
-    # forward quantities on the same scale
-    # (the loss is ONE number: the emulated run's distance is one draw of a zero-mean quantity and can be anything down to nothing --
-    #  4.8e-7 at 32 pairs, where HIP's is 1.7e-5 with all 58 gradient tensors inside their bars -- so the floor is absolute: 5e-5, a sixth
-    #  of the bf16 loss bar of tests/test_config1_gpu.py)
-    dl_h, dl_e = abs(loss.item() - o["loss"]), abs(e["loss"] - o["loss"])
-    assert dl_h <= K_NOISE * dl_e + 5e-5, (loss.item(), o["loss"], e["loss"])
-    for th, key in ((d_t, "d_t"), (d_r, "d_r")):
-        eh = (th.detach().cpu() - o[key]).abs().mean().item()
-        ee = (e[key] - o[key]).abs().mean().item()
-        assert eh <= K_NOISE * ee, (key, eh, ee)
+            assert_bf16_step_at_the_noise_level(step, seed, table=f)
+    else:
+        assert_bf16_step_at_the_noise_level(step, seed)

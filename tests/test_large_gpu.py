@@ -1,4 +1,5 @@
-"""-m gpu: BASELINE configs[2] size (B=32, 640x512) end to end -- the whole step runs, stays finite, and the sliced
+"""-m gpu: BASELINE configs[2] size (B=32, 640x512) end to end -- the whole step runs, stays finite, selects the kernel forms
+that tests/test_step_shapes_gpu.py holds to the float64 oracle at this resolution, and the sliced
 wgrad path (tensors >= 1 GiB in fp32) equals the unsliced one."""
 import pytest
 import torch
@@ -10,8 +11,9 @@ pytestmark = pytest.mark.gpu
 
 
 def test_config2_full_step_bf16():
-    from coivo_amd import nn as hnn
+    from coivo_amd import _lib, nn as hnn
     from coivo_amd.optim import FusedAdam
+    from tests.test_step_shapes_gpu import FORMS, selected
     B, H, W = 32, 512, 640
     d = dev()
     dn, pn = hnn.DepthNet(compute_dtype=torch.bfloat16), hnn.PoseNet(compute_dtype=torch.bfloat16)
@@ -26,6 +28,7 @@ def test_config2_full_step_bf16():
     tgt, ref, K = rep(b["tgt"]), rep(b["ref"]), rep(b["K"])
     opt = FusedAdam([dn, pn], lr=1e-4)
     losses = []
+    _lib.form_counts(reset=True)
     for _ in range(2):
         opt.zero_grad()
         loss = hnn.dcdp_forward(dn, pn, tgt, ref, K)[0]
@@ -35,6 +38,11 @@ def test_config2_full_step_bf16():
     assert all(0 < l < 1 for l in losses)
     assert torch.isfinite(dn.flat_grad).all() and torch.isfinite(pn.flat_grad).all()
     assert dn.flat_grad.abs().max() > 0
+    # the kernel forms these 32 pairs select are the ones tests/test_step_shapes_gpu.py holds to the oracle, tensor by tensor, at the
+    # smallest pair count of 512x640 that selects them all
+    forms = _lib.form_counts()
+    print(f"kernel forms of configs[2]'s step: {forms}")
+    assert selected(forms) == FORMS["bf16", 512, 640], sorted(selected(forms))
 
 
 def test_wgrad_batch_slicing_matches_unsliced():
