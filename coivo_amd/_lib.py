@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("COLVO_LIB_PATH") or os.path.join(_HERE, "lib", "libcolvo.so")
 
 F32, BF16 = 0, 1
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 
@@ -34,6 +34,7 @@ class WgradSlabs(C.Structure):
                 ("Ctot", C.c_int32), ("pad_", C.c_int32)]
 
 
+AUG_ROW_FLOATS = 20               # sizeof(ColvoAugRow) / 4: oy ox sy sx flip gamma A[12] pad[2]
 WGRAD_GROUP_MAX = 16
 MAX_ARENAS = 4
 ADAM_PLAIN_PER_WG = 2048          # COLVO_ADAM_PLAIN_PER_WG
@@ -118,6 +119,7 @@ SIGNATURES = {
     "colvo_cast_f32_bf16": (_i, [_vp, _vp, _sz, _i, _vp]),
     "colvo_zero": (_i, [_vp, _sz, _vp]),
     "colvo_frames_u8_to_f32": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "colvo_frames_u8_augment": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "colvo_read_npy_u8_frames": (_i, [_vp, _i, _i, _i, _vp, _i]),
     "colvo_backproject": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "colvo_stitch_workspace_ints": (_sz, [_i, _i, _i, _i]),

@@ -8,6 +8,33 @@ pread() straight into the pinned buffer, no interpreter lock): 15-30 k pairs/s a
 the interpreter; PNG / JPEG frames are decoded by PIL on the thread pool (~1.0 k pairs/s beside a training loop) or, with
 `decoders=N`, by N worker processes writing into shared pinned staging buffers (~3 k pairs/s beside a training loop, N = 10).  One process per GPU: `rank` / `world_size` shard the pairs
 with no communication (a seeded permutation every rank computes identically).
+
+Augmentation (`PairLoader(..., augment=Augment(...))`; DESIGN.md §3.6e holds the same contract with the table layout and the
+measurements).  It is folded into the conversion pass (csrc/augment.hip: one launch, the source read once); parameters are per PAIR
+unless marked per frame.
+
+* Geometry: target and reference share it, so a pair stays one consistent (possibly mirrored) scene.  The crop rectangle is in native
+  edge coordinates (pixel i covers [i, i+1)): origin (oy, ox) and size (ch, cw) are float32 with 0 <= oy, oy + ch <= h, 0 <= ox,
+  ox + cw <= w; flip is 0 or 1.  Output pixel (y, x) reads the source at  fy = oy + (ch/H)(y + 0.5) - 0.5,
+  fx = ox + (cw/W)(x' + 0.5) - 0.5  with  x' = W-1-x  under a flip, else x.  The kernel evaluates each as ONE float32 fused
+  multiply-add, fma(step, y + 0.5, oy - 0.5) with step = float32(ch/H) -- today's kernel with oy = 0 -- clamps at 0, and takes the
+  taps y0 = min(floor(fy), h-1), y1 = min(y0+1, h-1) (likewise in x) with the bilinear weights of k_frames_u8_to_f32 (clamping the
+  taps is clamping fy to h-1: both taps are then the last row).  With oy = ox = 0, ch = h, cw = w, flip = 0 this is that kernel, term
+  for term.
+* Intrinsics: on the host in float64, stored float32; pixel centres on integers as in resize_intrinsics:
+  fx' = fx * W/cw,  cx' = (cx + 0.5 - ox) * W/cw - 0.5  (the same in y), and under a flip  cx'' = W - 1 - cx'.  resize_intrinsics is
+  the case ox = 0, cw = w; a pair that is neither cropped nor mirrored is handed to resize_intrinsics itself, so that
+  Augment.identity() gives augment=None's K bit for bit (float32 arithmetic can sit an ulp or two from the float64 result).
+* Colour: one row-major 3x4 float32 matrix A per FRAME on the resized RGB in [0,1]:  out_c = clamp(A[c][0] r + A[c][1] g +
+  A[c][2] b + A[c][3], 0, 1), then  out_c = out_c ** gamma  when gamma != 1.  The host composes A in float64 from, in this order and
+  shared by the pair: a brightness gain, contrast about MID-GREY 0.5, saturation about the pixel's own luma (0.299 / 0.587 / 0.114),
+  hue as a rotation about the grey axis; then, drawn independently for target and reference, an illumination gain a_f and offset b_f
+  (the synthetic generator's ranges): what LCC has to calibrate.  The fixed mid-grey pivot instead of the image mean is deliberate:
+  the colour step stays a per-pixel map -- no reduction pass, no host sync.
+* Sampling: one zoom s in [1, max_zoom] gives ch = h/s, cw = w/s; the origin is uniform in the slack, on a 1/64-pixel grid.
+  Augment.params(seed, epoch, index, hw) is a PURE function of its arguments: a counter-based generator (numpy's Philox) keyed on
+  (seed, epoch) with the dataset pair index as its counter -- no stream shared between pairs, so the draw of a pair does not depend on
+  rank, world size, batch size or composition, prefetch, workers or thread order.  set_epoch() changes the draws.
 """
 from __future__ import annotations
 
@@ -16,7 +43,9 @@ import os
 import queue
 import subprocess
 import sys
+import threading
 from concurrent.futures import ThreadPoolExecutor
+import math
 from typing import Dict, Iterator, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -45,6 +74,227 @@ def resize_intrinsics(K: torch.Tensor, hw_from: Tuple[int, int], hw_to: Tuple[in
     K2[..., 0, 2] = (K[..., 0, 2] + 0.5) * sx - 0.5
     K2[..., 1, 2] = (K[..., 1, 2] + 0.5) * sy - 0.5
     return K2
+
+
+# ---- augmentation: seeded per-pair parameters (host) for csrc/augment.hip ----------------------------------------------------- #
+LUMA = (0.299, 0.587, 0.114)
+IDENTITY_A = np.concatenate([np.eye(3), np.zeros((3, 1))], axis=1).astype(np.float32)
+
+
+def _f32(v) -> float:
+    """v rounded to float32, as a Python float."""
+    return float(np.float32(v))
+
+
+class FrameAug:
+    """What ONE frame's row of the kernel's table is made from: crop origin / size (float32 values, native edge coordinates), flip,
+    gamma (float32 value), and the 3x4 colour matrix A (float32)."""
+    __slots__ = ("oy", "ox", "ch", "cw", "flip", "gamma", "A")
+
+    def __init__(self, oy=0.0, ox=0.0, ch=0.0, cw=0.0, flip=0, gamma=1.0, A=IDENTITY_A):
+        self.oy, self.ox, self.ch, self.cw, self.gamma = _f32(oy), _f32(ox), _f32(ch), _f32(cw), _f32(gamma)
+        self.flip = int(flip)
+        self.A = np.asarray(A, dtype=np.float32).reshape(3, 4)
+
+    @classmethod
+    def _of(cls, rec: "AugRecord", A: np.ndarray) -> "FrameAug":
+        """The frame of a pair's record: its values are float32 values already."""
+        f = cls.__new__(cls)
+        f.oy, f.ox, f.ch, f.cw, f.flip, f.gamma, f.A = rec.oy, rec.ox, rec.ch, rec.cw, rec.flip, rec.gamma, A
+        return f
+
+
+class AugRecord:
+    """The draw of one PAIR: shared geometry (oy, ox, ch, cw, flip) and gamma -- Python floats holding float32 values -- one float32
+    colour matrix per frame (A_tgt, A_ref), and `terms`, the sampled quantities A was composed from (for logging)."""
+    __slots__ = ("oy", "ox", "ch", "cw", "flip", "gamma", "A_tgt", "A_ref", "terms")
+
+    def __init__(self, oy, ox, ch, cw, flip, gamma, A_tgt, A_ref, terms=None):
+        self.oy, self.ox, self.ch, self.cw, self.gamma = _f32(oy), _f32(ox), _f32(ch), _f32(cw), _f32(gamma)
+        self.flip = int(flip)
+        self.A_tgt = np.asarray(A_tgt, dtype=np.float32).reshape(3, 4)
+        self.A_ref = np.asarray(A_ref, dtype=np.float32).reshape(3, 4)
+        self.terms = terms or {}
+
+    @property
+    def tgt(self) -> FrameAug:
+        return FrameAug._of(self, self.A_tgt)
+
+    @property
+    def ref(self) -> FrameAug:
+        return FrameAug._of(self, self.A_ref)
+
+    def key(self):
+        return (self.oy, self.ox, self.ch, self.cw, self.flip, self.gamma, self.A_tgt.tobytes(), self.A_ref.tobytes())
+
+    def __eq__(self, other):
+        return isinstance(other, AugRecord) and self.key() == other.key()
+
+    def __hash__(self):
+        return hash(self.key())
+
+    def __repr__(self):
+        return (f"AugRecord(oy={self.oy:.4f}, ox={self.ox:.4f}, ch={self.ch:.4f}, cw={self.cw:.4f}, flip={self.flip}, "
+                f"gamma={self.gamma:.4f}, terms={self.terms})")
+
+
+def aug_table(frames: Sequence, H: int, W: int, out: Optional[np.ndarray] = None) -> np.ndarray:
+    """The kernel's parameter table (include/colvo.h ColvoAugRow: oy ox sy sx | flip gamma | A[12] | pad[2], 20 float32 a row) of
+    `frames` (FrameAug, or anything with its attributes); written into `out` ([len(frames), 20] float32) when given."""
+    n = len(frames)
+    t = np.empty((n, _lib.AUG_ROW_FLOATS), dtype=np.float32) if out is None else out
+    if t.shape != (n, _lib.AUG_ROW_FLOATS) or t.dtype != np.float32:
+        raise ValueError("aug_table: out must be float32 [len(frames), 20]")
+    # the steps ch/H, cw/W are formed in float64 and rounded to float32 once, by the store
+    t[...] = [[f.oy, f.ox, float(f.ch) / H, float(f.cw) / W, 0.0, f.gamma, *np.asarray(f.A, dtype=np.float32).ravel().tolist(), 0.0, 0.0]
+              for f in frames]
+    t[:, 4].view(np.int32)[:] = [int(f.flip) for f in frames]
+    return t
+
+
+def augment_intrinsics(K: torch.Tensor, rec, hw_from: Tuple[int, int], hw_to: Tuple[int, int]) -> torch.Tensor:
+    """K [3,3] at the native size -> K' (float64) of the frame cropped by `rec` (oy, ox, ch, cw, flip) and resized to hw_to: pixel
+    centres on integers, x -> (x + 1/2 - ox) W/cw - 1/2, mirrored to W - 1 - x under a flip.  resize_intrinsics is ox = 0, cw = w."""
+    return torch.from_numpy(_augment_intrinsics(K[None], [rec], hw_to)[0])
+
+
+def _augment_intrinsics(Ks: torch.Tensor, recs: Sequence, hw_to: Tuple[int, int]) -> np.ndarray:
+    """augment_intrinsics of a batch: Ks [n,3,3], one record each -> [n,3,3] float64 (numpy; a handful of array operations a batch)."""
+    (H, W) = hw_to
+    g = np.array([(r.oy, r.ox, r.ch, r.cw, r.flip) for r in recs], dtype=np.float64)
+    sy, sx = H / g[:, 2], W / g[:, 3]
+    K2 = Ks.to(torch.float64).numpy().copy()
+    K2[:, 0, 0] *= sx
+    K2[:, 1, 1] *= sy
+    K2[:, 0, 2] = (K2[:, 0, 2] + 0.5 - g[:, 1]) * sx - 0.5
+    K2[:, 1, 2] = (K2[:, 1, 2] + 0.5 - g[:, 0]) * sy - 0.5
+    K2[:, 0, 2] = np.where(g[:, 4] != 0, W - 1 - K2[:, 0, 2], K2[:, 0, 2])
+    return K2
+
+
+def batch_intrinsics(Ks: torch.Tensor, recs: Sequence, hw_from: Tuple[int, int], hw_to: Tuple[int, int]) -> torch.Tensor:
+    """The float32 K' [n,3,3] the loader ships for native Ks [n,3,3] (float32) and one record a pair: augment_intrinsics rounded to
+    float32 once, except that a pair that is neither cropped nor mirrored takes resize_intrinsics itself -- augment=None's K bit for
+    bit (float32 arithmetic can sit an ulp or two from the float64 result)."""
+    K = torch.from_numpy(_augment_intrinsics(Ks, recs, hw_to).astype(np.float32))
+    same = [j for j, r in enumerate(recs) if (r.oy, r.ox, r.ch, r.cw, r.flip) == (0.0, 0.0, hw_from[0], hw_from[1], 0)]
+    if same:
+        K[same] = resize_intrinsics(Ks[same], hw_from, hw_to)
+    return K
+
+
+def _shared_colour_rows(brightness, contrast, saturation, hue) -> List[List[float]]:
+    """The pair's shared colour map as three rows of four Python floats.  rot sat = saturation rot + (1 - saturation) 1 luma^T (a
+    rotation about the grey axis leaves 1 alone), with rot = cos I + (1 - cos)/3 J + sin/sqrt(3) [1]x."""
+    th = 2.0 * math.pi * hue
+    c, s = math.cos(th), math.sin(th) / math.sqrt(3.0)
+    d, o = c + (1.0 - c) / 3.0, (1.0 - c) / 3.0
+    k, t, q = contrast * brightness, 0.5 * (1.0 - contrast), 1.0 - saturation
+    l0, l1, l2 = q * LUMA[0], q * LUMA[1], q * LUMA[2]
+    rows = []
+    for r0, r1, r2 in ((d, o - s, o + s), (o + s, d, o - s), (o - s, o + s, d)):
+        a0, a1, a2 = saturation * r0 + l0, saturation * r1 + l1, saturation * r2 + l2
+        rows.append([k * a0, k * a1, k * a2, t * (a0 + a1 + a2)])
+    return rows
+
+
+def _frame_colour_rows(shared, gain, offset) -> List[List[float]]:
+    """The frame's illumination gain and offset behind the shared map: a (M x + t) + b."""
+    return [[gain * r[0], gain * r[1], gain * r[2], gain * r[3] + offset] for r in shared]
+
+
+def compose_colour(brightness=1.0, contrast=1.0, saturation=1.0, hue=0.0, gain=1.0, offset=0.0) -> np.ndarray:
+    """The 3x4 colour matrix (float64) of: brightness gain, contrast about mid-grey 0.5, saturation about the pixel's own luma, hue as a
+    rotation by `hue` turns about the grey axis, then the frame's illumination gain and offset -- applied in that order."""
+    return np.array(_frame_colour_rows(_shared_colour_rows(brightness, contrast, saturation, hue), gain, offset), dtype=np.float64)
+
+
+_philox = threading.local()
+
+
+def _uniforms(seed: int, epoch: int, index: int, n: int) -> List[float]:
+    """n float64 uniforms in [0,1) of the Philox-4x64 stream with key (seed, epoch) that starts at counter (0, index, 0, 0): the
+    values numpy.random.Generator(Philox(key=..., counter=...)).random(n) gives (53 high bits of each word).  The bit generator
+    object is kept per thread and re-keyed: constructing one costs more than everything else here."""
+    mask = (1 << 64) - 1
+    st = getattr(_philox, "state", None)
+    if st is None:
+        _philox.bits = np.random.Philox(key=[0, 0], counter=[0, 0, 0, 0])
+        st = _philox.state = _philox.bits.state
+    ctr, key = st["state"]["counter"], st["state"]["key"]
+    ctr[0] = ctr[2] = ctr[3] = 0
+    ctr[1] = int(index) & mask
+    key[0], key[1] = int(seed) & mask, int(epoch) & mask
+    st["buffer_pos"], st["has_uint32"], st["uinteger"] = 4, 0, 0
+    _philox.bits.state = st
+    raw = _philox.bits.random_raw(n)
+    return ((raw >> np.uint64(11)) * (2.0 ** -53)).tolist()
+
+
+class Augment:
+    """Seeded augmentation of a frame pair (module docstring: the contract).  Ranges: flip with probability p_flip; zoom in
+    [1, max_zoom]; brightness, contrast and saturation factors in [1 - v, 1 + v]; hue in [-hue, hue] turns; gamma log-uniform in
+    gamma = (lo, hi); per frame an illumination gain in [1 - illum_gain, 1 + illum_gain] and offset in [-illum_offset, illum_offset]."""
+
+    def __init__(self, p_flip: float = 0.5, max_zoom: float = 1.15, brightness: float = 0.2, contrast: float = 0.2,
+                 saturation: float = 0.2, hue: float = 0.1, gamma: Tuple[float, float] = (0.8, 1.25), illum_gain: float = 0.1,
+                 illum_offset: float = 0.05):
+        try:
+            g = (float(gamma[0]), float(gamma[1]))
+            vals = dict(p_flip=float(p_flip), max_zoom=float(max_zoom), brightness=float(brightness), contrast=float(contrast),
+                        saturation=float(saturation), hue=float(hue), illum_gain=float(illum_gain), illum_offset=float(illum_offset))
+        except (TypeError, IndexError) as e:
+            raise ValueError(f"Augment: {e}") from None
+        for k, v in list(vals.items()) + [("gamma[0]", g[0]), ("gamma[1]", g[1])]:
+            if not math.isfinite(v):
+                raise ValueError(f"Augment: {k} = {v} is not finite")
+        if not 0.0 <= vals["p_flip"] <= 1.0:
+            raise ValueError("Augment: p_flip must be in [0, 1]")
+        if vals["max_zoom"] < 1.0:
+            raise ValueError("Augment: max_zoom must be >= 1")
+        if not 0.0 < g[0] <= g[1]:
+            raise ValueError("Augment: gamma must be a range 0 < lo <= hi")
+        for k in ("brightness", "contrast", "saturation", "illum_gain"):
+            if not 0.0 <= vals[k] < 1.0:
+                raise ValueError(f"Augment: {k} must be in [0, 1) (factors are drawn from [1 - v, 1 + v] and stay positive)")
+        if not 0.0 <= vals["hue"] <= 0.5:
+            raise ValueError("Augment: hue (turns) must be in [0, 0.5]")
+        if vals["illum_offset"] < 0.0:
+            raise ValueError("Augment: illum_offset must be >= 0")
+        self.gamma = g
+        for k, v in vals.items():
+            setattr(self, k, v)
+
+    @classmethod
+    def identity(cls) -> "Augment":
+        """Every range degenerate: the identity record for any key."""
+        return cls(p_flip=0.0, max_zoom=1.0, brightness=0.0, contrast=0.0, saturation=0.0, hue=0.0, gamma=(1.0, 1.0),
+                   illum_gain=0.0, illum_offset=0.0)
+
+    def params(self, seed: int, epoch: int, index: int, hw: Tuple[int, int]) -> AugRecord:
+        """The draw of dataset pair `index` in `epoch`: a pure function of (self's ranges, seed, epoch, index, hw).  Philox keyed on
+        (seed, epoch), counter = index (in the counter's second word: a pair's 13 draws take four consecutive 4-word blocks, which advance the FIRST word, so no
+        two pairs share a block)."""
+        u = _uniforms(seed, epoch, index, 13)              # fixed slots: a range that is switched off does not shift the others
+        h, w = hw
+        sym = lambda v, r: 1.0 + r * (2.0 * v - 1.0)
+        flip = int(u[0] < self.p_flip)
+        s = 1.0 + u[1] * (self.max_zoom - 1.0)
+        ch, cw = _f32(h / s), _f32(w / s)
+        # uniform in the slack, on a 1/64-pixel grid (rounded down: oy + ch <= h holds exactly)
+        oy = math.floor(u[2] * (h - ch) * 64.0) / 64.0
+        ox = math.floor(u[3] * (w - cw) * 64.0) / 64.0
+        terms = dict(zoom=s, brightness=sym(u[4], self.brightness), contrast=sym(u[5], self.contrast),
+                     saturation=sym(u[6], self.saturation), hue=self.hue * (2.0 * u[7] - 1.0))
+        lo, hi = math.log(self.gamma[0]), math.log(self.gamma[1])
+        gamma = math.exp(lo + u[8] * (hi - lo))
+        shared = _shared_colour_rows(terms["brightness"], terms["contrast"], terms["saturation"], terms["hue"])
+        mats = []
+        for k, f in ((9, "tgt"), (11, "ref")):           # the frame's illumination gain and offset come last
+            a, b = sym(u[k], self.illum_gain), self.illum_offset * (2.0 * u[k + 1] - 1.0)
+            terms[f"a_{f}"], terms[f"b_{f}"] = a, b
+            mats.append(_frame_colour_rows(shared, a, b))
+        return AugRecord(oy, ox, ch, cw, flip, gamma, mats[0], mats[1], terms)
 
 
 def read_frame(path: str) -> np.ndarray:
@@ -189,13 +439,22 @@ def shard_indices(n: int, batch: int, rank: int, world_size: int, *, shuffle: bo
 
 class PairLoader:
     """Iterating yields dict(tgt, ref [B,3,H,W] fp32 in [0,1] on `device`, K [B,3,3] at (H,W), frames [2B,3,H,W] = the buffer tgt
-    and ref are the two halves of).  Every batch's frames must share one native size (a sequence folder from one camera does)."""
+    and ref are the two halves of).  Every batch's frames must share one native size (a sequence folder from one camera does).
+    With `augment` (an Augment) the frames are cropped / mirrored / colour-jittered by the conversion pass, K follows the crop, and
+    the dict also holds aug = the batch's AugRecords."""
 
     def __init__(self, dataset: SequenceFolder, batch_size: int, size: Tuple[int, int], *, rank: int = 0,
                  world_size: int = 1, shuffle: bool = True, seed: int = 0, device="cuda", workers: int = 8, prefetch: int = 2,
-                 own_copy_stream: Optional[bool] = None, decoders: int = 0):
+                 own_copy_stream: Optional[bool] = None, decoders: int = 0, augment: Optional[Augment] = None):
         if size[0] % 32 or size[1] % 32:
             raise ValueError("size (H, W) must be multiples of 32 (DepthNet)")
+        if augment is not None and not isinstance(augment, Augment):
+            raise ValueError("PairLoader: augment must be an Augment or None")
+        # None: the plain conversion (colvo_frames_u8_to_f32).  An Augment: every pair's crop / flip / colour draw -- a pure function
+        # of (seed, epoch, dataset pair index) -- goes to the GPU as a small table beside the frames and is applied by the conversion
+        # pass itself (colvo_frames_u8_augment); the batch dict gains "aug", the host-side records.
+        self.augment = augment
+        self._tables: Dict[Tuple[int, int, int, int], torch.Tensor] = {}     # (slot, pairs, h, w), a staging buffer's key -> its pinned table [2 pairs, 20]
         self.ds, self.B, self.size = dataset, batch_size, tuple(size)
         self.rank, self.world, self.shuffle, self.seed = rank, world_size, shuffle, seed
         self.device = torch.device(device)
@@ -315,9 +574,10 @@ class PairLoader:
         return len(shard_indices(len(self.ds), self.B, self.rank, self.world, shuffle=False, seed=0, epoch=0)) // self.B
 
     # ---- host half: decode into pinned memory ------------------------------------------------ #
-    def _stage(self, idx: Sequence[int], slot: int):
+    def _stage(self, idx: Sequence[int], slot: int, epoch: Optional[int] = None):
         """Decode one batch into the pinned buffer of ring slot `slot` (slots are handed out by the iterating thread: a slot is
-        staged by one thread at a time and comes round again only after prefetch + 2 batches)."""
+        staged by one thread at a time and comes round again only after prefetch + 2 batches).  -> (pinned frames, K at the training
+        size, native (h, w), pinned parameter table or None, records or None)."""
         infos = [self.ds.pair_info(i) for i in idx]
         h, w = infos[0][3]
         for info in infos:
@@ -334,8 +594,7 @@ class PairLoader:
         paths = [info[0] for info in infos] + [info[1] for info in infos]
         if all(p.endswith(".npy") for p in paths):
             read_npy_frames(paths, view, self.workers)      # native: headers checked and payloads read in C, no interpreter lock
-            K = resize_intrinsics(torch.stack([info[2] for info in infos]), (h, w), self.size)
-            return buf, K, (h, w)
+            return self._staged(buf, infos, idx, slot, (h, w), epoch)
         if self._procs:                   # one frame per request to whichever decoder process is idle
             shm_name, fb = self._shm[key].name, h * w * 3
             todo = [(j, p) for j, p in enumerate(paths) if not p.endswith(".npy")]
@@ -343,8 +602,7 @@ class PairLoader:
                 if p.endswith(".npy"):
                     read_frame_into(p, view[j])
             list(self.pool.map(lambda jp: self._decode_remote(shm_name, jp[0] * fb, h, w, jp[1]), todo))
-            K = resize_intrinsics(torch.stack([info[2] for info in infos]), (h, w), self.size)
-            return buf, K, (h, w)
+            return self._staged(buf, infos, idx, slot, (h, w), epoch)
         jobs = [(p, view[j]) for j, p in enumerate(paths)]
         nw = min(len(jobs), self.workers)
 
@@ -352,31 +610,57 @@ class PairLoader:
             for path, out in chunk:
                 read_frame_into(path, out)
         list(self.pool.map(run, [jobs[c::nw] for c in range(nw)]))
-        K = resize_intrinsics(torch.stack([info[2] for info in infos]), (h, w), self.size)      # one batched call
-        return buf, K, (h, w)
+        return self._staged(buf, infos, idx, slot, (h, w), epoch)
+
+    def _staged(self, buf, infos, idx, slot, hw, epoch):
+        """The rest of a staged batch: K at the training size and, with an Augment, every pair's record and the parameter table
+        (target rows, then reference rows) in the pinned table that belongs to this very frame buffer (one table per staging buffer,
+        under the buffer's key): the event that guards the buffer's reuse, recorded after both copies on the same stream and waited
+        for by _stage, guards the table too."""
+        Ks = torch.stack([info[2] for info in infos])
+        if self.augment is None:
+            return buf, resize_intrinsics(Ks, hw, self.size), hw, None, None           # one batched call
+        H, W = self.size
+        n = len(infos)
+        epoch = self.epoch if epoch is None else epoch
+        recs = [self.augment.params(self.seed, epoch, i, hw) for i in idx]
+        key = (slot, n) + tuple(hw)
+        tab = self._tables.get(key)
+        if tab is None:
+            tab = self._tables[key] = torch.empty(2 * n, _lib.AUG_ROW_FLOATS, dtype=torch.float32).pin_memory()
+        aug_table([r.tgt for r in recs] + [r.ref for r in recs], H, W, out=tab.numpy())
+        return buf, batch_intrinsics(Ks, recs, hw, self.size), hw, tab, recs
 
     # ---- device half: upload + convert on the copy stream ------------------------------------ #
     def _upload(self, staged):
-        buf, K, (h, w) = staged
+        buf, K, (h, w), tab, recs = staged
         lib = _lib.load()
         n = buf.shape[0]
         H, W = self.size
         stream = self.copy_stream if self.copy_stream is not None else torch.cuda.current_stream(self.device)
         with torch.cuda.stream(stream):
-            raw = buf.to(self.device, non_blocking=True)
+            keep = (buf.to(self.device, non_blocking=True),)          # what the conversion reads: alive until the consumer has it
+            raw = keep[0]
             out = torch.empty(n, 3, H, W, device=self.device, dtype=torch.float32)
-            _lib.check(lib.colvo_frames_u8_to_f32(_lib.ptr(raw), n, h, w, H, W, _lib.ptr(out), _lib.stream_ptr()),
-                       "colvo_frames_u8_to_f32")
+            if tab is None:
+                _lib.check(lib.colvo_frames_u8_to_f32(_lib.ptr(raw), n, h, w, H, W, _lib.ptr(out), _lib.stream_ptr()),
+                           "colvo_frames_u8_to_f32")
+            else:                       # one small extra H2D copy on the same stream
+                dtab = tab.to(self.device, non_blocking=True)
+                _lib.check(lib.colvo_frames_u8_augment(_lib.ptr(raw), n, h, w, H, W, _lib.ptr(dtab), _lib.ptr(out),
+                                                       _lib.stream_ptr()), "colvo_frames_u8_augment")
+                keep += (dtab,)
             Kd = K.to(self.device, non_blocking=True)
             done = torch.cuda.Event()
             done.record(stream)
         self._uploaded[buf.data_ptr()] = done
-        return out, Kd, done, raw
+        return out, Kd, done, keep, recs
 
     def __iter__(self) -> Iterator[Dict[str, torch.Tensor]]:
         idx = shard_indices(len(self.ds), self.B, self.rank, self.world, shuffle=self.shuffle, seed=self.seed,
                             epoch=self.epoch)
         batches = [idx[i:i + self.B] for i in range(0, len(idx), self.B)]
+        epoch = self.epoch              # the augmentation draws of this pass: fixed here, like the permutation
         # decode of batches k+1 .. k+prefetch (staging threads + the decoder pool) overlaps the upload and the training step
         # of batch k; ring of prefetch + 2 pinned buffers: `prefetch` being filled, one being uploaded, one of margin
         ring = self.prefetch + 2
@@ -390,7 +674,7 @@ class PairLoader:
         def submit():
             nonlocal submitted
             if submitted < len(batches):
-                futs.append(self._stager.submit(self._stage, batches[submitted], self._slot_seq % ring))
+                futs.append(self._stager.submit(self._stage, batches[submitted], self._slot_seq % ring, epoch))
                 self._slot_seq += 1
                 submitted += 1
         try:
@@ -404,14 +688,17 @@ class PairLoader:
                     submit()
                     nxt = self._upload(staged)
                 if pending is not None:
-                    out, Kd, done, raw = pending
+                    out, Kd, done, keep, recs = pending
                     torch.cuda.current_stream(self.device).wait_event(done)
-                    for t in (out, Kd, raw):
+                    for t in (out, Kd) + keep:
                         t.record_stream(torch.cuda.current_stream(self.device))
                     B = out.shape[0] // 2
                     # "frames": the stacked buffer itself, [target frames | reference frames] = what DepthNet.forward_pair* and
                     # nn.dcdp_forward(frames=...) take -- no torch.cat in the train loop
-                    yield {"tgt": out[:B], "ref": out[B:], "K": Kd, "frames": out}
+                    batch = {"tgt": out[:B], "ref": out[B:], "K": Kd, "frames": out}
+                    if recs is not None:
+                        batch["aug"] = recs
+                    yield batch
                 pending = nxt
         finally:
             self._drain()           # generator closed early (break / exception): no staging task outlives its iterator

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define COLVO_ABI_VERSION 14
+#define COLVO_ABI_VERSION 15
 
 typedef void* colvo_stream_t; /* hipStream_t */
 
@@ -532,6 +532,28 @@ int colvo_depth_metrics(const float* pred, const float* gt, const uint8_t* mask,
  * centres (source index = (h/H)*(y+0.5)-0.5 clamped at 0), channel de-interleave and /255 in one pass. */
 int colvo_frames_u8_to_f32(const uint8_t* frames, int B, int h, int w, int H, int W, float* out,
                            colvo_stream_t stream);
+
+/* The same pass with a per-frame augmentation folded in: crop / mirror / resize, a 3x4 colour map, clamp and
+ * gamma, one launch, the source read once.  `params` (device, 16-byte aligned) holds one ColvoAugRow per frame.  Output pixel
+ * (y, x) of frame i reads the source at
+ *     fy = fma(sy, y + 0.5, oy - 0.5),   fx = fma(sx, x' + 0.5, ox - 0.5),   x' = flip ? W-1-x : x        (float32, one rounding each)
+ * clamped below at 0, taps y0 = min(floor(fy), h-1), y1 = min(y0+1, h-1) (likewise in x) and the bilinear weights of
+ * colvo_frames_u8_to_f32; then, on the resized r, g, b in [0,1],
+ *     out_c = clamp(A[c][0]*r + A[c][1]*g + A[c][2]*b + A[c][3], 0, 1),   out_c = out_c ** gamma  when gamma != 1.
+ * With oy = ox = 0, sy = h/H, sx = w/W, flip = 0, A = [I | 0], gamma = 1 the result equals colvo_frames_u8_to_f32's bit for bit.
+ * The kernel is memory-safe for ANY bit pattern in the table (every tap index is clamped into the frame, a NaN coordinate reads
+ * pixel 0; the output is finite and in [0,1] whatever the row holds); whether a row makes sense is the caller's business.
+ * Same limits as colvo_frames_u8_to_f32. */
+typedef struct ColvoAugRow {
+    float oy, ox;      /* crop origin in native edge coordinates (pixel i covers [i, i+1)) */
+    float sy, sx;      /* source step per output pixel: crop height / H, crop width / W */
+    int32_t flip;      /* != 0: mirrored left-right (the reads are reversed, the stores stay in order) */
+    float gamma;       /* exponent applied after the clamp; exactly 1 skips it */
+    float A[12];       /* row-major 3x4 colour matrix: out_c = A[4c..4c+2] . (r, g, b) + A[4c+3] */
+    float pad_[2];     /* 80 bytes: rows of a 16-byte aligned table stay 16-byte aligned */
+} ColvoAugRow;
+int colvo_frames_u8_augment(const uint8_t* frames, int n, int h, int w, int H, int W, const ColvoAugRow* params, float* out,
+                            colvo_stream_t stream);
 
 /* Host side of the same row (no GPU work): n raw frames -- `.npy` files holding [h,w,3] uint8 arrays in C order -- read into
  * dst[n][h][w][3] (the caller's staging buffer, normally pinned) by up to `nthreads` threads; every header is checked against

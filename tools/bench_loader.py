@@ -1,9 +1,12 @@
 #!/usr/bin/env python3
 """Throughput of the frame-pair input pipeline (coivo_amd.data.PairLoader) on synthetic sequence folders:
-   python tools/bench_loader.py [npy|png] [workers=8] [native=256x320] [batch=8] [prefetch=3]
+   python tools/bench_loader.py [npy|png] [workers=8] [native=256x320] [batch=8] [prefetch=3] [train] [--augment | --augment=gamma1]
 Writes a temporary dataset (under $TMPDIR), iterates two epochs and prints pairs/s of the second one -- with nothing else on
 the GPU, so this is the rate the loader can deliver, to be read against the training step's rate.  With a sixth argument
 `train` every batch is also trained on (bf16 DCDP+LCC step, random weights): the end-to-end rate of loader + step in one process.
+--augment turns the loader's seeded augmentation on with its default ranges (data.Augment(): crop / flip / colour / gamma folded into
+the conversion pass); --augment=gamma1 the same with gamma fixed at 1, which takes the powf out of the kernel.  Read either against
+the same command without the flag, on the same box.
 DECODERS=n decodes images in n worker processes; OWN_COPY_STREAM=0 / 1 overrides the loader's choice of stream for the upload (see data.PairLoader)."""
 import os
 import shutil
@@ -15,16 +18,21 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from coivo_amd.data import PairLoader, SequenceFolder  # noqa: E402
+from coivo_amd.data import Augment, PairLoader, SequenceFolder  # noqa: E402
 
 
 def main():
-    kind = sys.argv[1] if len(sys.argv) > 1 else "npy"
-    workers = int(sys.argv[2]) if len(sys.argv) > 2 else 8
-    h, w = (int(v) for v in (sys.argv[3] if len(sys.argv) > 3 else "256x320").split("x"))
-    B = int(sys.argv[4]) if len(sys.argv) > 4 else 8
-    prefetch = int(sys.argv[5]) if len(sys.argv) > 5 else 2
-    train = len(sys.argv) > 6 and sys.argv[6] == "train"
+    flags = [a for a in sys.argv[1:] if a.startswith("--")]
+    argv = [sys.argv[0]] + [a for a in sys.argv[1:] if not a.startswith("--")]
+    if any(f not in ("--augment", "--augment=gamma1") for f in flags):
+        sys.exit(f"unknown option in {flags} (--augment, --augment=gamma1)")
+    augment = None if not flags else Augment(gamma=(1.0, 1.0)) if "--augment=gamma1" in flags else Augment()
+    kind = argv[1] if len(argv) > 1 else "npy"
+    workers = int(argv[2]) if len(argv) > 2 else 8
+    h, w = (int(v) for v in (argv[3] if len(argv) > 3 else "256x320").split("x"))
+    B = int(argv[4]) if len(argv) > 4 else 8
+    prefetch = int(argv[5]) if len(argv) > 5 else 2
+    train = len(argv) > 6 and argv[6] == "train"
     root = tempfile.mkdtemp(prefix="colvo_loader_")
     try:
         rng = np.random.default_rng(0)
@@ -42,7 +50,7 @@ def main():
         ds = SequenceFolder(root)
         ld = PairLoader(ds, B, (256, 320), shuffle=True, workers=workers, prefetch=prefetch,
                         own_copy_stream={None: None, "0": False, "1": True}[os.environ.get("OWN_COPY_STREAM")],
-                        decoders=int(os.environ.get("DECODERS", "0")))
+                        decoders=int(os.environ.get("DECODERS", "0")), augment=augment)
         if os.environ.get("KEEP_AUX"):       # probe: keep the auxiliary side stream although the loader claimed a queue
             from coivo_amd import streams
             streams.configure(0)
@@ -73,7 +81,7 @@ def main():
                     step(batch)
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
-            print(f"{kind} {h}x{w} batch {B} workers {workers} prefetch {prefetch}{' +train' if train else ''} epoch {ep}: {n} pairs in {dt * 1e3:.1f} ms = {n / dt:.0f} pairs/s", flush=True)
+            print(f"{kind} {h}x{w} batch {B} workers {workers} prefetch {prefetch}{' +train' if train else ''}{' ' + flags[0][2:] if flags else ''} epoch {ep}: {n} pairs in {dt * 1e3:.1f} ms = {n / dt:.0f} pairs/s", flush=True)
     finally:
         shutil.rmtree(root, ignore_errors=True)
 
