@@ -115,7 +115,11 @@ namespace tune {
                         "bytes each), compacted through LDS; 0: every issuing lane adds its record's words in four instructions "            \
                         "(same shape: 5784 us against 1517 at 8 rounds, 4084 against 1244 at 64: the memory side works in requests)")       \
     X(fuse_count_limit, 16777216, "a voxel with this many samples raises the overflow flag (2^24: 255 * 2^24 < 2^32, the 32-bit sums "  \
-                                  "cannot have wrapped below it; the tests lower it)")
+                                  "cannot have wrapped below it; the tests lower it)")                                                  \
+    /* ---- depth consistency (consistency.hip) ---- */                                                                              \
+    X(consist_stat_lines, 8, "a workgroup's five integer adds go to one of this many 64-byte counter lines of its frame (1..8; 1: "    \
+                             "every workgroup of a frame adds to the same line).  Integer sums: the result does not depend on it.  "  \
+                             "512 frames of 256x320, window 2, whole call: 1 -> 574.6 us, 8 -> 566.0 (tools/bench_consistency.py)")
 
 struct Table {
 #define X(name, dflt, doc) double name = dflt;

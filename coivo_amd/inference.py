@@ -2,7 +2,8 @@
 the coloured, voxel-averaged cloud fused from it.
 
 Reference: README.md:9 ("complete 3D reconstruction of the intestine"), README.md:29 ("stitching together the dense depth
-maps of each frame using the colonoscopic trajectory").  Spec: oracle/colvo_spec.py integrate_trajectory / backproject /
+maps of each frame using the colonoscopic trajectory").  filter_depths is the cross-view check in front of both (DESIGN.md
+§3.6f, csrc/consistency.hip).  Spec: oracle/colvo_spec.py integrate_trajectory / backproject /
 stitch_point_cloud (oracle/SPEC.md §6c).  The per-pixel work runs in csrc/reconstruct.hip; the trajectory integration is N
 products of 4x4 matrices and is done on the host in float64 (it is control flow, not a kernel).  The fusion runs in
 csrc/fuse.hip.
@@ -212,6 +213,78 @@ def fuse_point_cloud(depths: torch.Tensor, K: torch.Tensor, cam2world: torch.Ten
     return FusedCloud(points, out_colors, counts, voxels, origin, dims, vs, n_input, n_outside, n_bricks, n_voxels)
 
 
+class Consistency(NamedTuple):
+    """The policy of filter_depths; also what reconstruct_sequence takes.  The defaults are choices, not tuned values."""
+    window: int = 2          # neighbours i +/- k*step, k = 1..window, that exist in [0, N)
+    step: int = 1            # frame distance between neighbours (a wider baseline discriminates better)
+    rel_tol: float = 0.01    # agree iff |P_z - s| / (P_z + s) < rel_tol
+    min_agree: int = 1       # keep iff agree >= min_agree ...
+    max_violated: int = 0    # ... and violated <= max_violated
+
+
+class ConsistencyResult(NamedTuple):
+    depths: torch.Tensor     # [N,1,H,W] float32: the input depth where kept, +inf elsewhere
+    votes: torch.Tensor      # [N,3,H,W] uint8: planes agree / occluded / violated
+    stats: torch.Tensor      # [N,5] int32: candidates, kept, no_view, few_agree, violated_out
+
+
+def _check_consistency(who: str, window, step, rel_tol, min_agree, max_violated, max_depth) -> None:
+    for name, val in (("window", window), ("step", step), ("min_agree", min_agree), ("max_violated", max_violated)):
+        if isinstance(val, bool) or not isinstance(val, int):
+            raise ValueError(f"{who}: {name} must be an int, got {val!r}")
+    if not 1 <= window <= 16:
+        raise ValueError(f"{who}: window must be in 1..16, got {window}")
+    if step < 1:
+        raise ValueError(f"{who}: step must be >= 1, got {step}")
+    if min_agree < 0 or max_violated < 0:
+        raise ValueError(f"{who}: min_agree and max_violated must be >= 0, got {min_agree}, {max_violated}")
+    if min_agree > 2 * window:
+        raise ValueError(f"{who}: min_agree {min_agree} can never be reached with 2 * window = {2 * window} neighbours")
+    for name, val in (("rel_tol", rel_tol), ("max_depth", max_depth)):
+        try:
+            ok = math.isfinite(_f32(val)) and _f32(val) > 0.0
+        except (TypeError, ValueError, OverflowError, struct.error):
+            ok = False
+        if not ok:
+            raise ValueError(f"{who}: {name} must be finite and positive (as float32), got {val!r}")
+
+
+def filter_depths(depths: torch.Tensor, K: torch.Tensor, cam2world: torch.Tensor, *, window: int = 2, step: int = 1,
+                  rel_tol: float = 0.01, min_agree: int = 1, max_violated: int = 0,
+                  max_depth: float = MAX_DEPTH) -> ConsistencyResult:
+    """Multi-view consistency check of a sequence's depth maps (contract: include/colvo.h colvo_consistency_filter, DESIGN.md
+    §3.6f; csrc/consistency.hip).  depths [N,1,H,W], K [N,3,3] (per frame), cam2world [N,4,4], float32 on the device.  Every
+    pixel with 0 < d < max_depth is carried through the trajectory into the frames i +/- k*step, k = 1..window, that exist;
+    a neighbour that sees the point (in front, inside the image, four valid taps) AGREES if |P_z - s| / (P_z + s) < rel_tol
+    for its own interpolated depth s, is OCCLUDED if s < P_z (legitimate: it does not count against the pixel) and is
+    VIOLATED otherwise (the neighbour sees through the point).  A pixel is kept iff agree >= min_agree and violated <=
+    max_violated.  N = 1, or a window * step that reaches past the sequence, is legal: those neighbours do not exist.
+
+    A rejected pixel, and one that never was a candidate, is written as +inf, not 0: stitch_point_cloud keeps d < max_depth,
+    so 0 would pass and put a point at the camera centre; fuse_point_cloud and localize_polyps keep 0 < d < max_depth.  +inf
+    is dropped by all three, so the result feeds them unchanged.  No read-back and no host synchronisation."""
+    _check_consistency("filter_depths", window, step, rel_tol, min_agree, max_violated, max_depth)
+    if not isinstance(depths, torch.Tensor) or depths.dim() != 4:
+        raise ValueError("filter_depths: depths must be [N,1,H,W]")
+    N, _, H, W = depths.shape
+    depths = _chk(depths, "depths", (N, 1, H, W))
+    K = _chk(K, "K", (N, 3, 3))
+    cam2world = _chk(cam2world, "cam2world", (N, 4, 4))
+    lib = _lib.load()
+    ws_bytes = int(lib.colvo_consistency_workspace_bytes(N, window))
+    if ws_bytes == 0 or H <= 0 or W <= 0 or H * W >= 1 << 30:
+        raise ValueError(f"filter_depths: shape N={N} H={H} W={W} beyond the kernels' limits (N <= 65535, H*W < 2^30)")
+    dev = depths.device
+    ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
+    out = torch.empty(N, 1, H, W, device=dev, dtype=torch.float32)
+    votes = torch.empty(N, 3, H, W, device=dev, dtype=torch.uint8)
+    stats = torch.empty(N, 5, device=dev, dtype=torch.int32)
+    _lib.check(lib.colvo_consistency_filter(_lib.ptr(depths), _lib.ptr(K), _lib.ptr(cam2world), N, H, W, window, min(step, 1 << 30),
+                                            float(rel_tol), min_agree, max_violated, float(max_depth), _lib.ptr(ws), _lib.ptr(out),
+                                            _lib.ptr(votes), _lib.ptr(stats), _lib.stream_ptr()), "colvo_consistency_filter")
+    return ConsistencyResult(out, votes, stats)
+
+
 def write_ply(path, points: torch.Tensor, colors: Optional[torch.Tensor] = None) -> None:
     """Binary little-endian PLY: `float x y z` per vertex and, with colours [M,3] in [0,1], `uchar red green blue`
     (rint(c * 255), clamped).  Host code; one device -> host copy."""
@@ -253,17 +326,22 @@ class _ReconstructionFields(NamedTuple):
 
 class Reconstruction(_ReconstructionFields):
     """The five fields above -- it still unpacks into five -- and, behind them, `polyps`: with labels the PolypLocalization
-    of the same depths and trajectory (coivo_amd.localize), else None."""
+    of the same depths and trajectory (coivo_amd.localize), else None; and `consistency`: with a Consistency policy the
+    ConsistencyResult whose depths points, fused and polyps were computed from (`depths` stays the raw network output), else
+    None."""
     polyps = None               # Optional[PolypLocalization]
+    consistency = None          # Optional[ConsistencyResult]
 
-    def __new__(cls, depths, rel_poses, cam2world, points, fused=None, polyps=None):
+    def __new__(cls, depths, rel_poses, cam2world, points, fused=None, polyps=None, consistency=None):
         self = super().__new__(cls, depths, rel_poses, cam2world, points, fused)
         self.polyps = polyps
+        self.consistency = consistency
         return self
 
     def _replace(self, **kw):
         polyps = kw.pop("polyps", self.polyps)
-        return type(self)(*super()._replace(**kw), polyps=polyps)
+        consistency = kw.pop("consistency", self.consistency)
+        return type(self)(*super()._replace(**kw), polyps=polyps, consistency=consistency)
 
 
 @torch.no_grad()
@@ -285,23 +363,32 @@ def run_networks(depth_net, pose_net, frames: torch.Tensor, *, chunk: int = 16):
 def reconstruct_sequence(depth_net, pose_net, frames: torch.Tensor, K: torch.Tensor, *, stride: int = 4,
                          max_depth: float = MAX_DEPTH, chunk: int = 16, voxel_size: Optional[float] = None,
                          min_obs: int = 1, labels: Optional[torch.Tensor] = None,
-                         num_labels: Optional[int] = None) -> Reconstruction:
+                         num_labels: Optional[int] = None, consistency: Optional[Consistency] = None) -> Reconstruction:
     """frames [N+1,3,H,W] of one sequence, K [3,3] or [N+1,3,3] -> depth of every frame, the pose of every consecutive
     pair (DCDP: PoseNet sees both depth maps), the integrated trajectory and the stitched cloud.  With a voxel_size also
     the fused cloud of the same samples, coloured by the frames (fuse_point_cloud; `fused`, else None).  With labels
     [N+1,1,H,W] uint8 and num_labels also the polyps they mark, localised from the same depths, K, trajectory and max_depth at
-    stride 1 (localize.localize_polyps; `polyps`, else None)."""
+    stride 1 (localize.localize_polyps; `polyps`, else None).  With a Consistency policy the depth maps first pass
+    filter_depths along the integrated trajectory (same K and max_depth): points, fused and polyps are computed from the
+    filtered depths, `depths` stays the raw network output and the ConsistencyResult is `consistency` (else None)."""
     n = frames.shape[0]
     if n < 2:
         raise ValueError("reconstruct_sequence: need at least two frames")
     if labels is not None and num_labels is None:
         raise ValueError("reconstruct_sequence: labels need num_labels")
+    if consistency is not None:
+        consistency = Consistency(*consistency)
+        _check_consistency("reconstruct_sequence", *consistency, max_depth)
     if K.dim() == 2:
         K = K.unsqueeze(0).expand(n, 3, 3)
     K = K.to(frames.device, torch.float32).contiguous()
     depths, rel = run_networks(depth_net, pose_net, frames, chunk=chunk)
     traj = integrate_trajectory(rel)
     traj32 = traj.to(frames.device, torch.float32)
+    raw, checked = depths, None
+    if consistency is not None:
+        checked = filter_depths(depths, K, traj32, **consistency._asdict(), max_depth=max_depth)
+        depths = checked.depths
     cloud = stitch_point_cloud(depths, K, traj32, stride=stride, max_depth=max_depth)
     fused = None
     if voxel_size is not None:
@@ -311,4 +398,4 @@ def reconstruct_sequence(depth_net, pose_net, frames: torch.Tensor, K: torch.Ten
     if labels is not None:
         from . import localize                       # (localize imports this module)
         polyps = localize.localize_polyps(depths, labels, K, traj32, num_labels=num_labels, stride=1, max_depth=max_depth)
-    return Reconstruction(depths, rel, traj, cloud, fused, polyps)
+    return Reconstruction(raw, rel, traj, cloud, fused, polyps, checked)

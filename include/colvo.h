@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define COLVO_ABI_VERSION 15
+#define COLVO_ABI_VERSION 16
 
 typedef void* colvo_stream_t; /* hipStream_t */
 
@@ -509,6 +509,39 @@ int colvo_localize_finish(const void* records, const float* cam2world, int N, in
                           int32_t* n_samples, int32_t* bbox, double* pixel, double* center_cam, double* cov_cam,
                           double* center_world, int32_t* n_frames, int64_t* n_samples_total, int32_t* first_frame,
                           int32_t* last_frame, double* position, double* cov_world, int64_t* stats, colvo_stream_t stream);
+
+/* Multi-view depth consistency: a pixel of frame i keeps its depth only if neighbouring frames, through the
+ * trajectory, see the same surface there.  depths [N,1,H,W], K [N,3,3] (per frame), cam2world [N,4,4], all float32.  The
+ * neighbours of frame i are the frames j = i + k * step, k = -window..-1, 1..window, that exist in [0, N): 2 * window slots in
+ * ascending j.  Float32, every operation individually rounded in the order written (no FMA contraction), plain divisions:
+ *   transforms  for every (i, slot) whose j exists, [R|t] maps frame-i camera coordinates into frame j; float64 from the float32
+ *               cam2world (rotation block taken as orthonormal; Ri, ti / Rj, tj its blocks for i / j), each value rounded to float32:
+ *                 R[a][b] = (Rj[0][a] * Ri[0][b] + Rj[1][a] * Ri[1][b]) + Rj[2][a] * Ri[2][b],
+ *                 t[a]    = (Rj[0][a] * (ti[0] - tj[0]) + Rj[1][a] * (ti[1] - tj[1])) + Rj[2][a] * (ti[2] - tj[2]).
+ *   candidate   pixel (i, u, v) with d = depth_i[v][u] is a candidate iff 0 < d < max_depth (NaN falls out).
+ *   neighbour   px = ((u - cx_i) / fx_i) * d, py = ((v - cy_i) / fy_i) * d, P_a = ((R_a0 * px + R_a1 * py) + R_a2 * d) + t_a;
+ *               front iff P_z > 1e-3f;  x = (fx_j * P_x) / P_z + cx_j, y = (fy_j * P_y) / P_z + cy_j;
+ *               inside iff 0 <= x <= W - 1 and 0 <= y <= H - 1;  x0 = floor(x), wx = x - x0, x1 = min(x0 + 1, W - 1), the same in y;
+ *               taps t00 = depth_j[y0][x0], t01 = [y0][x1], t10 = [y1][x0], t11 = [y1][x1], valid iff each has 0 < t < max_depth;
+ *               s = (((t00 * (1 - wx)) + (t01 * wx)) * (1 - wy)) + (((t10 * (1 - wx)) + (t11 * wx)) * wy);
+ *               rel = |P_z - s| / (P_z + s).  The neighbour is visible iff front, inside and taps valid; a visible neighbour counts
+ *               as AGREE if rel < rel_tol, else as OCCLUDED if s < P_z (frame j has a surface in front of the point), else as
+ *               VIOLATED (frame j sees through the point).
+ *   keep        a pixel is kept iff it is a candidate, agree >= min_agree and violated <= max_violated.
+ *   outputs     out_depths [N,1,H,W] float32: the input depth where kept, +inf elsewhere (dropped by the `d < max_depth` of
+ *               colvo_stitch_point_cloud and by the `0 < d < max_depth` of the fusion and the localisation);
+ *               out_votes [N,3,H,W] uint8: planes agree, occluded, violated (0 where no candidate);
+ *               out_stats [N,5] int32 per frame: candidates, kept, no_view (a candidate without a visible neighbour that is not kept:
+ *               min_agree = 0 keeps it), few_agree (a candidate with a visible neighbour, violated <= max_violated and
+ *               agree < min_agree), violated_out (a candidate with violated > max_violated); the last four sum to the first.  Integer sums: identical bits on every call and stream.
+ * workspace: colvo_consistency_workspace_bytes(N, window) bytes, 16-byte aligned: the transform table [N][2 * window][12] (R row-major,
+ * then t) and the per-frame counters, both written by the call.  0 for what the call refuses.
+ * Limits: N <= 65535, H*W < 2^30, window in 1..16, step >= 1, 0 <= min_agree <= 2 * window, max_violated >= 0, rel_tol and
+ * max_depth finite and positive. */
+size_t colvo_consistency_workspace_bytes(int N, int window);
+int colvo_consistency_filter(const float* depths, const float* K, const float* cam2world, int N, int H, int W, int window, int step,
+                             float rel_tol, int min_agree, int max_violated, float max_depth, void* workspace, float* out_depths,
+                             uint8_t* out_votes, int32_t* out_stats, colvo_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------- *
  * SURVEY.md §6  evaluation: depth error measures with per-image median scaling. *
