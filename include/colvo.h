@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define COLVO_ABI_VERSION 16
+#define COLVO_ABI_VERSION 17
 
 typedef void* colvo_stream_t; /* hipStream_t */
 
@@ -542,6 +542,63 @@ size_t colvo_consistency_workspace_bytes(int N, int window);
 int colvo_consistency_filter(const float* depths, const float* K, const float* cam2world, int N, int H, int W, int window, int step,
                              float rel_tol, int min_agree, int max_violated, float max_depth, void* workspace, float* out_depths,
                              uint8_t* out_votes, int32_t* out_stats, colvo_stream_t stream);
+
+/* Pose refinement by dense depth and intensity alignment: a few Gauss-Newton steps per edge on the per-pixel geometric
+ * and photometric residuals of the two frames it connects, starting from the pose given.  depths [N,1,H,W], frames [N,3,H,W], K [N,3,3]
+ * (per frame), float32; edges [E][2] int32 (i, j) ON THE DEVICE.  An edge is (i, j, T): T = [R|t] maps frame-i camera coordinates into
+ * frame j, float64 state (T arrays are [E][4][4] row-major; rows 0..2 are read), with a gain a and an offset b (float64 state, 1 and 0
+ * at the start).  Each of the 14 values is rounded once to float32 for the per-pixel arithmetic.  Float32 per sample, every operation
+ * individually rounded in the order written (no FMA contraction), plain divisions:
+ *   intensity   grey = ((r + g) + b) * (1/3) of the frames (the float32 quotient 1.0f / 3.0f); I_i, I_j the grey planes.
+ *   geometry    for pixel (u, v) of frame i: candidate, px, py, P, front, x, y, inside, x0, x1, y0, y1, wx, wy, the taps t00 .. t11 of
+ *               depth_j, their validity and s exactly as colvo_consistency_filter's "neighbour" (K_i, K_j per frame); the sample is
+ *               VISIBLE iff candidate, front, inside and taps valid.  c00 .. c11 are the same four positions of I_j and
+ *               c = (((c00 * (1 - wx)) + (c01 * wx)) * (1 - wy)) + (((c10 * (1 - wx)) + (c11 * wx)) * wy).
+ *   gradients   sx = ((t01 - t00) * (1 - wy)) + ((t11 - t10) * wy), sy = ((t10 - t00) * (1 - wx)) + ((t11 - t01) * wx); cx, cy likewise
+ *               from c00 .. c11.  iz = 1 / P_z.  G(gx, gy): A = gx * fx_j, B = gy * fy_j,
+ *                 G = (A * iz, B * iz, -((((A * P_x) + (B * P_y)) * iz) * iz)).
+ *               P x g = ((P_y * g_z) - (P_z * g_y), (P_z * g_x) - (P_x * g_z), (P_x * g_y) - (P_y * g_x)).
+ *               The update is a left perturbation T <- exp(xi) T, xi = (upsilon, omega): a scalar with P-gradient g has the pose row
+ *               [g, P x g].
+ *   geometric   den = P_z + s, rel = (P_z - s) / den, k = 2 / (den * den), G = G(sx, sy),
+ *               g_r = (-(k * (P_z * G_x)), -(k * (P_z * G_y)), k * (s - (P_z * G_z)));  with w_g = 1.0f / sigma_geo:
+ *               e_g = rel * w_g, J_g = [g_r * w_g, (P x g_r) * w_g, 0, 0].  Used iff visible and |rel| < gate_geo.
+ *   photometric r_I = ((a * c) + b) - I_i[v][u], G = G(cx, cy), h = a * G;  with w_p = 1.0f / sigma_photo:
+ *               e_p = r_I * w_p, J_p = [h * w_p, (P x h) * w_p, c * w_p, 1 * w_p].  Used iff visible and |r_I| < gate_photo.
+ *   sums        per edge, float64: the 36 upper-triangle entries of sum J^T J (row-major: (0,0) .. (0,7), (1,1) ..) and the 8 of
+ *               sum J^T e over the used samples of the enabled terms; C_g = sum over the visible samples of min(e_g^2, cap_g),
+ *               cap_g = the square of the float32 product gate_geo * w_g, and C_p likewise; the integer counts n_visible, n_geo,
+ *               n_photo.  A disabled term adds nothing (its count and C are 0).  Rows and residuals are float32, so every product
+ *               is exact in float64; the order of the float64 additions is fixed by the kernels (per thread over its samples, a
+ *               fixed tree over the workgroup, the workgroups' rows in a fixed order): identical bits on every call and stream.
+ *   solve       float64, one thread per edge: the unknowns are the 6 pose entries, and a, b as well iff the photometric term and
+ *               the brightness are enabled; H + damping * diag(H), Cholesky, delta = -H^-1 sum J^T e; T <- exp(delta_1..6) T by the
+ *               closed form (its series below |omega|^2 = 1e-8), a += delta_7, b += delta_8.  An edge FREEZES -- initial T, a, b,
+ *               for the rest of the call -- with status 1 if n_visible < min_samples and status 2 at a pivot that is not positive.
+ *   loop        `iterations` times sums and solve, then the sums of the final state.  With F = (C_g + C_p) / n_visible, an edge
+ *               whose F_final > F_initial is REVERTED to its initial state, status 3.  history [E][iterations + 1][5] float64 holds
+ *               n_visible, n_geo, C_g, n_photo, C_p of every evaluation.  status 0: refined.  status 4: an edge with i == j or an
+ *               index outside [0, N) -- the edge list is on the device, so the call cannot refuse it; the kernels read nothing
+ *               through it, its history is 0 and its outputs are its inputs.
+ * terms: bit 0 geometric, bit 1 photometric, bit 2 brightness (a, b unknowns); at least one of bits 0 and 1.
+ * colvo_refine_accumulate: the sums of one evaluation at the states given (gain / offset NULL: 1 and 0): out_sums [E][48] float64 (the
+ * 36, the 8, C_g, C_p, two zeros), out_counts [E][4] int32 (n_visible, n_geo, n_photo, 0).
+ * colvo_refine_edges: the whole loop; out_T [E][4][4] (last row 0 0 0 1), out_gain, out_offset [E] float64, status [E] int32.  out_T
+ * must not alias T_init.  No read-back and no host synchronisation.
+ * workspace: colvo_refine_workspace_bytes(E, N, H, W, iterations) bytes, 16-byte aligned, written by the call (the per-workgroup rows,
+ * the grey planes, the float32 states); 0 for what the calls refuse.  `iterations` is range-checked (0 .. 64) and otherwise reserved:
+ * the size does not depend on it today (colvo_refine_accumulate's workspace is the same size).
+ * Limits: E <= 65535, N <= 65535, H*W < 2^30, 1 <= iterations <= 64, sigma_geo, sigma_photo, gate_geo, gate_photo and max_depth
+ * finite and positive, damping >= 0 and finite, min_samples >= 1. */
+size_t colvo_refine_workspace_bytes(int E, int N, int H, int W, int iterations);
+int colvo_refine_accumulate(const float* depths, const float* frames, const float* K, int N, int H, int W, const int32_t* edges, int E,
+                            const double* T, const double* gain, const double* offset, float sigma_geo, float sigma_photo,
+                            float gate_geo, float gate_photo, int terms, float max_depth, void* workspace, double* out_sums,
+                            int32_t* out_counts, colvo_stream_t stream);
+int colvo_refine_edges(const float* depths, const float* frames, const float* K, int N, int H, int W, const int32_t* edges, int E,
+                       const double* T_init, int iterations, float sigma_geo, float sigma_photo, float gate_geo, float gate_photo,
+                       double damping, int min_samples, int terms, float max_depth, void* workspace, double* out_T, double* out_gain,
+                       double* out_offset, double* history, int32_t* status, colvo_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------- *
  * SURVEY.md §6  evaluation: depth error measures with per-image median scaling. *
