@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("COLVO_LIB_PATH") or os.path.join(_HERE, "lib", "libcolvo.so")
 
 F32, BF16 = 0, 1
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 
@@ -90,6 +90,8 @@ SIGNATURES = {
     "colvo_conv_bwd_fused_ok": (_i, [C.POINTER(ConvDesc)]),
     "colvo_conv_bwd_fused": (_i, [C.POINTER(ConvDesc), _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "colvo_conv_bwd_fused_head_rows": (_i, [C.POINTER(ConvDesc)]),
+    "colvo_conv_bwd_fused_scratch_bytes": (_sz, [C.POINTER(ConvDesc), _i]),
+    "colvo_conv_bwd_fused_det": (_i, [C.POINTER(ConvDesc), _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "colvo_depth_head_wgrad_reduce": (_i, [_vp, _i, _vp, _vp, _vp]),
     "colvo_depth_head_wgrad_mfma_rows": (_i, [_i, _i, _i]),
     "colvo_depth_head_wgrad_mfma": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),

@@ -22,6 +22,12 @@
 // A workgroup walks `tiles_per_wg` consecutive tiles; the next tile's patches are loaded into registers before the MFMAs of the
 // current one (as k_wgrad3x3 does).  The grid is capped (tuning: bwd16_wgs) because every workgroup ends with 2304 + 16 atomics on the
 // SAME addresses.
+// Two ways out of the weight / bias sums (template flag SLAB): the fp32 atomics above (colvo_conv_bwd_fused), or plain stores into
+// row blockIdx.x of a caller-owned scratch ([rows][16 * 9 * 16] weight slabs, then [rows][16] bias slabs: ColvoWgradSlabs), which
+// k_wgrad_reduce_group (csrc/wgrad.hip) then adds to dw / db in row order on the same stream (colvo_conv_bwd_fused_det): bitwise
+// repeatable; called without dw it leaves the rows to a reduction the caller orders).  Only the flush behind the last guard differs.
+// The deterministic training step runs mode 0 of this form since it exists (before, it ran the plain input gradient and k_wgrad3x3 +
+// k_wgrad_reduce instead of this pass) and adds the rows on a weight-gradient stream.
 //
 // The two products run as one pinned software pipeline (operands of step n + 1 requested before the MFMAs of step n); the HEAD form makes
 // its gradient patch by MFMA from the split d(pre) patch (make_g below).
@@ -56,6 +62,9 @@ struct Bwd16K {
     // HEAD form, optional: the head's own weight / bias gradient as well -- dWh[t][c] = sum_p dpre[p] y[p + t - 1][c], db_h = sum_p dpre[p]
     // -- as one partial row of 9 * 16 + 1 floats per WAVE (4 rows per workgroup) for the table reduction of csrc/misc.hip
     float* head_partials;
+    // SLAB way-out (colvo_conv_bwd_fused_det): workgroup r stores its sums into row r of [gridDim.x][16 * 9 * 16] weight slabs followed by
+    // [gridDim.x][16] bias slabs (the layout of ColvoWgradSlabs, include/colvo.h) instead of adding them to dw / db
+    float* slabs;
 };
 
 constexpr int DH = PH + 2, DW = PW + 2;                                      // d(pre) patch of the HEAD form: 12 x 20
@@ -69,7 +78,10 @@ constexpr int DH = PH + 2, DW = PW + 2;                                      // 
 #ifndef COLVO_BWD16_HEAD_WGS
 #define COLVO_BWD16_HEAD_WGS 4
 #endif
-template <int MODE>
+// SLAB: the way out of the weight / bias sums -- false: fp32 atomics on dw / db; true: plain stores into the workgroup's own slab row
+// (bitwise repeatable: k_wgrad_reduce_group adds the rows in row order).  Compile-time like MODE, and only the flush behind the last
+// guard differs: the tile loop, and with it the registers of a form, are the same either way.
+template <int MODE, bool SLAB = false>
 __global__ __launch_bounds__(NT, MODE == 2 ? 3 : MODE == 1 ? COLVO_BWD16_HEAD_WGS : 4) void k_bwd16(const Bwd16K a) {
     constexpr bool HEAD = MODE >= 1, headw = MODE == 2;
     __shared__ __attribute__((aligned(16))) char sG[NPIX * PIXB];
@@ -280,7 +292,7 @@ __global__ __launch_bounds__(NT, MODE == 2 ? 3 : MODE == 1 ? COLVO_BWD16_HEAD_WG
             __syncthreads();
         }
 
-        if (a.db) {
+        if (a.db) {                                                // (SLAB without db: the bias row is zeros)
             float s0 = 0.0f;
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
@@ -430,7 +442,12 @@ __global__ __launch_bounds__(NT, MODE == 2 ? 3 : MODE == 1 ? COLVO_BWD16_HEAD_WG
         const int tap = wave + 4 * fi;
         if (tap < 9) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) atomicAdd(a.dw + ((4 * kg + r) * 9 + tap) * 16 + l15, acc[2 + fi][r]);
+            for (int r = 0; r < 4; ++r) {
+                const int e = ((4 * kg + r) * 9 + tap) * 16 + l15;
+                // (every element of the row has one owner: taps 0..8 over the waves, 16 co x 16 ci over the lanes)
+                if constexpr (SLAB) a.slabs[(size_t)blockIdx.x * (16 * 9 * 16) + e] = acc[2 + fi][r];
+                else atomicAdd(a.dw + e, acc[2 + fi][r]);
+            }
         }
     }
     if constexpr (headw) {
@@ -444,7 +461,7 @@ __global__ __launch_bounds__(NT, MODE == 2 ? 3 : MODE == 1 ? COLVO_BWD16_HEAD_WG
             if (lane == 0) row[9 * 16] = hbs;
         }
     }
-    if (a.db) {
+    if (SLAB || a.db) {
         __syncthreads();
         sdb[tid] = dbacc;
         __syncthreads();
@@ -452,7 +469,8 @@ __global__ __launch_bounds__(NT, MODE == 2 ? 3 : MODE == 1 ? COLVO_BWD16_HEAD_WG
             float s = 0.0f;
 #pragma unroll
             for (int ph = 0; ph < 16; ++ph) s += sdb[ph * 16 + tid];
-            atomicAdd(a.db + tid, s);
+            if constexpr (SLAB) a.slabs[(size_t)gridDim.x * (16 * 9 * 16) + (size_t)blockIdx.x * 16 + tid] = s;
+            else atomicAdd(a.db + tid, s);
         }
     }
 }
@@ -703,6 +721,7 @@ extern "C" int colvo_conv_bwd_fused_ok(const ColvoConvDesc* d) {
 }
 
 // MODE as in k_bwd16 (0: dy given, 1: HEAD form, 2: HEAD form + the head's weight gradient)
+// (the slab forms of modes 0 and 1 take the grid of their atomic twins: one row of scratch per workgroup)
 static int bwd16_grid(const ColvoConvDesc* d, int mode, int* tiles_per_wg) {
     const int ntiles = d->B * ((d->Wi + TOW - 1) / TOW) * ((d->Hi + TOH - 1) / TOH);
     // grid: bwd16_wgs workgroups at 16 frames, more from 40 tiles per workgroup on, at most four times as many -- every workgroup ends
@@ -724,6 +743,28 @@ extern "C" int colvo_conv_bwd_fused_head_rows(const ColvoConvDesc* d) {
     return 4 * bwd16_grid(d, 2, nullptr);
 }
 
+// one launch of k_bwd16: the atomic form (slabs == nullptr) or the slab form; *rows = its grid
+static int bwd16_launch(const ColvoConvDesc* d, const void* dy, const void* w_bwd, const void* x, int relu_mask, void* dx, float* dw,
+                        float* db, const float* head_dpre, const float* head_w, float* head_partials, float* slabs, int* rows,
+                        hipStream_t stream) {
+    Bwd16K k{};
+    k.dy = (const char*)dy; k.x = (const char*)x; k.w_bwd = (const char*)w_bwd; k.dx = (char*)dx; k.dw = dw; k.db = db;
+    k.B = d->B; k.H = d->Hi; k.W = d->Wi; k.relu_mask = relu_mask;
+    k.tiles_x = (k.W + TOW - 1) / TOW; k.tiles_y = (k.H + TOH - 1) / TOH;
+    k.ntiles = k.B * k.tiles_x * k.tiles_y;
+    const int wgs = bwd16_grid(d, head_partials ? 2 : head_dpre ? 1 : 0, &k.tiles_per_wg);
+    k.dpre = head_dpre; k.head_w = head_w; k.head_partials = head_partials; k.slabs = slabs;
+    if (rows) *rows = wgs;
+    form_hit(FORM_BWD16);
+    if (slabs && head_dpre) colvo::launch(k_bwd16<1, true>, dim3((unsigned)wgs), dim3(NT), 0, stream, k);
+    else if (slabs) colvo::launch(k_bwd16<0, true>, dim3((unsigned)wgs), dim3(NT), 0, stream, k);
+    else if (head_partials) colvo::launch(k_bwd16<2>, dim3((unsigned)wgs), dim3(NT), 0, stream, k);
+    else if (head_dpre) colvo::launch(k_bwd16<1>, dim3((unsigned)wgs), dim3(NT), 0, stream, k);
+    else colvo::launch(k_bwd16<0>, dim3((unsigned)wgs), dim3(NT), 0, stream, k);
+    COLVO_CHECK_LAUNCH("k_bwd16");
+    return 0;
+}
+
 extern "C" int colvo_conv_bwd_fused(const ColvoConvDesc* d, const void* dy, const void* w_bwd, const void* x, int relu_mask, void* dx,
                                     float* dw, float* db, const float* head_dpre, const float* head_w, float* head_partials,
                                     colvo_stream_t stream) {
@@ -731,17 +772,35 @@ extern "C" int colvo_conv_bwd_fused(const ColvoConvDesc* d, const void* dy, cons
                     "colvo_conv_bwd_fused: null pointer argument");
     COLVO_CHECK_ARG(colvo_conv_bwd_fused_ok(d), "colvo_conv_bwd_fused: only bf16 16 -> 16 stride-1 layers over one directly stored source "
                                                 "below 1 GiB per tensor (colvo_conv_bwd_fused_ok)");
-    Bwd16K k{};
-    k.dy = (const char*)dy; k.x = (const char*)x; k.w_bwd = (const char*)w_bwd; k.dx = (char*)dx; k.dw = dw; k.db = db;
-    k.B = d->B; k.H = d->Hi; k.W = d->Wi; k.relu_mask = relu_mask;
-    k.tiles_x = (k.W + TOW - 1) / TOW; k.tiles_y = (k.H + TOH - 1) / TOH;
-    k.ntiles = k.B * k.tiles_x * k.tiles_y;
-    const int wgs = bwd16_grid(d, head_partials ? 2 : head_dpre ? 1 : 0, &k.tiles_per_wg);
-    k.dpre = head_dpre; k.head_w = head_w; k.head_partials = head_partials;
-    form_hit(FORM_BWD16);
-    if (head_partials) colvo::launch(k_bwd16<2>, dim3((unsigned)wgs), dim3(NT), 0, (hipStream_t)stream, k);
-    else if (head_dpre) colvo::launch(k_bwd16<1>, dim3((unsigned)wgs), dim3(NT), 0, (hipStream_t)stream, k);
-    else colvo::launch(k_bwd16<0>, dim3((unsigned)wgs), dim3(NT), 0, (hipStream_t)stream, k);
-    COLVO_CHECK_LAUNCH("k_bwd16");
-    return 0;
+    return bwd16_launch(d, dy, w_bwd, x, relu_mask, dx, dw, db, head_dpre, head_w, head_partials, nullptr, nullptr, (hipStream_t)stream);
+}
+
+// ---- deterministic form: slab rows + the fixed-tree reduction ----
+extern "C" size_t colvo_conv_bwd_fused_scratch_bytes(const ColvoConvDesc* d, int mode) {
+    if (!colvo_conv_bwd_fused_ok(d) || mode < 0 || mode > 1) return 0;
+    return (size_t)bwd16_grid(d, mode, nullptr) * (16 * 9 * 16 + 16) * sizeof(float);
+}
+
+extern "C" int colvo_conv_bwd_fused_det(const ColvoConvDesc* d, const void* dy, const void* w_bwd, const void* x, int relu_mask, void* dx,
+                                        float* dw, float* db, const float* head_dpre, const float* head_w, float* head_partials,
+                                        void* scratch, size_t scratch_bytes, colvo_stream_t stream) {
+    COLVO_CHECK_ARG(d && dy && w_bwd && x && dx && scratch && ((head_dpre == nullptr) == (head_w == nullptr)),
+                    "colvo_conv_bwd_fused_det: null pointer argument");
+    COLVO_CHECK_ARG(!head_partials, "colvo_conv_bwd_fused_det: the head's own weight gradient (head_partials) has no slab form");
+    COLVO_CHECK_ARG(colvo_conv_bwd_fused_ok(d), "colvo_conv_bwd_fused_det: only bf16 16 -> 16 stride-1 layers over one directly stored "
+                                                "source below 1 GiB per tensor (colvo_conv_bwd_fused_ok)");
+    const size_t need = colvo_conv_bwd_fused_scratch_bytes(d, head_dpre ? 1 : 0);
+    COLVO_CHECK_ARG(scratch_bytes >= need, "colvo_conv_bwd_fused_det: scratch of %zu bytes, %zu needed (colvo_conv_bwd_fused_scratch_bytes)",
+                    scratch_bytes, need);
+    COLVO_CHECK_ARG(((uintptr_t)scratch % 16) == 0 && ((uintptr_t)dw % 16) == 0 && ((uintptr_t)db % 16) == 0,
+                    "colvo_conv_bwd_fused_det: scratch, dw and db must be 16-byte aligned");
+    int rows = 0;
+    if (int e = bwd16_launch(d, dy, w_bwd, x, relu_mask, dx, dw, db, head_dpre, head_w, nullptr, (float*)scratch, &rows, (hipStream_t)stream))
+        return e;
+    // dw == NULL: the rows stay in the scratch for a colvo_wgrad_reduce_group that the caller orders behind this launch
+    if (!dw) return 0;
+    // the rows are added to dw / db in row order right behind the kernel, on its stream (the command is done when they are)
+    ColvoWgradSlabs set{};
+    set.scratch = scratch; set.dw = dw; set.db = db; set.nsplit = rows; set.Cout = 16; set.Ctot = 16;
+    return colvo_wgrad_reduce_group(&set, 1, stream);
 }

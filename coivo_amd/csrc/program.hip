@@ -135,6 +135,9 @@ static int run_one(const ColvoCmd& c, int k, colvo_stream_t s) {
         case COLVO_CMD_CONV_DGRAD_PLANES:
             return colvo_conv_dgrad_planes(&c.desc, c.p[0], (const float*)c.p[1], c.i[0], c.i[1], (float*)c.p[2], c.i[2], s);
         case COLVO_CMD_CONV_BWD_FUSED:
+            if (c.p[9]) return colvo_conv_bwd_fused_det(&c.desc, c.p[0], c.p[1], c.p[2], c.i[0], (void*)c.p[3], (float*)c.p[4], (float*)c.p[5],
+                                                        (const float*)c.p[6], (const float*)c.p[7], (float*)c.p[8], (void*)c.p[9],
+                                                        (size_t)(uint32_t)c.i[1], s);
             return colvo_conv_bwd_fused(&c.desc, c.p[0], c.p[1], c.p[2], c.i[0], (void*)c.p[3], (float*)c.p[4], (float*)c.p[5],
                                         (const float*)c.p[6], (const float*)c.p[7], (float*)c.p[8], s);
         case COLVO_CMD_CONV_HEAD_FUSED:

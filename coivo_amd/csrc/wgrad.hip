@@ -525,7 +525,18 @@ __global__ __launch_bounds__(NT) void k_wgrad_reduce_group(const ReduceGroup g) 
 #pragma unroll
         for (int u = 0; u < 8; ++u) t += v[u];
         (void)cnt;
-        for (int sp_i = s + 8 * e.sp; sp_i < e.nsplit; sp_i += e.sp) t += base[(long long)sp_i * e.n4];     // (more than 8 x 64 splits)
+        // more than 8 x 64 splits (the 732-1024 rows of colvo_conv_bwd_fused_det): further rounds of eight loads in flight, added in
+        // the same order as one dependent load per add would (which is what this loop was: ~1 us of L2 round trip per row beyond 512)
+        for (int sp0 = s + 8 * e.sp; sp0 < e.nsplit; sp0 += 8 * e.sp) {
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int sp_i = sp0 + u * e.sp;
+                if (sp_i < e.nsplit) v[u] = base[(long long)sp_i * e.n4];
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u)
+                if (sp0 + u * e.sp < e.nsplit) t += v[u];
+        }
     }
     if (e.sp > 1) {
         part[threadIdx.x] = t;

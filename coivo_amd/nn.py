@@ -811,9 +811,16 @@ class DepthNet(_ArenaModule):
             # The narrow full-resolution layer (iconv1) takes its input gradient and weight gradient in ONE pass over its input and
             # output (include/colvo.h colvo_conv_bwd_fused); in the training step's form of this call (gradient in parts) the head's
             # input gradient is made inside that pass as well (HEAD form) and never touches memory.
-            fuse1 = (not self.deterministic and not self.group_wgrad and ops.conv_bwd_fused_ok(P["iconv1"]) and
-                     _lib.dev_env("COLVO_NO_BWD16") is None)
-            fuse_head = fuse1 and parts is not None and _lib.dev_env("COLVO_NO_BWD16_HEAD") is None
+            # Deterministic mode takes the fused pass with the slab way-out (colvo_conv_bwd_fused_det): the workgroups' sums go to rows
+            # of a scratch and are added in row order by a reduction on a weight-gradient stream (below).  It keeps the head's input
+            # gradient g from the head's own kernel (mode 0): the HEAD form makes g by split-bf16 MFMA, 2^-16 relative in front of the bf16
+            # rounding, so which elements round up depends on the SCALE of the incoming gradient -- a step whose loss normaliser is
+            # applied by the optimizer instead (ddp.GradBuckets(defer_loss_normalisation=True)) then differs from the plain step in
+            # ~1 % of g's elements instead of ~1e-4 of them, and the two trajectories part (tests/test_ddp_gpu.py
+            # test_rccl_path_with_one_rank).  Developer switch COLVO_DET_BWD16_HEAD=1: the HEAD form all the same.
+            fuse1 = (not self.group_wgrad and ops.conv_bwd_fused_ok(P["iconv1"]) and _lib.dev_env("COLVO_NO_BWD16") is None)
+            fuse_head = (fuse1 and parts is not None and _lib.dev_env("COLVO_NO_BWD16_HEAD") is None and
+                         (not self.deterministic or _lib.dev_env("COLVO_DET_BWD16_HEAD") is not None))
             g = None if fuse_head else torch.empty_like(x1)
             # head: d(pre) + input gradient on the main stream, its weight gradient beside it like every other layer's
             if parts is None:
@@ -824,7 +831,7 @@ class DepthNet(_ArenaModule):
             # (the head's OWN weight gradient can ride along too -- colvo_conv_bwd_fused's head_partials -- and measured no gain: it
             # leaves the side streams, where it overlapped, for the main chain: 1.464 against 1.455 ms at configs[1], 3.729 against
             # 3.732 at the configs[3] shape; developer switch COLVO_BWD16_HEADW=1)
-            fuse_headw = fuse_head and _lib.dev_env("COLVO_BWD16_HEADW") is not None
+            fuse_headw = fuse_head and not self.deterministic and _lib.dev_env("COLVO_BWD16_HEADW") is not None
             if not fuse_headw:
                 if (self.compute_dtype == torch.bfloat16 and ops.depth_head_wgrad_mfma_ok(B, H, W) and
                         _lib.dev_env("COLVO_NO_HEAD_WGRAD_MFMA") is None):
@@ -844,16 +851,33 @@ class DepthNet(_ArenaModule):
                     # on the main stream: d_u is the next layer's dy
                     L = getattr(self, f"iconv{i}")
                     d_u = torch.empty_like(u)
+                    side_sum = False
                     if fuse_headw:
                         rows = ops.conv_bwd_fused_head_rows(Pi)
                         hp = torch.empty(rows * 145, device=dev, dtype=torch.float32)
                         ops.conv_bwd_fused(Pi, x1, L.w_bwd, u, True, d_u, L.g_master, L.g_bias, scratch, self.head.w_master, hp)
                         self._run_wgrad(self.head, lambda: ops.depth_head_wgrad_reduce(hp, rows, self.head.g_master, self.head.g_bias), hp)
-                    elif fuse_head:
-                        ops.conv_bwd_fused(Pi, x1, L.w_bwd, u, True, d_u, L.g_master, L.g_bias, scratch, self.head.w_master)
                     else:
-                        ops.conv_bwd_fused(Pi, g, L.w_bwd, u, True, d_u, L.g_master, L.g_bias)
-                    self._layer_done(L)
+                        # (deterministic: the slab rows -- a recorded pass keeps them, like the other deterministic scratch.  The
+                        # kernel runs here without dw: the rows are added below, on a weight-gradient stream)
+                        rows = ops.conv_bwd_fused_scratch(Pi, 1 if fuse_head else 0, dev) if self.deterministic else None
+                        side_sum = rows is not None and _lib.dev_env("COLVO_DET_BWD16_MAIN") is None
+                        dw1 = None if side_sum else L.g_master
+                        if fuse_head:
+                            ops.conv_bwd_fused(Pi, x1, L.w_bwd, u, True, d_u, dw1, L.g_bias, scratch, self.head.w_master, scratch=rows)
+                        else:
+                            ops.conv_bwd_fused(Pi, g, L.w_bwd, u, True, d_u, dw1, L.g_bias, scratch=rows)
+                    if side_sum:
+                        # The rows are added by a command of its own on a weight-gradient stream, like every other layer's second
+                        # launch, and iconv1 is reported done THERE, behind the reduction (_run_wgrad): the main chain goes on with
+                        # dx.  The next pass's k_bwd16, which overwrites the rows on the main stream, is ordered behind this
+                        # reduction by _order_deterministic_pass (a second backward pass joins the first one's side work in
+                        # deterministic mode) and by the optimizer's join.  (Developer switch COLVO_DET_BWD16_MAIN=1: the reduction
+                        # inside the command, on the main stream -- the B side of that measurement, profiles/det_bwd16_ab.md.)
+                        sets = [(rows, L.g_master, L.g_bias, rows.numel() // (16 * 9 * 16 + 16), 16, 16)]
+                        self._run_wgrad(L, lambda: ops.wgrad_reduce_group(sets), rows)
+                    else:
+                        self._layer_done(L)
                     below = A[f"iconv{i + 1}"] if i < 5 else A["enc5b"]
                     wgrad(f"up{i}", below, None, d_u)
                     g = dgrad(f"up{i}", 0, d_u, below)

@@ -98,13 +98,26 @@ def conv_bwd_fused_ok(d: ConvDesc) -> bool:
     return bool(_lib.load().colvo_conv_bwd_fused_ok(C.byref(d)))
 
 
-def conv_bwd_fused(d: ConvDesc, dy, w_bwd, x, relu_mask: bool, dx, dw, db, head_dpre=None, head_w=None, head_partials=None) -> None:
+def conv_bwd_fused(d: ConvDesc, dy, w_bwd, x, relu_mask: bool, dx, dw, db, head_dpre=None, head_w=None, head_partials=None,
+                   scratch: Optional[torch.Tensor] = None) -> None:
     """Input gradient (written to dx, masked by x > 0 when relu_mask) and weight / bias gradient (added to dw / db) of a qualifying
     narrow layer in one pass (include/colvo.h colvo_conv_bwd_fused).  head_dpre / head_w: the HEAD form -- `dy` is the layer's
     OUTPUT and the gradient is made on the fly from the depth head's d(pre) plane and weights; head_partials
-    ([conv_bwd_fused_head_rows(d), 145] floats): the head's own weight gradient as partial rows for depth_head_wgrad_reduce."""
-    _need_cuda(dy, w_bwd, x, dx, dw, db, head_dpre, head_w, head_partials)
-    _issue(_lib.CMD_CONV_BWD_FUSED, d, (dy, w_bwd, x, dx, dw, db, head_dpre, head_w, head_partials), (int(relu_mask),))
+    ([conv_bwd_fused_head_rows(d), 145] floats): the head's own weight gradient as partial rows for depth_head_wgrad_reduce.
+    With `scratch` (conv_bwd_fused_scratch) the deterministic form: one slab row per workgroup + the fixed-order reduction behind the
+    kernel instead of float atomics (colvo_conv_bwd_fused_det; not with head_partials); with dw None the rows stay in `scratch`
+    (db only says whether bias rows are wanted) until wgrad_reduce_group([(scratch, dw, db, scratch.numel() // 2320, 16, 16)])."""
+    _need_cuda(dy, w_bwd, x, dx, dw, db, head_dpre, head_w, head_partials, scratch)
+    nb = 0 if scratch is None else scratch.numel() * scratch.element_size()
+    _issue(_lib.CMD_CONV_BWD_FUSED, d, (dy, w_bwd, x, dx, dw, db, head_dpre, head_w, head_partials, scratch), (int(relu_mask), nb))
+
+
+def conv_bwd_fused_scratch(d: ConvDesc, mode: int, device) -> torch.Tensor:
+    """Scratch for the deterministic form of conv_bwd_fused; mode 0: dy given, 1: HEAD form (colvo_conv_bwd_fused_scratch_bytes)."""
+    n = _lib.load().colvo_conv_bwd_fused_scratch_bytes(C.byref(d), int(mode))
+    if n == 0:
+        raise RuntimeError("colvo_conv_bwd_fused_scratch_bytes: the layer or the mode has no deterministic fused backward")
+    return torch.empty(n // 4, device=device, dtype=torch.float32)
 
 
 def conv_bwd_fused_head_rows(d: ConvDesc) -> int:

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define COLVO_ABI_VERSION 17
+#define COLVO_ABI_VERSION 18
 
 typedef void* colvo_stream_t; /* hipStream_t */
 
@@ -224,7 +224,7 @@ int colvo_pack_stem_pose(const float* frames, int B2, int H, int W, void* stem, 
  * stride 1, one directly stored source -- DepthNet's iconv1.  Both backward kernels of such a layer are HBM-bound and read the same
  * two tensors (dy with a halo; the layer's input x as ReLU mask of dx and as second operand of dw): fused, the layer's backward is 3
  * tensor passes instead of 5.  dx = (relu_mask ? x > 0 : 1) * (dy (*) w_bwd), written (not added); dw / db are ADDED to (fp32
- * atomics: use the separate calls where bitwise repeatability is wanted).  colvo_conv_bwd_fused_ok: 1 when the layer qualifies. */
+ * atomics: colvo_conv_bwd_fused_det is the bitwise repeatable form).  colvo_conv_bwd_fused_ok: 1 when the layer qualifies. */
 int colvo_conv_bwd_fused_ok(const ColvoConvDesc* d);
 /* head_dpre / head_w (both or neither): the HEAD form for the layer in front of the 3x3 16 -> 1 depth head.  `dy` is then NOT the
  * gradient but the layer's OUTPUT y (post-ReLU) and the gradient is made on the fly from the head's d(pre) plane [B][H][W] (what
@@ -237,6 +237,22 @@ int colvo_conv_bwd_fused_ok(const ColvoConvDesc* d);
 int colvo_conv_bwd_fused(const ColvoConvDesc* d, const void* dy, const void* w_bwd, const void* x, int relu_mask, void* dx, float* dw,
                          float* db, const float* head_dpre, const float* head_w, float* head_partials, colvo_stream_t stream);
 int colvo_conv_bwd_fused_head_rows(const ColvoConvDesc* d);
+/* Deterministic form of colvo_conv_bwd_fused: the same pass, but workgroup r STORES its weight / bias sums into row r of `scratch`
+ * ([rows][16 * 9 * 16] weight slabs, then [rows][16] bias slabs -- the layout of ColvoWgradSlabs below; every row is written in full,
+ * no initialisation needed) and the fixed-tree reduction of colvo_wgrad_reduce_group then ADDS the rows to dw / db in row order, on the
+ * same stream right behind the kernel: two launches, no fp32 atomic, bitwise repeatable.  dx is what the atomic form writes, bit for
+ * bit.  rows = the launch's grid, a function of (B, H, W), the form and the tuning table alone.  mode: 0 (dy given) or 1 (HEAD form:
+ * head_dpre / head_w); head_partials must be NULL -- the head's own weight gradient has no slab form.
+ * colvo_conv_bwd_fused_scratch_bytes: rows * 2320 * 4, or 0 for a layer colvo_conv_bwd_fused_ok refuses or another mode; no HIP call,
+ * nothing counted.  scratch, dw and db must be 16-byte aligned; a scratch below that size is refused before any launch.
+ * dw == NULL: the kernel alone -- dx is written and the rows are left in `scratch` (bias rows hold the sums with db != NULL, which is
+ * not written; zeros otherwise); a later colvo_wgrad_reduce_group with {scratch, dw, db, nsplit = scratch bytes / 9280, Cout = 16,
+ * Ctot = 16} adds them, on whichever stream the caller orders behind this one (the training step: a weight-gradient stream, like
+ * every other layer's second launch).  The scratch must not be written again before that reduction has run. */
+size_t colvo_conv_bwd_fused_scratch_bytes(const ColvoConvDesc* d, int mode);
+int colvo_conv_bwd_fused_det(const ColvoConvDesc* d, const void* dy, const void* w_bwd, const void* x, int relu_mask, void* dx,
+                             float* dw, float* db, const float* head_dpre, const float* head_w, float* head_partials, void* scratch,
+                             size_t scratch_bytes, colvo_stream_t stream);
 int colvo_depth_head_wgrad_reduce(const float* partials, int rows, float* dw, float* db, colvo_stream_t stream);
 /* The 16-channel depth head's weight / bias gradient by MFMA (bf16 feature maps): partial rows ([colvo_depth_head_wgrad_mfma_rows(B, H,
  * W)][9 * 16 + 1] floats, plain stores) from y [B][H][W][16] and the d(pre) plane, then colvo_depth_head_wgrad_reduce.  d(pre) enters
@@ -676,7 +692,8 @@ enum {
     COLVO_CMD_CONV_DGRAD_BOTH,    /* p: dy w_bwd relu_mask0 relu_mask1 dx0 dx1 */
     COLVO_CMD_WGRAD_REDUCE_GROUP, /* p: sets (HOST pointer to ColvoWgradSlabs[n], alive as long as the list); i: n */
     COLVO_CMD_CONV_DGRAD_PLANES,  /* p: dy w_master dst; i: c_begin c_count accumulate */
-    COLVO_CMD_CONV_BWD_FUSED,     /* p: dy w_bwd x dx dw db head_dpre head_w head_partials; i: relu_mask */
+    COLVO_CMD_CONV_BWD_FUSED,     /* p: dy w_bwd x dx dw db head_dpre head_w head_partials scratch; i: relu_mask scratch_bytes
+                                   * (p[9] scratch != NULL: colvo_conv_bwd_fused_det; with p[4] dw == NULL the rows stay in the scratch) */
     COLVO_CMD_HEAD_WGRAD_REDUCE,  /* p: partials dw db; i: rows */
     COLVO_CMD_CONV_HEAD_FUSED,    /* p: x w_fwd bias head_w head_b y depth pose_in; f: min_depth max_depth */
     COLVO_CMD_PACK_STEM_POSE,     /* p: frames stem pose_in; i: B2 H W */
