@@ -1,0 +1,537 @@
+// cloud.hip -- exact truncated nearest neighbours between two point clouds: for every point of a query cloud the
+// squared distance to, and the index of, the nearest point of a reference cloud within max_dist, and exact integer statistics over
+// the query cloud.  Contract: include/colvo.h (colvo_cloud_*); NumPy replica tests/cloud_ref.py.
+//
+//   build   k_cloud_bounds: bounding box of the valid reference points, integer max on an order-preserving map of the float bits.
+//           k_cloud_grid: one thread turns the box into origin, cell edge and dims, in a device header the later kernels read.
+//           k_cloud_hist: one thread per point, 32-bit integer add into its cell's count; the value the add returns is the point's
+//           rank in its cell.  An ordered scan over the cells (chunk sums, one scan over them, in-chunk scan: fuse.hip's pattern,
+//           restated because the entry count lives on the device here).  k_cloud_scatter: 16-byte records (x, y, z, original index)
+//           to start[cell] + rank.  The order inside a cell follows the atomics; no output depends on it.
+//   query   k_cloud_query: one lane per query; the 9 x-runs of up to 3 cells around the query's cell are contiguous in the sorted
+//           records; the minimum of the 64-bit keys (bits(d2) << 32) | index stays in registers.  Statistics are reduced per
+//           workgroup and added to one of 256 counter lines; k_cloud_stats sums the lines.
+//
+// Every hand-off between phases is a kernel boundary.  The minimum of a set does not depend on the order it is taken in and every
+// sum is an unsigned integer, so a call's bits do not depend on scheduling or on the stream.  The arithmetic that decides a distance,
+// a cell or a quantum is pinned: float32, every operation individually rounded -- contraction is off for this whole file.
+#include <float.h>
+
+#include "common.h"
+
+#pragma clang fp contract(off)
+
+namespace colvo {
+namespace {
+
+constexpr int NT = 256;
+constexpr int AXIS_LIMIT = 128;                          // cells per axis, at most
+constexpr float AXIS_DIV = 126.0f;                       // edge >= extent / AXIS_DIV: floor(126 * (1 + 3 * 2^-24)) + 1 <= 128
+constexpr int MAX_CELLS = AXIS_LIMIT * AXIS_LIMIT * AXIS_LIMIT;
+constexpr float EDGE_MARGIN = 1.0f + 1.0f / 1024.0f;     // edge >= max_dist * (1 + 2^-10): DESIGN.md §3.6h
+constexpr int CHUNK_PER_THREAD = 16;
+constexpr int CHUNK = NT * CHUNK_PER_THREAD;             // entries one workgroup scans
+constexpr int SCAN_ENTRIES = MAX_CELLS + 1;              // the cells and one entry behind them: its prefix is the record count
+constexpr int SCAN_CHUNKS = (SCAN_ENTRIES + CHUNK - 1) / CHUNK;
+constexpr int COUNTER_LINES = 256;                       // the query's statistics: this many rows of N_STATS 64-bit words,
+constexpr int COUNTER_PITCH = 16;                        // ... 128 bytes apart (one hot address measured 41 x slower: §3.6c (c))
+constexpr int N_STATS = 12;
+constexpr int MAX_THRESHOLDS = 8;
+constexpr int BOUNDS_MAX_BLOCKS = 1024;
+constexpr int MAX_POINTS = 1 << 30;
+
+struct Header {                            // the head of the workspace: written by the build, read by the query
+    uint32_t key[6];                       // ordered keys: ~min x, y, z and max x, y, z (all of them gathered with atomicMax)
+    uint32_t n_valid;                      // valid reference points
+    uint32_t single;                       // the box has no finite grid: one cell, searched whole
+    float o[3];                            // the box's lower corner
+    float inv;                             // float32(1) / edge
+    int n[3];                              // cells per axis
+    int cells;                             // 0: no valid reference point
+};
+static_assert(sizeof(Header) == 64, "Header is 64 B");
+
+struct Grid {                              // the header's geometry, wave-uniform
+    float o[3], inv;
+    int n[3], cells;
+    bool single;
+};
+
+struct Thresholds {
+    float t2[MAX_THRESHOLDS];              // float32(tau) * float32(tau)
+    int n;
+};
+
+struct Sim3 {
+    float r[9], t[3], s;
+};
+
+__device__ __forceinline__ bool finite_f(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
+
+// order-preserving map of the float bits onto unsigned integers, and back
+__device__ __forceinline__ uint32_t okey(float f) {
+    const uint32_t b = __float_as_uint(f);
+    return b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u);
+}
+__device__ __forceinline__ float okey_inv(uint32_t k) { return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xffffffffu)); }
+
+__device__ __forceinline__ Grid load_grid(const Header* __restrict__ h) {
+    Grid G;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        G.o[a] = uniform_f(h->o[a]);
+        G.n[a] = __builtin_amdgcn_readfirstlane(h->n[a]);
+    }
+    G.inv = uniform_f(h->inv);
+    G.cells = __builtin_amdgcn_readfirstlane(h->cells);
+    G.single = __builtin_amdgcn_readfirstlane((int)h->single) != 0;
+    // whatever the header holds, no index below leaves the cell arrays
+    G.cells = min(max(G.cells, 0), MAX_CELLS);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) G.n[a] = min(max(G.n[a], 1), AXIS_LIMIT);
+    if ((long long)G.n[0] * G.n[1] * G.n[2] > (long long)G.cells) G.cells = 0;
+    return G;
+}
+
+// The pinned cell coordinate of one axis: ((x - o) * inv), floored by the callers.
+__device__ __forceinline__ float grid_coord(const Grid& G, int a, float x) { return (x - G.o[a]) * G.inv; }
+
+// cell of a VALID reference point; the clamp never acts on a point of the box the grid was made from (the dims come from the same
+// routine, which is monotone) and turns the NaN of an unbounded box (G.single: inf * 0) into cell 0
+__device__ __forceinline__ int ref_cell(const Grid& G, float x, float y, float z) {
+    const float p[3] = {x, y, z};
+    int c[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) c[a] = (int)fminf(fmaxf(floorf(grid_coord(G, a, p[a])), 0.0f), (float)(G.n[a] - 1));
+    return (c[2] * G.n[1] + c[1]) * G.n[0] + c[0];
+}
+
+// ---- build ------------------------------------------------------------------------------------------------------------------- //
+// grid min(ceil(M / NT), BOUNDS_MAX_BLOCKS), grid-stride: six integer maxima and a count per workgroup
+__global__ __launch_bounds__(NT) void k_cloud_bounds(const float* __restrict__ P, int M, Header* __restrict__ h) {
+    __shared__ uint32_t sm[NT / 64][7];
+    uint32_t k[6] = {0u, 0u, 0u, 0u, 0u, 0u};
+    uint32_t n = 0u;
+    for (long long i = (long long)blockIdx.x * NT + threadIdx.x; i < M; i += (long long)gridDim.x * NT) {
+        const float x = P[i * 3 + 0], y = P[i * 3 + 1], z = P[i * 3 + 2];
+        if (!(finite_f(x) && finite_f(y) && finite_f(z))) continue;
+        const float p[3] = {x, y, z};
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const uint32_t q = okey(p[a]);
+            k[a] = max(k[a], ~q);
+            k[3 + a] = max(k[3 + a], q);
+        }
+        ++n;
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+#pragma unroll
+        for (int j = 0; j < 6; ++j) k[j] = max(k[j], (uint32_t)__shfl_xor((int)k[j], off));
+        n += (uint32_t)__shfl_xor((int)n, off);
+    }
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int j = 0; j < 6; ++j) sm[threadIdx.x >> 6][j] = k[j];
+        sm[threadIdx.x >> 6][6] = n;
+    }
+    __syncthreads();
+    if (threadIdx.x < 7) {
+        const int j = threadIdx.x;
+        if (j < 6) {
+            const uint32_t v = max(max(sm[0][j], sm[1][j]), max(sm[2][j], sm[3][j]));
+            if ((sm[0][6] + sm[1][6]) + (sm[2][6] + sm[3][6]) != 0u) atomicMax(&h->key[j], v);
+        } else {
+            const uint32_t v = (sm[0][6] + sm[1][6]) + (sm[2][6] + sm[3][6]);
+            if (v) atomicAdd(&h->n_valid, v);
+        }
+    }
+}
+
+// one thread: the box -> origin, edge, dims
+__global__ void k_cloud_grid(Header* __restrict__ h, float max_dist) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    if (h->n_valid == 0u) return;                                // the header was cleared: cells = 0
+    float lo[3], hi[3], ext = 0.0f;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        lo[a] = okey_inv(~h->key[a]);
+        hi[a] = okey_inv(h->key[3 + a]);
+        ext = fmaxf(ext, hi[a] - lo[a]);
+    }
+    const float edge = fmaxf(max_dist * EDGE_MARGIN, __fdiv_rn(ext, AXIS_DIV));
+    const float inv = __fdiv_rn(1.0f, edge);
+    const bool single = !(finite_f(ext) && finite_f(edge) && finite_f(inv) && inv > 0.0f);
+    int cells = 1;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        h->o[a] = lo[a];
+        int n = 1;
+        if (!single) n = (int)fminf(fmaxf(floorf((hi[a] - lo[a]) * inv), 0.0f), (float)(AXIS_LIMIT - 1)) + 1;
+        h->n[a] = n;
+        cells *= n;
+    }
+    h->inv = single ? 0.0f : inv;
+    h->single = single ? 1u : 0u;
+    h->cells = cells;
+}
+
+// one thread per reference point: count[cell] += 1; the value before the add is the point's rank in its cell (-1: invalid point)
+__global__ __launch_bounds__(NT) void k_cloud_hist(const float* __restrict__ P, int M, const Header* __restrict__ h,
+                                                   int32_t* __restrict__ count, int32_t* __restrict__ rank) {
+    const Grid G = load_grid(h);
+    const long long i = (long long)blockIdx.x * NT + threadIdx.x;
+    if (i >= M) return;
+    const float x = P[i * 3 + 0], y = P[i * 3 + 1], z = P[i * 3 + 2];
+    int r = -1;
+    if (G.cells > 0 && finite_f(x) && finite_f(y) && finite_f(z)) r = atomicAdd(&count[ref_cell(G, x, y, z)], 1);
+    rank[i] = r;
+}
+
+__device__ __forceinline__ int block_sum(int v, int* sm) {       // sum over the workgroup, in every thread
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (sm[0] + sm[1]) + (sm[2] + sm[3]);
+}
+
+// The scan runs over the header's cells + 1 entries; the launches are sized for SCAN_ENTRIES and the workgroups beyond the count leave.
+__device__ __forceinline__ int scan_entries(const Header* __restrict__ h) {
+    return min(max(__builtin_amdgcn_readfirstlane(h->cells), 0), MAX_CELLS) + 1;
+}
+
+// grid SCAN_CHUNKS: sums[chunk] = sum of the chunk's entries
+__global__ __launch_bounds__(NT) void k_cloud_chunk_sum(const int32_t* __restrict__ in, const Header* __restrict__ h,
+                                                        int32_t* __restrict__ sums) {
+    __shared__ int sm[NT / 64];
+    const int n = scan_entries(h);
+    const int base = blockIdx.x * CHUNK;
+    if (base >= n) return;
+    int s = 0;
+#pragma unroll
+    for (int r = 0; r < CHUNK_PER_THREAD; ++r) {
+        const int i = base + r * NT + threadIdx.x;
+        if (i < n) s += in[i];
+    }
+    s = block_sum(s, sm);
+    if (threadIdx.x == 0) sums[blockIdx.x] = s;
+}
+
+// one workgroup: exclusive scan of the chunk sums in place
+__global__ __launch_bounds__(NT) void k_cloud_scan(int32_t* __restrict__ sums, const Header* __restrict__ h) {
+    __shared__ int part[NT];
+    const int n = (scan_entries(h) + CHUNK - 1) / CHUNK;         // <= SCAN_CHUNKS
+    const int per = (n + NT - 1) / NT;
+    const int lo = min((int)threadIdx.x * per, n), hi = min(lo + per, n);
+    int s = 0;
+    for (int i = lo; i < hi; ++i) s += sums[i];
+    part[threadIdx.x] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int run = 0;
+        for (int i = 0; i < NT; ++i) { const int t = part[i]; part[i] = run; run += t; }
+    }
+    __syncthreads();
+    int run = part[threadIdx.x];
+    for (int i = lo; i < hi; ++i) { const int t = sums[i]; sums[i] = run; run += t; }
+}
+
+// grid SCAN_CHUNKS: entry i becomes the sum of the entries before it
+__global__ __launch_bounds__(NT) void k_cloud_chunk_scan(int32_t* __restrict__ data, const Header* __restrict__ h,
+                                                         const int32_t* __restrict__ offsets) {
+    __shared__ int wsum[NT / 64];
+    const int n = scan_entries(h);
+    if (blockIdx.x * CHUNK >= n) return;
+    const int base = blockIdx.x * CHUNK + threadIdx.x * CHUNK_PER_THREAD;      // 16 consecutive entries per thread
+    int v[CHUNK_PER_THREAD];
+    int s = 0;
+#pragma unroll
+    for (int r = 0; r < CHUNK_PER_THREAD; ++r) {
+        v[r] = base + r < n ? data[base + r] : 0;
+        s += v[r];
+    }
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    int inc = s;                                                                // inclusive scan over the wave
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int t = __shfl_up(inc, off);
+        if (lane >= off) inc += t;
+    }
+    if (lane == 63) wsum[wv] = inc;
+    __syncthreads();
+    int run = offsets[blockIdx.x] + inc - s;
+    for (int i = 0; i < wv; ++i) run += wsum[i];
+#pragma unroll
+    for (int r = 0; r < CHUNK_PER_THREAD; ++r) {
+        if (base + r >= n) break;
+        data[base + r] = run;
+        run += v[r];
+    }
+}
+
+// one thread per reference point: its record goes to start[cell] + rank
+__global__ __launch_bounds__(NT) void k_cloud_scatter(const float* __restrict__ P, int M, const Header* __restrict__ h,
+                                                      const int32_t* __restrict__ start, const int32_t* __restrict__ rank,
+                                                      float4* __restrict__ rec) {
+    const Grid G = load_grid(h);
+    const long long i = (long long)blockIdx.x * NT + threadIdx.x;
+    if (i >= M) return;
+    const int r = rank[i];
+    if (r < 0 || G.cells <= 0) return;
+    const float x = P[i * 3 + 0], y = P[i * 3 + 1], z = P[i * 3 + 2];
+    const long long pos = (long long)start[ref_cell(G, x, y, z)] + r;
+    if (pos >= 0 && pos < M) rec[pos] = make_float4(x, y, z, __int_as_float((int)i));       // (always, for the counts of this build)
+}
+
+// ---- query ------------------------------------------------------------------------------------------------------------------- //
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, off), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), off);
+        v += ((unsigned long long)hi << 32) | lo;
+    }
+    return v;
+}
+
+// grid ceil(N / NT), one lane per query
+__global__ __launch_bounds__(NT) void k_cloud_query(const float* __restrict__ Q, int N, const Header* __restrict__ h,
+                                                    const int32_t* __restrict__ start, const float4* __restrict__ rec, int M,
+                                                    float md2, float s, Thresholds thr, float* __restrict__ dist,
+                                                    float* __restrict__ dist2, int32_t* __restrict__ nearest,
+                                                    unsigned long long* __restrict__ counters) {
+    __shared__ unsigned long long sm[NT / 64][N_STATS];
+    const Grid G = load_grid(h);
+    const long long i = (long long)blockIdx.x * NT + threadIdx.x;
+    const bool in = i < N;
+    float q[3] = {0.0f, 0.0f, 0.0f};
+    if (in) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) q[a] = Q[i * 3 + a];
+    }
+    const bool valid = in && finite_f(q[0]) && finite_f(q[1]) && finite_f(q[2]);
+    unsigned long long best = ((unsigned long long)__float_as_uint(md2) << 32) | 0xffffffffull;
+    unsigned long long examined = 0ull;
+    bool walk = valid && G.cells > 0;
+    int c[3] = {0, 0, 0};
+    if (walk && !G.single) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const float g = grid_coord(G, a, q[a]);
+            // more than a cell outside the box: nothing within reach (and no integer is made of a coordinate out of range)
+            walk = walk && g >= -1.0f && g < (float)G.n[a] + 1.0f;
+            c[a] = walk ? (int)floorf(g) : 0;                   // -1 .. n
+        }
+    }
+    if (walk) {
+        const int x0 = max(c[0] - 1, 0), x1 = min(c[0] + 1, G.n[0] - 1);
+        const int y0 = max(c[1] - 1, 0), y1 = min(c[1] + 1, G.n[1] - 1);
+        const int z0 = max(c[2] - 1, 0), z1 = min(c[2] + 1, G.n[2] - 1);
+        if (x0 <= x1) {
+            for (int z = z0; z <= z1; ++z) {
+                for (int y = y0; y <= y1; ++y) {
+                    const int base = (z * G.n[1] + y) * G.n[0];          // < cells <= MAX_CELLS
+                    const int b = max(start[base + x0], 0), e = min(start[base + x1 + 1], M);
+                    for (int j = b; j < e; ++j) {
+                        const float4 r = rec[j];
+                        const float dx = q[0] - r.x, dy = q[1] - r.y, dz = q[2] - r.z;
+                        const float d2 = ((dx * dx + dy * dy) + dz * dz);
+                        const unsigned long long key = ((unsigned long long)__float_as_uint(d2) << 32) | (uint32_t)__float_as_int(r.w);
+                        if (d2 < md2 && key < best) best = key;
+                    }
+                    if (e > b) examined += (unsigned long long)(e - b);
+                }
+            }
+        }
+    }
+    const float d2v = __uint_as_float((uint32_t)(best >> 32));
+    const float dv = sqrtf(d2v);                             // correctly rounded (the build keeps HIP's default for sqrt and division)
+    const int idx = (int)(uint32_t)best;
+    if (in) {
+        dist[i] = dv;
+        dist2[i] = d2v;
+        nearest[i] = idx;
+    }
+    // statistics: per wave, per workgroup, then one add per word into this workgroup's counter line
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    unsigned long long st[N_STATS];
+    st[0] = (unsigned long long)__popcll(__ballot(valid));
+    st[1] = (unsigned long long)__popcll(__ballot(valid && idx >= 0));
+#pragma unroll
+    for (int k = 0; k < MAX_THRESHOLDS; ++k) st[2 + k] = (unsigned long long)__popcll(__ballot(valid && k < thr.n && d2v < thr.t2[k]));
+    st[10] = wave_sum_u64(valid ? (unsigned long long)(uint32_t)rintf(dv * s) : 0ull);
+    st[11] = wave_sum_u64(examined);
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < N_STATS; ++k) sm[wv][k] = st[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < N_STATS) {
+        const unsigned long long v = (sm[0][threadIdx.x] + sm[1][threadIdx.x]) + (sm[2][threadIdx.x] + sm[3][threadIdx.x]);
+        if (v) atomicAdd(&counters[(size_t)(blockIdx.x % COUNTER_LINES) * COUNTER_PITCH + threadIdx.x], v);
+    }
+}
+
+// one workgroup: stats[k] = sum over the counter lines
+__global__ void k_cloud_stats(const unsigned long long* __restrict__ counters, unsigned long long* __restrict__ stats) {
+    if (threadIdx.x >= N_STATS) return;
+    unsigned long long s = 0ull;
+    for (int l = 0; l < COUNTER_LINES; ++l) s += counters[(size_t)l * COUNTER_PITCH + threadIdx.x];
+    stats[threadIdx.x] = s;
+}
+
+// one thread per point
+__global__ __launch_bounds__(NT) void k_cloud_transform(const float* P, int N, Sim3 T, float* out) {      // (out may be P)
+    const long long i = (long long)blockIdx.x * NT + threadIdx.x;
+    if (i >= N) return;
+    const float x = P[i * 3 + 0], y = P[i * 3 + 1], z = P[i * 3 + 2];
+    float o[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) o[a] = ((T.s * ((T.r[a * 3 + 0] * x + T.r[a * 3 + 1] * y) + T.r[a * 3 + 2] * z)) + T.t[a]);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) out[i * 3 + a] = o[a];
+}
+
+// ---- host side --------------------------------------------------------------------------------------------------------------- //
+size_t pad16(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
+bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+struct Ws {                                // header, counter lines, cell starts, chunk sums, records [M], ranks [M]
+    Header* header;
+    unsigned long long* counters;
+    int32_t* cells;
+    int32_t* sums;
+    float4* rec;
+    int32_t* rank;
+    size_t bytes;
+};
+
+Ws layout(void* base, int M) {
+    Ws w;
+    char* c = static_cast<char*>(base);
+    w.header = reinterpret_cast<Header*>(c);
+    c += 256;
+    w.counters = reinterpret_cast<unsigned long long*>(c);
+    c += (size_t)COUNTER_LINES * COUNTER_PITCH * 8;
+    w.cells = reinterpret_cast<int32_t*>(c);
+    c += pad16((size_t)SCAN_ENTRIES * 4);
+    w.sums = reinterpret_cast<int32_t*>(c);
+    c += pad16((size_t)SCAN_CHUNKS * 4);
+    w.rec = reinterpret_cast<float4*>(c);
+    c += (size_t)M * 16;
+    w.rank = reinterpret_cast<int32_t*>(c);
+    c += pad16((size_t)M * 4);
+    w.bytes = (size_t)(c - static_cast<char*>(base));
+    return w;
+}
+
+bool good_sizes(int N, int M) { return N >= 0 && M >= 0 && N < MAX_POINTS && M < MAX_POINTS; }
+
+// max_dist finite and positive with a finite, normal square; md2 and the quantum scale, each rounded once
+bool good_max_dist(float max_dist, float& md2, float& scale) {
+    if (!(max_dist > 0.0f) || !(max_dist < __builtin_inff())) return false;
+    md2 = max_dist * max_dist;
+    scale = 1048576.0f / max_dist;
+    return md2 >= FLT_MIN && md2 < __builtin_inff() && scale < __builtin_inff();
+}
+
+int blocks_of(int n) { return (n + NT - 1) / NT; }
+
+}  // namespace
+}  // namespace colvo
+
+using namespace colvo;
+
+#define COLVO_CHECK_HIP(call, name)                                                       \
+    do {                                                                                  \
+        hipError_t e_ = (call);                                                           \
+        if (e_ != hipSuccess) {                                                           \
+            ::colvo::set_error("%s: %s failed: %s", name, #call, hipGetErrorString(e_)); \
+            return (int)e_;                                                               \
+        }                                                                                 \
+    } while (0)
+
+extern "C" size_t colvo_cloud_workspace_bytes(int N, int M) {
+    if (!good_sizes(N, M)) return 0;
+    return layout(nullptr, M).bytes;
+}
+
+extern "C" int colvo_cloud_index_build(const float* ref, int M, float max_dist, void* workspace, colvo_stream_t stream) {
+    COLVO_CHECK_ARG(workspace && (ref || M == 0), "colvo_cloud_index_build: null pointer argument");
+    COLVO_CHECK_ARG(good_sizes(0, M), "colvo_cloud_index_build: bad shape M=%d (0 .. 2^30 - 1)", M);
+    float md2, scale;
+    COLVO_CHECK_ARG(good_max_dist(max_dist, md2, scale),
+                    "colvo_cloud_index_build: bad max_dist %g (finite, positive, with a finite positive float32 square)", (double)max_dist);
+    COLVO_CHECK_ARG(aligned16(workspace), "colvo_cloud_index_build: workspace must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    const Ws w = layout(workspace, M);
+    COLVO_CHECK_HIP(hipMemsetAsync(w.header, 0, sizeof(Header), s), "colvo_cloud_index_build");
+    if (M == 0) return 0;                                        // cells = 0: the query walks nothing
+    COLVO_CHECK_HIP(hipMemsetAsync(w.cells, 0, (size_t)SCAN_ENTRIES * 4, s), "colvo_cloud_index_build");
+    const int nb = blocks_of(M);
+    colvo::launch(k_cloud_bounds, dim3(nb < BOUNDS_MAX_BLOCKS ? nb : BOUNDS_MAX_BLOCKS), dim3(NT), 0, s, ref, M, w.header);
+    COLVO_CHECK_LAUNCH("k_cloud_bounds");
+    colvo::launch(k_cloud_grid, dim3(1), dim3(64), 0, s, w.header, max_dist);
+    COLVO_CHECK_LAUNCH("k_cloud_grid");
+    colvo::launch(k_cloud_hist, dim3(nb), dim3(NT), 0, s, ref, M, w.header, w.cells, w.rank);
+    COLVO_CHECK_LAUNCH("k_cloud_hist");
+    colvo::launch(k_cloud_chunk_sum, dim3(SCAN_CHUNKS), dim3(NT), 0, s, w.cells, w.header, w.sums);
+    COLVO_CHECK_LAUNCH("k_cloud_chunk_sum");
+    colvo::launch(k_cloud_scan, dim3(1), dim3(NT), 0, s, w.sums, w.header);
+    COLVO_CHECK_LAUNCH("k_cloud_scan");
+    colvo::launch(k_cloud_chunk_scan, dim3(SCAN_CHUNKS), dim3(NT), 0, s, w.cells, w.header, w.sums);
+    COLVO_CHECK_LAUNCH("k_cloud_chunk_scan");
+    colvo::launch(k_cloud_scatter, dim3(nb), dim3(NT), 0, s, ref, M, w.header, w.cells, w.rank, w.rec);
+    COLVO_CHECK_LAUNCH("k_cloud_scatter");
+    return 0;
+}
+
+extern "C" int colvo_cloud_query(const float* query, int N, int M, float max_dist, const float* thresholds, int n_thresholds,
+                                 void* workspace, float* dist, float* dist2, int32_t* nearest, uint64_t* stats,
+                                 colvo_stream_t stream) {
+    COLVO_CHECK_ARG(workspace && stats && ((query && dist && dist2 && nearest) || N == 0) && (thresholds || n_thresholds == 0),
+                    "colvo_cloud_query: null pointer argument");
+    COLVO_CHECK_ARG(good_sizes(N, M), "colvo_cloud_query: bad shape N=%d M=%d (0 .. 2^30 - 1)", N, M);
+    float md2, scale;
+    COLVO_CHECK_ARG(good_max_dist(max_dist, md2, scale),
+                    "colvo_cloud_query: bad max_dist %g (finite, positive, with a finite positive float32 square)", (double)max_dist);
+    COLVO_CHECK_ARG(n_thresholds >= 0 && n_thresholds <= MAX_THRESHOLDS, "colvo_cloud_query: bad thresholds: %d of them (0 .. %d)",
+                    n_thresholds, MAX_THRESHOLDS);
+    Thresholds thr;
+    thr.n = n_thresholds;
+    for (int k = 0; k < MAX_THRESHOLDS; ++k) {
+        thr.t2[k] = 0.0f;
+        if (k >= n_thresholds) continue;
+        const float t = thresholds[k];
+        COLVO_CHECK_ARG(t > 0.0f && t <= max_dist && (k == 0 || t >= thresholds[k - 1]),
+                        "colvo_cloud_query: bad thresholds: tau[%d] = %g (positive, non-descending, <= max_dist %g)", k, (double)t,
+                        (double)max_dist);
+        thr.t2[k] = t * t;
+    }
+    COLVO_CHECK_ARG(aligned16(workspace), "colvo_cloud_query: workspace must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    const Ws w = layout(workspace, M);
+    COLVO_CHECK_HIP(hipMemsetAsync(w.counters, 0, (size_t)COUNTER_LINES * COUNTER_PITCH * 8, s), "colvo_cloud_query");
+    if (N > 0) {
+        colvo::launch(k_cloud_query, dim3(blocks_of(N)), dim3(NT), 0, s, query, N, (const Header*)w.header, (const int32_t*)w.cells,
+                      (const float4*)w.rec, M, md2, scale, thr, dist, dist2, nearest, w.counters);
+        COLVO_CHECK_LAUNCH("k_cloud_query");
+    }
+    colvo::launch(k_cloud_stats, dim3(1), dim3(64), 0, s, (const unsigned long long*)w.counters,
+                  reinterpret_cast<unsigned long long*>(stats));
+    COLVO_CHECK_LAUNCH("k_cloud_stats");
+    return 0;
+}
+
+extern "C" int colvo_cloud_transform(const float* points, int N, const float* Rts, float* out, colvo_stream_t stream) {
+    COLVO_CHECK_ARG(Rts && ((points && out) || N == 0), "colvo_cloud_transform: null pointer argument");
+    COLVO_CHECK_ARG(good_sizes(N, 0), "colvo_cloud_transform: bad shape N=%d (0 .. 2^30 - 1)", N);
+    if (N == 0) return 0;
+    Sim3 T;
+    for (int k = 0; k < 9; ++k) T.r[k] = Rts[k];
+    for (int k = 0; k < 3; ++k) T.t[k] = Rts[9 + k];
+    T.s = Rts[12];
+    colvo::launch(k_cloud_transform, dim3(blocks_of(N)), dim3(NT), 0, (hipStream_t)stream, points, N, T, out);
+    COLVO_CHECK_LAUNCH("k_cloud_transform");
+    return 0;
+}

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define COLVO_ABI_VERSION 18
+#define COLVO_ABI_VERSION 19
 
 typedef void* colvo_stream_t; /* hipStream_t */
 
@@ -629,6 +629,49 @@ size_t colvo_depth_metrics_workspace_bytes(int N, int H, int W);
 int colvo_depth_metrics(const float* pred, const float* gt, const uint8_t* mask, int N, int H, int W, float min_depth,
                         float max_depth, int median_scaling, void* workspace, double* per_image, float* scale,
                         int32_t* n_valid, colvo_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------- *
+ * SURVEY.md §6  evaluation of the reconstruction: exact truncated nearest neighbours between two  *
+ * point clouds (NumPy replica tests/cloud_ref.py).                               *
+ * ------------------------------------------------------------------------------------------- */
+/* query Q [N,3], ref P [M,3] float32, contiguous; max_dist > 0.  Pinned arithmetic: float32, every operation individually rounded
+ * (no FMA contraction).
+ *   valid     a point is valid iff its three coordinates are finite.  Invalid points take no part on either side and are counted.
+ *   d2(q,p)   ((dx*dx + dy*dy) + dz*dz) with dx = qx - px, dy = qy - py, dz = qz - pz.
+ *   md2       float32(max_dist) * float32(max_dist), rounded once.
+ *   reach     p is within reach of q iff d2(q,p) < md2 (strict).
+ *   dist2[q]  the minimum of d2 over the valid p within reach; nearest[q] the smallest original index p attaining it (the minimum
+ *             of the 64-bit keys (bits(d2) << 32) | p).  No point within reach, or q invalid: dist2[q] = md2, nearest[q] = -1.
+ *   dist[q]   sqrtf(dist2[q]), correctly rounded.
+ *   stats     device uint64[12], exact integers over the query cloud:
+ *               [0] n_valid    valid queries            [1] n_reached  valid queries with a point within reach
+ *               [2..9]         for threshold k < n_thresholds the valid queries with dist2 < float32(tau_k) * float32(tau_k); 0 beyond
+ *               [10]           sum over the valid queries of quantum(dist) = uint32(rint(dist * s)), s = float32(2^20) / float32(max_dist)
+ *                              (one IEEE division, the product rounded to float32, ties to even); the mean truncated distance is
+ *                              double(sum) / (double(s) * n_valid).  With N < 2^30 the sum stays below 2^51.
+ *               [11]           reference records examined, over all valid queries (a cost figure: it depends on the grid, not on
+ *                              the schedule).
+ * Every output bit follows from the inputs alone: the minimum does not depend on the order, the sums are integers; not on the
+ * schedule, the stream or the order in which atomics land.
+ * colvo_cloud_index_build sorts the valid reference points by the cell of a uniform grid over their bounding box (bounds, histogram,
+ * exclusive scan, scatter of 16-byte records x, y, z, original index) and writes origin, edge and dims into a device header at the
+ * head of the workspace: colvo_cloud_query reads them there, no read-back lies between the two.  The cell edge is
+ * max(max_dist * (1 + 2^-10), largest extent / 126), at most 128 cells per axis and 2^21 in all: the grid never outgrows the workspace,
+ * a wide box gets larger cells (DESIGN.md §3.6h has the argument that the 27 cells around a query's hold everything within reach
+ * although the cell index is computed in float32).  A box whose extent or cell edge is not finite is searched as one cell.
+ * colvo_cloud_query: the same max_dist as the build's.  thresholds: HOST array of n_thresholds <= 8 values, finite, positive,
+ * non-descending, each <= max_dist (as float32).  It clears and writes the counter lines of the workspace: one query at a time per
+ * workspace.  dist, dist2 [N] float32, nearest [N] int32.
+ * colvo_cloud_transform: out[i][a] = ((s * ((r_a0 * x + r_a1 * y) + r_a2 * z)) + t_a), pinned as above; Rts: HOST array of 13 floats,
+ * R row-major, t, s; out may be the input.
+ * Limits: N, M < 2^30 (0 is legal: an empty side launches nothing that indexes; the pointers of an empty cloud may be NULL);
+ * max_dist finite and positive with a finite, positive float32 square; workspace 16-byte aligned,
+ * colvo_cloud_workspace_bytes(N, M) bytes (0 for what the calls refuse; it does not depend on N today). */
+size_t colvo_cloud_workspace_bytes(int N, int M);
+int colvo_cloud_index_build(const float* ref, int M, float max_dist, void* workspace, colvo_stream_t stream);
+int colvo_cloud_query(const float* query, int N, int M, float max_dist, const float* thresholds, int n_thresholds, void* workspace,
+                      float* dist, float* dist2, int32_t* nearest, uint64_t* stats, colvo_stream_t stream);
+int colvo_cloud_transform(const float* points, int N, const float* Rts, float* out, colvo_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------- *
  * SURVEY.md §8f-4  frames as a decoder delivers them -> the path's input format.                *
