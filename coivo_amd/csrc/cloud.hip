@@ -5,8 +5,8 @@
 //   build   k_cloud_bounds: bounding box of the valid reference points, integer max on an order-preserving map of the float bits.
 //           k_cloud_grid: one thread turns the box into origin, cell edge and dims, in a device header the later kernels read.
 //           k_cloud_hist: one thread per point, 32-bit integer add into its cell's count; the value the add returns is the point's
-//           rank in its cell.  An ordered scan over the cells (chunk sums, one scan over them, in-chunk scan: fuse.hip's pattern,
-//           restated because the entry count lives on the device here).  k_cloud_scatter: 16-byte records (x, y, z, original index)
+//           rank in its cell.  The ordered scan of csrc/scan.hip over the cells, the entry count read from the device header
+//           and clamped to the launches' bound.  k_cloud_scatter: 16-byte records (x, y, z, original index)
 //           to start[cell] + rank.  The order inside a cell follows the atomics; no output depends on it.
 //   query   k_cloud_query: one lane per query; the 9 x-runs of up to 3 cells around the query's cell are contiguous in the sorted
 //           records; the minimum of the 64-bit keys (bits(d2) << 32) | index stays in registers.  Statistics are reduced per
@@ -17,7 +17,7 @@
 // a cell or a quantum is pinned: float32, every operation individually rounded -- contraction is off for this whole file.
 #include <float.h>
 
-#include "common.h"
+#include "scene.h"
 
 #pragma clang fp contract(off)
 
@@ -29,10 +29,7 @@ constexpr int AXIS_LIMIT = 128;                          // cells per axis, at m
 constexpr float AXIS_DIV = 126.0f;                       // edge >= extent / AXIS_DIV: floor(126 * (1 + 3 * 2^-24)) + 1 <= 128
 constexpr int MAX_CELLS = AXIS_LIMIT * AXIS_LIMIT * AXIS_LIMIT;
 constexpr float EDGE_MARGIN = 1.0f + 1.0f / 1024.0f;     // edge >= max_dist * (1 + 2^-10): DESIGN.md §3.6h
-constexpr int CHUNK_PER_THREAD = 16;
-constexpr int CHUNK = NT * CHUNK_PER_THREAD;             // entries one workgroup scans
 constexpr int SCAN_ENTRIES = MAX_CELLS + 1;              // the cells and one entry behind them: its prefix is the record count
-constexpr int SCAN_CHUNKS = (SCAN_ENTRIES + CHUNK - 1) / CHUNK;
 constexpr int COUNTER_LINES = 256;                       // the query's statistics: this many rows of N_STATS 64-bit words,
 constexpr int COUNTER_PITCH = 16;                        // ... 128 bytes apart (one hot address measured 41 x slower: §3.6c (c))
 constexpr int N_STATS = 12;
@@ -67,13 +64,6 @@ struct Sim3 {
 };
 
 __device__ __forceinline__ bool finite_f(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
-
-// order-preserving map of the float bits onto unsigned integers, and back
-__device__ __forceinline__ uint32_t okey(float f) {
-    const uint32_t b = __float_as_uint(f);
-    return b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u);
-}
-__device__ __forceinline__ float okey_inv(uint32_t k) { return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xffffffffu)); }
 
 __device__ __forceinline__ Grid load_grid(const Header* __restrict__ h) {
     Grid G;
@@ -118,7 +108,7 @@ __global__ __launch_bounds__(NT) void k_cloud_bounds(const float* __restrict__ P
         const float p[3] = {x, y, z};
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
-            const uint32_t q = okey(p[a]);
+            const uint32_t q = float_key(p[a]);
             k[a] = max(k[a], ~q);
             k[3 + a] = max(k[3 + a], q);
         }
@@ -155,8 +145,8 @@ __global__ void k_cloud_grid(Header* __restrict__ h, float max_dist) {
     float lo[3], hi[3], ext = 0.0f;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-        lo[a] = okey_inv(~h->key[a]);
-        hi[a] = okey_inv(h->key[3 + a]);
+        lo[a] = float_key_inv(~h->key[a]);
+        hi[a] = float_key_inv(h->key[3 + a]);
         ext = fmaxf(ext, hi[a] - lo[a]);
     }
     const float edge = fmaxf(max_dist * EDGE_MARGIN, __fdiv_rn(ext, AXIS_DIV));
@@ -188,88 +178,6 @@ __global__ __launch_bounds__(NT) void k_cloud_hist(const float* __restrict__ P, 
     rank[i] = r;
 }
 
-__device__ __forceinline__ int block_sum(int v, int* sm) {       // sum over the workgroup, in every thread
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (sm[0] + sm[1]) + (sm[2] + sm[3]);
-}
-
-// The scan runs over the header's cells + 1 entries; the launches are sized for SCAN_ENTRIES and the workgroups beyond the count leave.
-__device__ __forceinline__ int scan_entries(const Header* __restrict__ h) {
-    return min(max(__builtin_amdgcn_readfirstlane(h->cells), 0), MAX_CELLS) + 1;
-}
-
-// grid SCAN_CHUNKS: sums[chunk] = sum of the chunk's entries
-__global__ __launch_bounds__(NT) void k_cloud_chunk_sum(const int32_t* __restrict__ in, const Header* __restrict__ h,
-                                                        int32_t* __restrict__ sums) {
-    __shared__ int sm[NT / 64];
-    const int n = scan_entries(h);
-    const int base = blockIdx.x * CHUNK;
-    if (base >= n) return;
-    int s = 0;
-#pragma unroll
-    for (int r = 0; r < CHUNK_PER_THREAD; ++r) {
-        const int i = base + r * NT + threadIdx.x;
-        if (i < n) s += in[i];
-    }
-    s = block_sum(s, sm);
-    if (threadIdx.x == 0) sums[blockIdx.x] = s;
-}
-
-// one workgroup: exclusive scan of the chunk sums in place
-__global__ __launch_bounds__(NT) void k_cloud_scan(int32_t* __restrict__ sums, const Header* __restrict__ h) {
-    __shared__ int part[NT];
-    const int n = (scan_entries(h) + CHUNK - 1) / CHUNK;         // <= SCAN_CHUNKS
-    const int per = (n + NT - 1) / NT;
-    const int lo = min((int)threadIdx.x * per, n), hi = min(lo + per, n);
-    int s = 0;
-    for (int i = lo; i < hi; ++i) s += sums[i];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int run = 0;
-        for (int i = 0; i < NT; ++i) { const int t = part[i]; part[i] = run; run += t; }
-    }
-    __syncthreads();
-    int run = part[threadIdx.x];
-    for (int i = lo; i < hi; ++i) { const int t = sums[i]; sums[i] = run; run += t; }
-}
-
-// grid SCAN_CHUNKS: entry i becomes the sum of the entries before it
-__global__ __launch_bounds__(NT) void k_cloud_chunk_scan(int32_t* __restrict__ data, const Header* __restrict__ h,
-                                                         const int32_t* __restrict__ offsets) {
-    __shared__ int wsum[NT / 64];
-    const int n = scan_entries(h);
-    if (blockIdx.x * CHUNK >= n) return;
-    const int base = blockIdx.x * CHUNK + threadIdx.x * CHUNK_PER_THREAD;      // 16 consecutive entries per thread
-    int v[CHUNK_PER_THREAD];
-    int s = 0;
-#pragma unroll
-    for (int r = 0; r < CHUNK_PER_THREAD; ++r) {
-        v[r] = base + r < n ? data[base + r] : 0;
-        s += v[r];
-    }
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    int inc = s;                                                                // inclusive scan over the wave
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int t = __shfl_up(inc, off);
-        if (lane >= off) inc += t;
-    }
-    if (lane == 63) wsum[wv] = inc;
-    __syncthreads();
-    int run = offsets[blockIdx.x] + inc - s;
-    for (int i = 0; i < wv; ++i) run += wsum[i];
-#pragma unroll
-    for (int r = 0; r < CHUNK_PER_THREAD; ++r) {
-        if (base + r >= n) break;
-        data[base + r] = run;
-        run += v[r];
-    }
-}
-
 // one thread per reference point: its record goes to start[cell] + rank
 __global__ __launch_bounds__(NT) void k_cloud_scatter(const float* __restrict__ P, int M, const Header* __restrict__ h,
                                                       const int32_t* __restrict__ start, const int32_t* __restrict__ rank,
@@ -285,15 +193,6 @@ __global__ __launch_bounds__(NT) void k_cloud_scatter(const float* __restrict__ 
 }
 
 // ---- query ------------------------------------------------------------------------------------------------------------------- //
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, off), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), off);
-        v += ((unsigned long long)hi << 32) | lo;
-    }
-    return v;
-}
-
 // grid ceil(N / NT), one lane per query
 __global__ __launch_bounds__(NT) void k_cloud_query(const float* __restrict__ Q, int N, const Header* __restrict__ h,
                                                     const int32_t* __restrict__ start, const float4* __restrict__ rec, int M,
@@ -353,23 +252,14 @@ __global__ __launch_bounds__(NT) void k_cloud_query(const float* __restrict__ Q,
         nearest[i] = idx;
     }
     // statistics: per wave, per workgroup, then one add per word into this workgroup's counter line
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     unsigned long long st[N_STATS];
     st[0] = (unsigned long long)__popcll(__ballot(valid));
     st[1] = (unsigned long long)__popcll(__ballot(valid && idx >= 0));
 #pragma unroll
     for (int k = 0; k < MAX_THRESHOLDS; ++k) st[2 + k] = (unsigned long long)__popcll(__ballot(valid && k < thr.n && d2v < thr.t2[k]));
-    st[10] = wave_sum_u64(valid ? (unsigned long long)(uint32_t)rintf(dv * s) : 0ull);
-    st[11] = wave_sum_u64(examined);
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < N_STATS; ++k) sm[wv][k] = st[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < N_STATS) {
-        const unsigned long long v = (sm[0][threadIdx.x] + sm[1][threadIdx.x]) + (sm[2][threadIdx.x] + sm[3][threadIdx.x]);
-        if (v) atomicAdd(&counters[(size_t)(blockIdx.x % COUNTER_LINES) * COUNTER_PITCH + threadIdx.x], v);
-    }
+    st[10] = wave_sum(valid ? (unsigned long long)(uint32_t)rintf(dv * s) : 0ull);
+    st[11] = wave_sum(examined);
+    striped_counter_add(st, sm, counters + (size_t)(blockIdx.x % COUNTER_LINES) * COUNTER_PITCH);
 }
 
 // one workgroup: stats[k] = sum over the counter lines
@@ -393,9 +283,6 @@ __global__ __launch_bounds__(NT) void k_cloud_transform(const float* P, int N, S
 }
 
 // ---- host side --------------------------------------------------------------------------------------------------------------- //
-size_t pad16(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 struct Ws {                                // header, counter lines, cell starts, chunk sums, records [M], ranks [M]
     Header* header;
     unsigned long long* counters;
@@ -407,21 +294,15 @@ struct Ws {                                // header, counter lines, cell starts
 };
 
 Ws layout(void* base, int M) {
+    Carver c(base);
     Ws w;
-    char* c = static_cast<char*>(base);
-    w.header = reinterpret_cast<Header*>(c);
-    c += 256;
-    w.counters = reinterpret_cast<unsigned long long*>(c);
-    c += (size_t)COUNTER_LINES * COUNTER_PITCH * 8;
-    w.cells = reinterpret_cast<int32_t*>(c);
-    c += pad16((size_t)SCAN_ENTRIES * 4);
-    w.sums = reinterpret_cast<int32_t*>(c);
-    c += pad16((size_t)SCAN_CHUNKS * 4);
-    w.rec = reinterpret_cast<float4*>(c);
-    c += (size_t)M * 16;
-    w.rank = reinterpret_cast<int32_t*>(c);
-    c += pad16((size_t)M * 4);
-    w.bytes = (size_t)(c - static_cast<char*>(base));
+    w.header = c.take<Header>(1, 256);
+    w.counters = c.take<unsigned long long>((size_t)COUNTER_LINES * COUNTER_PITCH);
+    w.cells = c.take<int32_t>(SCAN_ENTRIES);
+    w.sums = c.take<int32_t>(scan_chunks(SCAN_ENTRIES));
+    w.rec = c.take<float4>(M);
+    w.rank = c.take<int32_t>(M);
+    w.bytes = c.bytes();
     return w;
 }
 
@@ -435,21 +316,10 @@ bool good_max_dist(float max_dist, float& md2, float& scale) {
     return md2 >= FLT_MIN && md2 < __builtin_inff() && scale < __builtin_inff();
 }
 
-int blocks_of(int n) { return (n + NT - 1) / NT; }
-
 }  // namespace
 }  // namespace colvo
 
 using namespace colvo;
-
-#define COLVO_CHECK_HIP(call, name)                                                       \
-    do {                                                                                  \
-        hipError_t e_ = (call);                                                           \
-        if (e_ != hipSuccess) {                                                           \
-            ::colvo::set_error("%s: %s failed: %s", name, #call, hipGetErrorString(e_)); \
-            return (int)e_;                                                               \
-        }                                                                                 \
-    } while (0)
 
 extern "C" size_t colvo_cloud_workspace_bytes(int N, int M) {
     if (!good_sizes(N, M)) return 0;
@@ -468,19 +338,14 @@ extern "C" int colvo_cloud_index_build(const float* ref, int M, float max_dist, 
     COLVO_CHECK_HIP(hipMemsetAsync(w.header, 0, sizeof(Header), s), "colvo_cloud_index_build");
     if (M == 0) return 0;                                        // cells = 0: the query walks nothing
     COLVO_CHECK_HIP(hipMemsetAsync(w.cells, 0, (size_t)SCAN_ENTRIES * 4, s), "colvo_cloud_index_build");
-    const int nb = blocks_of(M);
+    const int nb = blocks_of(M, NT);
     colvo::launch(k_cloud_bounds, dim3(nb < BOUNDS_MAX_BLOCKS ? nb : BOUNDS_MAX_BLOCKS), dim3(NT), 0, s, ref, M, w.header);
     COLVO_CHECK_LAUNCH("k_cloud_bounds");
     colvo::launch(k_cloud_grid, dim3(1), dim3(64), 0, s, w.header, max_dist);
     COLVO_CHECK_LAUNCH("k_cloud_grid");
     colvo::launch(k_cloud_hist, dim3(nb), dim3(NT), 0, s, ref, M, w.header, w.cells, w.rank);
     COLVO_CHECK_LAUNCH("k_cloud_hist");
-    colvo::launch(k_cloud_chunk_sum, dim3(SCAN_CHUNKS), dim3(NT), 0, s, w.cells, w.header, w.sums);
-    COLVO_CHECK_LAUNCH("k_cloud_chunk_sum");
-    colvo::launch(k_cloud_scan, dim3(1), dim3(NT), 0, s, w.sums, w.header);
-    COLVO_CHECK_LAUNCH("k_cloud_scan");
-    colvo::launch(k_cloud_chunk_scan, dim3(SCAN_CHUNKS), dim3(NT), 0, s, w.cells, w.header, w.sums);
-    COLVO_CHECK_LAUNCH("k_cloud_chunk_scan");
+    if (int rc = scan_exclusive(Scan{w.cells, SCAN_ENTRIES, &w.header->cells, w.sums, nullptr, nullptr, 0}, s)) return rc;
     colvo::launch(k_cloud_scatter, dim3(nb), dim3(NT), 0, s, ref, M, w.header, w.cells, w.rank, w.rec);
     COLVO_CHECK_LAUNCH("k_cloud_scatter");
     return 0;
@@ -513,7 +378,7 @@ extern "C" int colvo_cloud_query(const float* query, int N, int M, float max_dis
     const Ws w = layout(workspace, M);
     COLVO_CHECK_HIP(hipMemsetAsync(w.counters, 0, (size_t)COUNTER_LINES * COUNTER_PITCH * 8, s), "colvo_cloud_query");
     if (N > 0) {
-        colvo::launch(k_cloud_query, dim3(blocks_of(N)), dim3(NT), 0, s, query, N, (const Header*)w.header, (const int32_t*)w.cells,
+        colvo::launch(k_cloud_query, dim3(blocks_of(N, NT)), dim3(NT), 0, s, query, N, (const Header*)w.header, (const int32_t*)w.cells,
                       (const float4*)w.rec, M, md2, scale, thr, dist, dist2, nearest, w.counters);
         COLVO_CHECK_LAUNCH("k_cloud_query");
     }
@@ -531,7 +396,7 @@ extern "C" int colvo_cloud_transform(const float* points, int N, const float* Rt
     for (int k = 0; k < 9; ++k) T.r[k] = Rts[k];
     for (int k = 0; k < 3; ++k) T.t[k] = Rts[9 + k];
     T.s = Rts[12];
-    colvo::launch(k_cloud_transform, dim3(blocks_of(N)), dim3(NT), 0, (hipStream_t)stream, points, N, T, out);
+    colvo::launch(k_cloud_transform, dim3(blocks_of(N, NT)), dim3(NT), 0, (hipStream_t)stream, points, N, T, out);
     COLVO_CHECK_LAUNCH("k_cloud_transform");
     return 0;
 }

@@ -32,6 +32,15 @@ void set_error(const char* fmt, ...);
         }                                                                           \
     } while (0)
 
+#define COLVO_CHECK_HIP(call, name)                                                       \
+    do {                                                                                  \
+        hipError_t e_ = (call);                                                           \
+        if (e_ != hipSuccess) {                                                           \
+            ::colvo::set_error("%s: %s failed: %s", name, #call, hipGetErrorString(e_)); \
+            return (int)e_;                                                               \
+        }                                                                                 \
+    } while (0)
+
 // Every kernel launch of the library goes through launch(): a launch can then CARRY an event.  hipEventRecord puts a marker packet
 // behind the kernel on its queue, and the next kernel of that queue waits for it: 2.8 us per record on the producing chain, 5.3 us
 // when another queue already waits on the event -- the backward pass forks a weight-gradient kernel off every layer of its
@@ -71,6 +80,30 @@ inline int allow_dynamic_lds(size_t lds, int limit, const char* who) {
     done.store(true, std::memory_order_release);
     return 0;
 }
+
+// Host-side sizes and layouts.
+inline size_t pad16(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+inline int blocks_of(long long n, int nt) { return (int)((n + nt - 1) / nt); }    // ceil(n / nt)
+
+// A workspace laid out as consecutive arrays: take<T>(count) hands out the next `count` elements and advances by their size rounded up
+// to `pad` bytes.  On a null base it only measures (every pointer it returns is null): bytes() is what the same takes need, so a
+// layout is written once and serves both the size query and the call.
+class Carver {
+public:
+    explicit Carver(void* base) : base_(static_cast<char*>(base)) {}
+    template <typename T>
+    T* take(size_t count, size_t pad = 16) {
+        T* p = base_ ? reinterpret_cast<T*>(base_ + used_) : nullptr;
+        used_ += (count * sizeof(T) + pad - 1) / pad * pad;
+        return p;
+    }
+    size_t bytes() const { return used_; }
+
+private:
+    char* base_;
+    size_t used_ = 0;
+};
 
 // Which kernel FORM a dispatcher chose, counted per process (colvo_form_counts: the tests of the grid-size-selected forms read it --
 // a parity test at a small shape must be able to say that the large-grid kernel is what actually ran).  Every leaf of
@@ -122,6 +155,67 @@ __device__ __forceinline__ float wave_sum(float v) {
     const float r2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32));
     const float r3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 48));
     return (r0 + r1) + (r2 + r3);
+}
+
+// The same for integers.  The rotations act on the two halves of a 64-bit value (VALU only; six xor-shuffles of a 64-bit value are
+// twelve trips through the LDS crossbar, and csrc/localize.hip needs eleven such sums per group of lanes).  Called by the whole wave,
+// result uniform.
+template <int N>
+__device__ __forceinline__ int row_ror(int x) {
+    return __builtin_amdgcn_update_dpp(0, x, 0x120 + N, 0xf, 0xf, false);
+}
+template <int N>
+__device__ __forceinline__ long long row_ror(long long x) {
+    const unsigned lo = (unsigned)row_ror<N>((int)(unsigned)x), hi = (unsigned)row_ror<N>((int)(unsigned)((unsigned long long)x >> 32));
+    return (long long)(((unsigned long long)hi << 32) | lo);
+}
+__device__ __forceinline__ int lane_value(int v, int lane) { return __builtin_amdgcn_readlane(v, lane); }
+__device__ __forceinline__ long long lane_value(long long v, int lane) {
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, lane);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)((unsigned long long)v >> 32), lane);
+    return (long long)(((unsigned long long)hi << 32) | lo);
+}
+__device__ __forceinline__ long long wave_sum(long long v) {
+    v += row_ror<8>(v);
+    v += row_ror<4>(v);
+    v += row_ror<2>(v);
+    v += row_ror<1>(v);
+    return (lane_value(v, 0) + lane_value(v, 16)) + (lane_value(v, 32) + lane_value(v, 48));
+}
+__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) { return (unsigned long long)wave_sum((long long)v); }
+// (no caller yet: block_sum below keeps its xor-shuffles, so that the kernels using it keep the instructions they had)
+__device__ __forceinline__ int wave_sum(int v) {
+    v += row_ror<8>(v);
+    v += row_ror<4>(v);
+    v += row_ror<2>(v);
+    v += row_ror<1>(v);
+    return (lane_value(v, 0) + lane_value(v, 16)) + (lane_value(v, 32) + lane_value(v, 48));
+}
+__device__ __forceinline__ int wave_max(int v) {
+    v = max(v, row_ror<8>(v));
+    v = max(v, row_ror<4>(v));
+    v = max(v, row_ror<2>(v));
+    v = max(v, row_ror<1>(v));
+    return max(max(lane_value(v, 0), lane_value(v, 16)), max(lane_value(v, 32), lane_value(v, 48)));
+}
+
+// Sum over a workgroup of 256 threads, in every thread; sm: four ints of LDS (one call per array between barriers).
+__device__ __forceinline__ int block_sum(int v, int* sm) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (sm[0] + sm[1]) + (sm[2] + sm[3]);
+}
+
+// Order-preserving map of every float bit pattern to uint32 (negatives flipped whole, positives get the sign bit), and back: total, so
+// any input -- NaN included -- has a key, and a selection or a maximum over keys always terminates.
+__device__ __forceinline__ uint32_t float_key(float f) {
+    const uint32_t u = __float_as_uint(f);
+    return u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
+}
+__device__ __forceinline__ float float_key_inv(uint32_t k) {
+    return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xffffffffu));
 }
 
 // bf16 <-> f32 on raw 16-bit storage

@@ -10,7 +10,7 @@
 //
 // Every float32 operation that decides a vote is individually rounded -- contraction is off for this whole file -- and every sum is
 // an integer: a call's bits do not depend on scheduling or on the stream.
-#include "common.h"
+#include "scene.h"
 #include "tuning.h"
 
 #pragma clang fp contract(off)
@@ -31,8 +31,6 @@ constexpr float Z_EPS = 1e-3f;             // spec: Z_EPS
 struct Geom {
     int N, H, W, window, step, tiles_x, tiles;
 };
-
-__device__ __forceinline__ bool valid_depth(float d, float max_depth) { return (int)(d > 0.0f) & (int)(d < max_depth); }   // NaN falls out
 
 // neighbour slot s of frame i: k = -window..-1 for s < window, 1..window from there on (ascending j); -1 where it does not exist
 __host__ __device__ __forceinline__ int neighbour(int i, int s, int window, int step, int N) {
@@ -184,16 +182,7 @@ __global__ __launch_bounds__(NT) void k_consist_filter(const float* __restrict__
     }
     const int n[N_STATS] = {(int)__popcll(__ballot(cand)), (int)__popcll(__ballot(kept)), (int)__popcll(__ballot(no_view)),
                             (int)__popcll(__ballot(few)), (int)__popcll(__ballot(viol_out))};
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < N_STATS; ++k) sm_stats[wave][k] = n[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < N_STATS) {
-        const int k = threadIdx.x;
-        const int t = (sm_stats[0][k] + sm_stats[1][k]) + (sm_stats[2][k] + sm_stats[3][k]);
-        if (t) atomicAdd(&counters[((size_t)i * MAX_LINES + blockIdx.x % (unsigned)lines) * LINE_INTS + k], t);
-    }
+    striped_counter_add(n, sm_stats, counters + ((size_t)i * MAX_LINES + blockIdx.x % (unsigned)lines) * LINE_INTS);
 }
 
 // grid N, one wave: out_stats[i][k] = sum over the frame's counter lines
@@ -206,11 +195,22 @@ __global__ __launch_bounds__(64) void k_consist_stats(const int32_t* __restrict_
     out_stats[(size_t)i * N_STATS + k] = t;
 }
 
-size_t pad16(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
-
 bool ws_shape(int N, int window) { return N > 0 && N <= 65535 && window >= 1 && window <= MAX_WINDOW; }
 
-size_t table_bytes(int N, int window) { return pad16((size_t)N * 2 * window * REL_FLOATS * sizeof(float)); }
+struct Ws {                                // the transform table [N][2 * window][12], the counter lines [N][MAX_LINES][LINE_INTS]
+    float* rel;
+    int32_t* counters;
+    size_t bytes;
+};
+
+Ws layout(void* base, int N, int window) {
+    Carver c(base);
+    Ws w;
+    w.rel = c.take<float>((size_t)N * 2 * window * REL_FLOATS);
+    w.counters = c.take<int32_t>((size_t)N * MAX_LINES * LINE_INTS);
+    w.bytes = c.bytes();
+    return w;
+}
 
 }  // namespace
 }  // namespace colvo
@@ -219,7 +219,7 @@ using namespace colvo;
 
 extern "C" size_t colvo_consistency_workspace_bytes(int N, int window) {
     if (!ws_shape(N, window)) return 0;
-    return table_bytes(N, window) + (size_t)N * MAX_LINES * LINE_INTS * sizeof(int32_t);
+    return layout(nullptr, N, window).bytes;
 }
 
 extern "C" int colvo_consistency_filter(const float* depths, const float* K, const float* cam2world, int N, int H, int W, int window,
@@ -237,24 +237,23 @@ extern "C" int colvo_consistency_filter(const float* depths, const float* K, con
     COLVO_CHECK_ARG(rel_tol > 0.0f && rel_tol < __builtin_inff() && max_depth > 0.0f && max_depth < __builtin_inff(),
                     "colvo_consistency_filter: bad tolerance rel_tol %g or max_depth %g (finite and positive)", (double)rel_tol,
                     (double)max_depth);
-    COLVO_CHECK_ARG(((uintptr_t)workspace & 15) == 0, "colvo_consistency_filter: workspace must be 16-byte aligned");
+    COLVO_CHECK_ARG(aligned16(workspace), "colvo_consistency_filter: workspace must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     Geom g;
     g.N = N; g.H = H; g.W = W; g.window = window;
     g.step = step < 65536 ? step : 65536;                        // a step of N or more has no neighbour: any such step is the same
-    g.tiles_x = (W + WG_TILE - 1) / WG_TILE;
-    g.tiles = g.tiles_x * ((H + WG_TILE - 1) / WG_TILE);
-    float* rel = static_cast<float*>(workspace);
-    int32_t* counters = reinterpret_cast<int32_t*>(static_cast<char*>(workspace) + table_bytes(N, window));
+    g.tiles_x = blocks_of(W, WG_TILE);
+    g.tiles = g.tiles_x * blocks_of(H, WG_TILE);
+    const Ws w = layout(workspace, N, window);
     long lines = TUNE(consist_stat_lines);
     lines = lines < 1 ? 1 : lines > MAX_LINES ? MAX_LINES : lines;
-    colvo::launch(k_consist_rel, dim3((N * MAX_LINES * LINE_INTS + NT - 1) / NT), dim3(NT), 0, s, cam2world, N, window, g.step, rel,
-                  counters);
+    colvo::launch(k_consist_rel, dim3(blocks_of(N * MAX_LINES * LINE_INTS, NT)), dim3(NT), 0, s, cam2world, N, window, g.step, w.rel,
+                  w.counters);
     COLVO_CHECK_LAUNCH("k_consist_rel");
-    colvo::launch(k_consist_filter, dim3(g.tiles, N), dim3(NT), 0, s, depths, K, (const float*)rel, g, rel_tol, min_agree, max_violated,
-                  max_depth, (int)lines, out_depths, out_votes, counters);
+    colvo::launch(k_consist_filter, dim3(g.tiles, N), dim3(NT), 0, s, depths, K, (const float*)w.rel, g, rel_tol, min_agree, max_violated,
+                  max_depth, (int)lines, out_depths, out_votes, w.counters);
     COLVO_CHECK_LAUNCH("k_consist_filter");
-    colvo::launch(k_consist_stats, dim3(N), dim3(64), 0, s, (const int32_t*)counters, out_stats);
+    colvo::launch(k_consist_stats, dim3(N), dim3(64), 0, s, (const int32_t*)w.counters, out_stats);
     COLVO_CHECK_LAUNCH("k_consist_stats");
     return 0;
 }

@@ -33,33 +33,19 @@ struct EvalWs {
     uint32_t* hist;                        // [N][2][BINS]
     EvalState* state;                      // [N]
     double* partials;                      // [N][chunks][NSUM]
+    size_t bytes;
 };
 
-int eval_chunks(int H, int W) { return (int)(((long long)H * W + PIX_PER_WG - 1) / PIX_PER_WG); }
+int eval_chunks(int H, int W) { return blocks_of((long long)H * W, PIX_PER_WG); }
 
-size_t eval_ws_bytes(int N, int chunks) {
-    return (size_t)N * 2 * BINS * sizeof(uint32_t) + (size_t)N * sizeof(EvalState) + (size_t)N * chunks * NSUM * sizeof(double);
-}
-
-EvalWs eval_ws(void* base, int N) {
+EvalWs eval_ws(void* base, int N, int chunks) {
+    Carver c(base);
     EvalWs w;
-    char* p = static_cast<char*>(base);
-    w.hist = reinterpret_cast<uint32_t*>(p);
-    p += (size_t)N * 2 * BINS * sizeof(uint32_t);
-    w.state = reinterpret_cast<EvalState*>(p);
-    p += (size_t)N * sizeof(EvalState);
-    w.partials = reinterpret_cast<double*>(p);
+    w.hist = c.take<uint32_t>((size_t)N * 2 * BINS);
+    w.state = c.take<EvalState>(N);
+    w.partials = c.take<double>((size_t)N * chunks * NSUM);
+    w.bytes = c.bytes();
     return w;
-}
-
-// Order-preserving map of every float bit pattern to uint32 (negatives flipped whole, positives get the sign bit): total, so any
-// input -- NaN included -- has a key and the selection always terminates.
-__device__ __forceinline__ uint32_t f2key(float f) {
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key2f(uint32_t k) {
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
 }
 
 // One LDS histogram increment per active lane, called by the whole (converged) wave.  Depth maps are smooth, so the 64
@@ -130,7 +116,7 @@ __global__ __launch_bounds__(NT) void k_eval_hist(const float* __restrict__ pred
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const bool v = in[u] && gv[u] > lo && gv[u] < hi;
-            const uint32_t kp = f2key(pv[u]), kg = f2key(gv[u]);
+            const uint32_t kp = float_key(pv[u]), kg = float_key(gv[u]);
             const bool vp = v && (pass == 0 || (kp >> hi_shift) == pre_p);
             const bool vg = v && (pass == 0 || (kg >> hi_shift) == pre_g);
             wave_hist_add(h, vp, (kp >> lo_shift) & dmask);
@@ -215,7 +201,7 @@ __global__ __launch_bounds__(NT) void k_eval_select(uint32_t* __restrict__ hist,
     if (pass == 0) st.n = total;
     if (last) {
         float s = 1.0f;
-        if (median_scaling) s = __fdiv_rn(key2f(pre[1]), key2f(pre[0]));   // med(gt) / med(pred)
+        if (median_scaling) s = __fdiv_rn(float_key_inv(pre[1]), float_key_inv(pre[0]));   // med(gt) / med(pred)
         scale_out[img] = s;
         n_out[img] = total;
     }
@@ -300,7 +286,7 @@ using namespace colvo;
 
 extern "C" size_t colvo_depth_metrics_workspace_bytes(int N, int H, int W) {
     if (N <= 0 || N > 65535 || H <= 0 || W <= 0 || (long long)H * W >= (1ll << 30)) return 0;
-    return eval_ws_bytes(N, eval_chunks(H, W));
+    return eval_ws(nullptr, N, eval_chunks(H, W)).bytes;
 }
 
 extern "C" int colvo_depth_metrics(const float* pred, const float* gt, const uint8_t* mask, int N, int H, int W, float min_depth,
@@ -311,9 +297,9 @@ extern "C" int colvo_depth_metrics(const float* pred, const float* gt, const uin
                     "colvo_depth_metrics: bad shape N=%d H=%d W=%d", N, H, W);
     COLVO_CHECK_ARG(min_depth < max_depth, "colvo_depth_metrics: bad depth range (min_depth %g, max_depth %g)", (double)min_depth,
                     (double)max_depth);
-    COLVO_CHECK_ARG(((uintptr_t)workspace & 15) == 0, "colvo_depth_metrics: workspace must be 16-byte aligned");
+    COLVO_CHECK_ARG(aligned16(workspace), "colvo_depth_metrics: workspace must be 16-byte aligned");
     const int HW = H * W, chunks = eval_chunks(H, W);
-    const EvalWs ws = eval_ws(workspace, N);
+    const EvalWs ws = eval_ws(workspace, N, chunks);
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid(chunks, N);
     colvo::launch(k_eval_init, dim3(N), dim3(NT), 0, s, ws.hist, ws.state);

@@ -2,7 +2,7 @@
 // observation count of the samples that fell into each voxel of a regular grid.  Contract: include/colvo.h (colvo_fuse_*).
 //
 //   plan        k_fuse_mark: one thread per sample, marks the 8x8x8 brick it falls into.  The marks are numbered in ascending brick
-//               order by an ordered scan (chunk sums, one scan over them, ordered write) -- no hash, so the output order is fixed.
+//               order by the ordered scan of csrc/scan.hip -- no hash, so the output order is fixed.
 //   accumulate  k_fuse_accumulate: the same walk and the same point routine (so the same bits), slot lookup, integer adds into the
 //               brick's 512 records.  Lanes of a wave that hit the same voxel add once, through the first of them, and a record's
 //               four words are added by four adjacent lanes of one instruction.
@@ -11,7 +11,7 @@
 // Every hand-off between phases is a kernel boundary.  All sums are unsigned integers added with native atomics, so a call's bits do
 // not depend on scheduling, on the stream or on the order of the frames.  The arithmetic that decides a sample's voxel is pinned:
 // float32, every operation individually rounded -- contraction is off for this whole file.
-#include "common.h"
+#include "scene.h"
 #include "tuning.h"
 
 #pragma clang fp contract(off)
@@ -23,8 +23,6 @@ constexpr int NT = 256;
 constexpr int BRICK = 8;                   // voxels per brick edge
 constexpr int BRICK_VOX = 512;
 constexpr int TILE = 8;                    // a wave owns TILE x TILE samples: neighbouring pixels share voxels
-constexpr int CHUNK_PER_THREAD = 16;
-constexpr int CHUNK = NT * CHUNK_PER_THREAD;   // entries one workgroup scans
 constexpr int MAX_SLOTS = 1 << 22;         // n_bricks below this: a pool index (slot * 512 + local) stays below 2^31
 constexpr int MAX_AGG_ROUNDS = 64;           // a wave holds at most 64 distinct voxels
 constexpr int COUNTER_LINES = 256;         // k_fuse_mark's sample counters: this many pairs,
@@ -37,29 +35,6 @@ struct Record {
 };
 static_assert(sizeof(Record) == 32, "Record is 32 B");
 
-struct Cam {
-    float fx, fy, cx, cy;
-    float r[9];
-    float t[3];
-};
-
-__device__ __forceinline__ Cam load_cam(const float* __restrict__ K, const float* __restrict__ M, int b) {
-    Cam c;
-    const float* k = K + (size_t)b * 9;
-    const float* m = M + (size_t)b * 16;
-    c.fx = uniform_f(k[0]);
-    c.fy = uniform_f(k[4]);
-    c.cx = uniform_f(k[2]);
-    c.cy = uniform_f(k[5]);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-#pragma unroll
-        for (int j = 0; j < 3; ++j) c.r[i * 3 + j] = uniform_f(m[i * 4 + j]);
-        c.t[i] = uniform_f(m[i * 4 + 3]);
-    }
-    return c;
-}
-
 struct Grid {
     float o[3];
     float inv;                             // float32(1) / float32(voxel_size), computed on the host
@@ -67,8 +42,8 @@ struct Grid {
     int nb[3];                             // bricks
 };
 
-struct Walk {                              // the samples of one frame as 8x8 tiles, one per wave
-    int H, W, stride, Hs, Ws, tiles_x, tiles, blocks_per_frame;
+struct Walk : StridedFrame {                // the samples of one frame as 8x8 tiles, one per wave
+    int tiles_x, tiles, blocks_per_frame;
 };
 
 // sample (frame-local) of this thread; false beyond the image
@@ -108,19 +83,8 @@ __device__ __forceinline__ bool locate(const Cam& c, const Grid& G, float u, flo
     return inside;
 }
 
-__device__ __forceinline__ bool kept_depth(float d, float max_depth) { return d > 0.0f && d < max_depth; }   // NaN falls out
-
 __device__ __forceinline__ uint32_t colour_quantum(float c) {
     return (uint32_t)fminf(fmaxf(rintf(c * 255.0f), 0.0f), 255.0f);       // fmaxf(NaN, 0) = 0
-}
-
-// ---- ordered scan over n int32 entries: chunk sums, one workgroup over the sums, in-chunk scan ------------------------------- //
-__device__ __forceinline__ int block_sum(int v, int* sm) {       // sum over the workgroup, in every thread
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (sm[0] + sm[1]) + (sm[2] + sm[3]);
 }
 
 // grid (blocks_per_frame, N).  The two sample counts are summed per workgroup and added to one of COUNTER_LINES pairs, each in a
@@ -128,27 +92,19 @@ __device__ __forceinline__ int block_sum(int v, int* sm) {       // sum over the
 __global__ __launch_bounds__(NT) void k_fuse_mark(const float* __restrict__ depth, const float* __restrict__ K,
                                                   const float* __restrict__ M, Walk w, Grid G, float max_depth,
                                                   int32_t* __restrict__ brick_table, int32_t* __restrict__ counters) {
-    __shared__ int sm[2][NT / 64];
+    __shared__ int sm[NT / 64][2];
     const int b = blockIdx.y;
     int u = 0, v = 0;
     const bool in = walk_pixel(w, u, v);
     const float d = in ? depth[((size_t)b * w.H + v) * w.W + u] : 0.0f;
-    const bool kept = in && kept_depth(d, max_depth);
+    const bool kept = in && valid_depth(d, max_depth);
     const Cam c = load_cam(K, M, b);
     Voxel vx;
     const bool inside = kept && locate(c, G, (float)u, (float)v, d, vx);
     if (inside) brick_table[vx.brick] = 1;                       // idempotent same-value store
-    const int n_kept = __popcll(__ballot(kept)), n_out = __popcll(__ballot(kept && !inside));
-    if ((threadIdx.x & 63) == 0) {
-        sm[0][threadIdx.x >> 6] = n_kept;
-        sm[1][threadIdx.x >> 6] = n_out;
-    }
-    __syncthreads();
-    if (threadIdx.x < 2) {
-        const int n = (sm[threadIdx.x][0] + sm[threadIdx.x][1]) + (sm[threadIdx.x][2] + sm[threadIdx.x][3]);
-        const unsigned line = (blockIdx.y * gridDim.x + blockIdx.x) % COUNTER_LINES;
-        if (n) atomicAdd(&counters[line * COUNTER_PITCH + threadIdx.x], n);
-    }
+    const int n[2] = {(int)__popcll(__ballot(kept)), (int)__popcll(__ballot(kept && !inside))};
+    const unsigned line = (blockIdx.y * gridDim.x + blockIdx.x) % COUNTER_LINES;
+    striped_counter_add(n, sm, counters + line * COUNTER_PITCH);
 }
 
 // one workgroup: stats[0], stats[1] = sums over the counter lines
@@ -161,77 +117,6 @@ __global__ __launch_bounds__(NT) void k_fuse_stats(const int32_t* __restrict__ c
     if (threadIdx.x == 0) {
         stats[0] = n_kept;
         stats[1] = n_out;
-    }
-}
-
-// grid ceil(n / CHUNK): sums[chunk] = sum of the chunk's entries
-__global__ __launch_bounds__(NT) void k_fuse_chunk_sum(const int32_t* __restrict__ in, int n, int32_t* __restrict__ sums) {
-    __shared__ int sm[NT / 64];
-    const int base = blockIdx.x * CHUNK;
-    int s = 0;
-#pragma unroll
-    for (int r = 0; r < CHUNK_PER_THREAD; ++r) {
-        const int i = base + r * NT + threadIdx.x;
-        if (i < n) s += in[i];
-    }
-    s = block_sum(s, sm);
-    if (threadIdx.x == 0) sums[blockIdx.x] = s;
-}
-
-// one workgroup: exclusive scan of `n` chunk sums in place; total -> *total
-__global__ __launch_bounds__(NT) void k_fuse_scan(int32_t* __restrict__ sums, int n, int32_t* __restrict__ total) {
-    __shared__ int part[NT];
-    const int per = (n + NT - 1) / NT;
-    const int lo = min((int)threadIdx.x * per, n), hi = min(lo + per, n);
-    int s = 0;
-    for (int i = lo; i < hi; ++i) s += sums[i];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int run = 0;
-        for (int i = 0; i < NT; ++i) { const int t = part[i]; part[i] = run; run += t; }
-        *total = run;
-    }
-    __syncthreads();
-    int run = part[threadIdx.x];
-    for (int i = lo; i < hi; ++i) { const int t = sums[i]; sums[i] = run; run += t; }
-}
-
-// grid ceil(n / CHUNK): entry i becomes the sum of the entries before it.  LIST (the brick table): an entry is a mark; a marked
-// entry becomes its slot and list[slot] = i, an unmarked one -1.
-template <bool LIST>
-__global__ __launch_bounds__(NT) void k_fuse_chunk_scan(int32_t* __restrict__ data, int n, const int32_t* __restrict__ offsets,
-                                                        int32_t* __restrict__ list, int list_cap) {
-    __shared__ int wsum[NT / 64];
-    const int base = blockIdx.x * CHUNK + threadIdx.x * CHUNK_PER_THREAD;      // 16 consecutive entries per thread
-    int v[CHUNK_PER_THREAD];
-    int s = 0;
-#pragma unroll
-    for (int r = 0; r < CHUNK_PER_THREAD; ++r) {
-        v[r] = base + r < n ? data[base + r] : 0;
-        s += v[r];
-    }
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    int inc = s;                                                                // inclusive scan over the wave
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int t = __shfl_up(inc, off);
-        if (lane >= off) inc += t;
-    }
-    if (lane == 63) wsum[wv] = inc;
-    __syncthreads();
-    int run = offsets[blockIdx.x] + inc - s;
-    for (int i = 0; i < wv; ++i) run += wsum[i];
-#pragma unroll
-    for (int r = 0; r < CHUNK_PER_THREAD; ++r) {
-        if (base + r >= n) break;
-        if (LIST) {
-            data[base + r] = v[r] ? run : -1;
-            if (v[r] && run < list_cap) list[run] = base + r;
-        } else {
-            data[base + r] = run;
-        }
-        run += v[r];
     }
 }
 
@@ -262,7 +147,7 @@ __global__ __launch_bounds__(NT) void k_fuse_accumulate(const float* __restrict_
     const size_t HW = (size_t)w.H * w.W;
     const size_t px = (size_t)v * w.W + u;
     const float d = in ? depth[(size_t)b * HW + px] : 0.0f;
-    const bool kept = in && kept_depth(d, max_depth);
+    const bool kept = in && valid_depth(d, max_depth);
     const Cam c = load_cam(K, M, b);
     Voxel vx;
     bool inside = kept && locate(c, G, (float)u, (float)v, d, vx);
@@ -420,14 +305,11 @@ __global__ __launch_bounds__(NT) void k_fuse_write(const Record* __restrict__ po
 
 // ---- host side: geometry and workspace layouts ------------------------------------------------------------------------------- //
 bool walk_geom(int N, int H, int W, int stride, Walk& g) {
-    if (N <= 0 || N > 65535 || H <= 0 || W <= 0 || stride <= 0 || (long long)H * W >= (1ll << 30)) return false;
-    g.H = H; g.W = W; g.stride = stride;
-    g.Hs = (H + stride - 1) / stride;
-    g.Ws = (W + stride - 1) / stride;
+    if (!strided_frame(N, H, W, stride, g)) return false;
     if ((long long)N * g.Hs * g.Ws >= (1ll << 31)) return false;             // the sample counters are int32
-    g.tiles_x = (g.Ws + TILE - 1) / TILE;
-    g.tiles = g.tiles_x * ((g.Hs + TILE - 1) / TILE);
-    g.blocks_per_frame = (g.tiles + NT / 64 - 1) / (NT / 64);
+    g.tiles_x = blocks_of(g.Ws, TILE);
+    g.tiles = g.tiles_x * blocks_of(g.Hs, TILE);
+    g.blocks_per_frame = blocks_of(g.tiles, NT / 64);
     return true;
 }
 
@@ -454,8 +336,6 @@ bool grid_geom(float ox, float oy, float oz, float voxel_size, int nx, int ny, i
 }
 
 int total_bricks(const Grid& G) { return G.nb[0] * G.nb[1] * G.nb[2]; }
-size_t pad16(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
-int chunks_of(int n) { return (n + CHUNK - 1) / CHUNK; }
 
 struct PlanWs {                            // sample counters, brick table [bricks], brick list [min(bricks, MAX_SLOTS)], chunk sums
     int32_t* counters;
@@ -468,18 +348,14 @@ struct PlanWs {                            // sample counters, brick table [bric
 
 PlanWs plan_ws(void* base, const Grid& G) {
     const int tb = total_bricks(G);
+    Carver c(base);
     PlanWs p;
     p.list_cap = tb < MAX_SLOTS ? tb : MAX_SLOTS;
-    char* c = static_cast<char*>(base);
-    p.counters = reinterpret_cast<int32_t*>(c);
-    c += (size_t)COUNTER_LINES * COUNTER_PITCH * 4;
-    p.table = reinterpret_cast<int32_t*>(c);
-    c += pad16((size_t)tb * 4);
-    p.list = reinterpret_cast<int32_t*>(c);
-    c += pad16((size_t)p.list_cap * 4);
-    p.sums = reinterpret_cast<int32_t*>(c);
-    c += pad16((size_t)chunks_of(tb) * 4);
-    p.bytes = (size_t)(c - static_cast<char*>(base));
+    p.counters = c.take<int32_t>((size_t)COUNTER_LINES * COUNTER_PITCH);
+    p.table = c.take<int32_t>(tb);                               // (cleared together with the counters: it lies right behind them)
+    p.list = c.take<int32_t>(p.list_cap);
+    p.sums = c.take<int32_t>(scan_chunks(tb));
+    p.bytes = c.bytes();
     return p;
 }
 
@@ -490,31 +366,18 @@ struct ExtractWs {                         // rows per brick [n_bricks] (offsets
 };
 
 ExtractWs extract_ws(void* base, int n_bricks) {
+    Carver c(base);
     ExtractWs e;
-    char* c = static_cast<char*>(base);
-    e.rows = reinterpret_cast<int32_t*>(c);
-    c += pad16((size_t)n_bricks * 4);
-    e.sums = reinterpret_cast<int32_t*>(c);
-    c += pad16((size_t)chunks_of(n_bricks) * 4);
-    e.bytes = (size_t)(c - static_cast<char*>(base));
+    e.rows = c.take<int32_t>(n_bricks);
+    e.sums = c.take<int32_t>(scan_chunks(n_bricks));
+    e.bytes = c.bytes();
     return e;
 }
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 }  // namespace colvo
 
 using namespace colvo;
-
-#define COLVO_CHECK_HIP(call, name)                                                       \
-    do {                                                                                  \
-        hipError_t e_ = (call);                                                           \
-        if (e_ != hipSuccess) {                                                           \
-            ::colvo::set_error("%s: %s failed: %s", name, #call, hipGetErrorString(e_)); \
-            return (int)e_;                                                               \
-        }                                                                                 \
-    } while (0)
 
 extern "C" size_t colvo_fuse_plan_workspace_bytes(int N, int H, int W, int stride, int nx, int ny, int nz) {
     Walk w;
@@ -536,20 +399,14 @@ extern "C" int colvo_fuse_plan(const float* depths, const float* K, const float*
     COLVO_CHECK_ARG(aligned16(workspace), "colvo_fuse_plan: workspace must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     const PlanWs p = plan_ws(workspace, G);
-    const int tb = total_bricks(G), chunks = chunks_of(tb);
+    const int tb = total_bricks(G);
     COLVO_CHECK_HIP(hipMemsetAsync(p.counters, 0, (size_t)COUNTER_LINES * COUNTER_PITCH * 4 + (size_t)tb * 4, s),     // ... and the table
                     "colvo_fuse_plan");
     colvo::launch(k_fuse_mark, dim3(w.blocks_per_frame, N), dim3(NT), 0, s, depths, K, cam2world, w, G, max_depth, p.table, p.counters);
     COLVO_CHECK_LAUNCH("k_fuse_mark");
     colvo::launch(k_fuse_stats, dim3(1), dim3(NT), 0, s, p.counters, stats);
     COLVO_CHECK_LAUNCH("k_fuse_stats");
-    colvo::launch(k_fuse_chunk_sum, dim3(chunks), dim3(NT), 0, s, p.table, tb, p.sums);
-    COLVO_CHECK_LAUNCH("k_fuse_chunk_sum");
-    colvo::launch(k_fuse_scan, dim3(1), dim3(NT), 0, s, p.sums, chunks, stats + 2);
-    COLVO_CHECK_LAUNCH("k_fuse_scan");
-    colvo::launch(k_fuse_chunk_scan<true>, dim3(chunks), dim3(NT), 0, s, p.table, tb, p.sums, p.list, p.list_cap);
-    COLVO_CHECK_LAUNCH("k_fuse_chunk_scan");
-    return 0;
+    return scan_exclusive(Scan{p.table, tb, nullptr, p.sums, stats + 2, p.list, p.list_cap}, s);
 }
 
 extern "C" size_t colvo_fuse_pool_bytes(int n_bricks) {
@@ -594,20 +451,13 @@ extern "C" int colvo_fuse_count(const void* pool, int n_bricks, int min_obs, voi
     COLVO_CHECK_ARG(aligned16(pool) && aligned16(extract_workspace), "colvo_fuse_count: pool and workspace must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     const ExtractWs e = extract_ws(extract_workspace, n_bricks);
-    const int chunks = chunks_of(n_bricks);
     double limit = TUNE_F(fuse_count_limit);
     limit = limit < 1.0 ? 1.0 : limit > 16777216.0 ? 16777216.0 : limit;
     COLVO_CHECK_HIP(hipMemsetAsync(stats2, 0, 3 * sizeof(int32_t), s), "colvo_fuse_count");
     colvo::launch(k_fuse_count, dim3(n_bricks), dim3(NT), 0, s, static_cast<const Record*>(pool), min_obs, (unsigned long long)limit,
                   e.rows, stats2);
     COLVO_CHECK_LAUNCH("k_fuse_count");
-    colvo::launch(k_fuse_chunk_sum, dim3(chunks), dim3(NT), 0, s, e.rows, n_bricks, e.sums);
-    COLVO_CHECK_LAUNCH("k_fuse_chunk_sum");
-    colvo::launch(k_fuse_scan, dim3(1), dim3(NT), 0, s, e.sums, chunks, stats2 + 1);
-    COLVO_CHECK_LAUNCH("k_fuse_scan");
-    colvo::launch(k_fuse_chunk_scan<false>, dim3(chunks), dim3(NT), 0, s, e.rows, n_bricks, e.sums, (int32_t*)nullptr, 0);
-    COLVO_CHECK_LAUNCH("k_fuse_chunk_scan");
-    return 0;
+    return scan_exclusive(Scan{e.rows, n_bricks, nullptr, e.sums, stats2 + 1, nullptr, 0}, s);
 }
 
 extern "C" int colvo_fuse_write(const void* workspace, const void* pool, int n_bricks, int min_obs, float ox, float oy, float oz,

@@ -15,7 +15,7 @@
 // and of their products, a bounding box), added with native 64-bit adds and 32-bit max: a call's bits depend on nothing but its
 // inputs.  The point arithmetic is pinned: float32, every operation individually rounded -- contraction is off for this whole
 // file, which also pins the float64 expressions of the finish kernels.
-#include "common.h"
+#include "scene.h"
 
 #pragma clang fp contract(off)
 
@@ -43,58 +43,33 @@ struct Record {
 };
 static_assert(sizeof(Record) == 128, "Record is 128 B");
 
-struct Walk {
-    int H, W, stride, Hs, Ws, chunks;
+struct Walk : StridedFrame {
+    int chunks;
 };
 
 bool walk_geom(int N, int H, int W, int stride, Walk& g) {
-    if (N <= 0 || N > 65535 || H <= 0 || W <= 0 || stride <= 0 || (long long)H * W >= (1ll << 30)) return false;
-    g.H = H; g.W = W; g.stride = stride;
-    g.Hs = (H + stride - 1) / stride;
-    g.Ws = (W + stride - 1) / stride;
-    g.chunks = (g.Hs * g.Ws + PIX_PER_WG - 1) / PIX_PER_WG;
+    if (!strided_frame(N, H, W, stride, g)) return false;
+    g.chunks = blocks_of(g.Hs * g.Ws, PIX_PER_WG);
     return true;
 }
 
 bool labels_ok(int L) { return L >= 1 && L <= MAX_LABELS; }
 bool depth_ok(float m) { return m > 0.0f && m < __builtin_inff(); }          // NaN fails
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // workspace: records [N][L], then one 64-bit count of ignored pixels per frame
-size_t records_bytes(int N, int L) { return (size_t)N * L * sizeof(Record); }
-size_t workspace_bytes(int N, int L) { return records_bytes(N, L) + (((size_t)N * 8 + 15) & ~(size_t)15); }
+struct Ws {
+    Record* records;
+    unsigned long long* ignored;
+    size_t bytes;
+};
 
-// Sum / maximum over the 64 lanes, called by the whole wave, result uniform.  Row rotations by DPP on the two halves of the
-// value (VALU only; six xor-shuffles of a 64-bit value are twelve trips through the LDS crossbar, and a group needs eleven such
-// sums), then the four 16-lane row totals through scalar registers.
-template <int N>
-__device__ __forceinline__ int row_ror(int x) {
-    return __builtin_amdgcn_update_dpp(0, x, 0x120 + N, 0xf, 0xf, false);
-}
-template <int N>
-__device__ __forceinline__ long long row_ror(long long x) {
-    const unsigned lo = (unsigned)row_ror<N>((int)(unsigned)x), hi = (unsigned)row_ror<N>((int)(unsigned)((unsigned long long)x >> 32));
-    return (long long)(((unsigned long long)hi << 32) | lo);
-}
-__device__ __forceinline__ long long lane_value(long long v, int lane) {
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, lane);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)((unsigned long long)v >> 32), lane);
-    return (long long)(((unsigned long long)hi << 32) | lo);
-}
-__device__ __forceinline__ long long wave_sum(long long v) {
-    v += row_ror<8>(v);
-    v += row_ror<4>(v);
-    v += row_ror<2>(v);
-    v += row_ror<1>(v);
-    return (lane_value(v, 0) + lane_value(v, 16)) + (lane_value(v, 32) + lane_value(v, 48));
-}
-__device__ __forceinline__ int wave_max(int v) {
-    v = max(v, row_ror<8>(v));
-    v = max(v, row_ror<4>(v));
-    v = max(v, row_ror<2>(v));
-    v = max(v, row_ror<1>(v));
-    return max(max(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)),
-               max(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
+Ws layout(void* base, int N, int L) {
+    Carver c(base);
+    Ws w;
+    w.records = c.take<Record>((size_t)N * L);
+    w.ignored = c.take<unsigned long long>(N);
+    w.bytes = c.bytes();
+    return w;
 }
 
 // grid (chunks, N).  bounds: NULL, or per (frame, label) the pair (mean_z, limit) of k_localize_bounds.
@@ -418,18 +393,9 @@ __global__ __launch_bounds__(64) void k_localize_polyps(const float* __restrict_
 
 using namespace colvo;
 
-#define COLVO_CHECK_HIP(call, name)                                                       \
-    do {                                                                                  \
-        hipError_t e_ = (call);                                                           \
-        if (e_ != hipSuccess) {                                                           \
-            ::colvo::set_error("%s: %s failed: %s", name, #call, hipGetErrorString(e_)); \
-            return (int)e_;                                                               \
-        }                                                                                 \
-    } while (0)
-
 extern "C" size_t colvo_localize_workspace_bytes(int N, int num_labels) {
     if (N <= 0 || N > 65535 || !labels_ok(num_labels)) return 0;
-    return workspace_bytes(N, num_labels);
+    return layout(nullptr, N, num_labels).bytes;
 }
 
 extern "C" int colvo_localize_accumulate(const float* depths, const uint8_t* labels, const float* K, int N, int H, int W, int stride,
@@ -442,10 +408,10 @@ extern "C" int colvo_localize_accumulate(const float* depths, const uint8_t* lab
     COLVO_CHECK_ARG(depth_ok(max_depth), "colvo_localize_accumulate: bad max_depth %g (finite, positive)", (double)max_depth);
     COLVO_CHECK_ARG(aligned16(records) && aligned16(clip_bounds), "colvo_localize_accumulate: records and clip_bounds must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
-    COLVO_CHECK_HIP(hipMemsetAsync(records, 0, workspace_bytes(N, num_labels), s), "colvo_localize_accumulate");
-    unsigned long long* ignored = reinterpret_cast<unsigned long long*>(static_cast<char*>(records) + records_bytes(N, num_labels));
+    const Ws w = layout(records, N, num_labels);
+    COLVO_CHECK_HIP(hipMemsetAsync(records, 0, w.bytes, s), "colvo_localize_accumulate");
     colvo::launch(k_localize_accumulate, dim3(g.chunks, N), dim3(NT), 0, s, depths, labels, K, g, max_depth, num_labels, clip_bounds,
-                  static_cast<Record*>(records), ignored);
+                  w.records, w.ignored);
     COLVO_CHECK_LAUNCH("k_localize_accumulate");
     return 0;
 }
@@ -459,7 +425,7 @@ extern "C" int colvo_localize_bounds(const void* records, int N, int num_labels,
                     (double)clip_sigma);
     COLVO_CHECK_ARG(aligned16(records) && aligned16(clip_bounds), "colvo_localize_bounds: records and clip_bounds must be 16-byte aligned");
     const int n = N * num_labels;
-    colvo::launch(k_localize_bounds, dim3((n + NT - 1) / NT), dim3(NT), 0, (hipStream_t)stream, static_cast<const Record*>(records), n,
+    colvo::launch(k_localize_bounds, dim3(blocks_of(n, NT)), dim3(NT), 0, (hipStream_t)stream, static_cast<const Record*>(records), n,
                   clip_sigma, clip_bounds);
     COLVO_CHECK_LAUNCH("k_localize_bounds");
     return 0;
@@ -481,13 +447,12 @@ extern "C" int colvo_localize_finish(const void* records, const float* cam2world
     const int n = N * num_labels;
     const ObsOut o{n_pixels, n_samples, bbox, pixel, center_cam, cov_cam, center_world};
     const PolypOut p{n_frames, reinterpret_cast<long long*>(n_samples_total), first_frame, last_frame, position, cov_world};
-    const unsigned long long* ignored =
-        reinterpret_cast<const unsigned long long*>(static_cast<const char*>(records) + records_bytes(N, num_labels));
-    colvo::launch(k_localize_observations, dim3((n + NT - 1) / NT), dim3(NT), 0, s, static_cast<const Record*>(records), cam2world, n,
-                  num_labels, o, reinterpret_cast<long long*>(stats));
-    COLVO_CHECK_LAUNCH("k_localize_observations");
-    colvo::launch(k_localize_polyps, dim3(num_labels), dim3(64), 0, s, cam2world, N, num_labels, min_samples, o, p, ignored,
+    const Ws w = layout(const_cast<void*>(records), N, num_labels);
+    colvo::launch(k_localize_observations, dim3(blocks_of(n, NT)), dim3(NT), 0, s, (const Record*)w.records, cam2world, n, num_labels, o,
                   reinterpret_cast<long long*>(stats));
+    COLVO_CHECK_LAUNCH("k_localize_observations");
+    colvo::launch(k_localize_polyps, dim3(num_labels), dim3(64), 0, s, cam2world, N, num_labels, min_samples, o, p,
+                  (const unsigned long long*)w.ignored, reinterpret_cast<long long*>(stats));
     COLVO_CHECK_LAUNCH("k_localize_polyps");
     return 0;
 }

@@ -3,36 +3,14 @@
 // intestine", :29 "stitching together the dense depth maps of each frame using the colonoscopic trajectory").
 // Spec: oracle/colvo_spec.py backproject / stitch_point_cloud (oracle/SPEC.md §6c).  All HBM-bound: 4 B read and
 // 12 B written per pixel; the stitched cloud keeps the oracle's order (frame-major, row-major) through a per-block count,
-// one scan over the block counts and an ordered in-block compaction -- no atomics, so the output is deterministic.
-#include "common.h"
+// one scan over the block counts (k_scan_top of csrc/scan.hip: a block's count is already its chunk sum) and an ordered in-block
+// compaction -- no atomics, so the output is deterministic.
+#include "scene.h"
 
 namespace colvo {
 namespace {
 
 constexpr int NT = 256;
-
-struct Cam {          // per frame: intrinsics and the camera-to-world transform
-    float fx, fy, cx, cy;
-    float r[9];
-    float t[3];
-};
-
-__device__ __forceinline__ Cam load_cam(const float* __restrict__ K, const float* __restrict__ M, int b) {
-    Cam c;
-    const float* k = K + (size_t)b * 9;
-    const float* m = M + (size_t)b * 16;
-    c.fx = uniform_f(k[0]);
-    c.fy = uniform_f(k[4]);
-    c.cx = uniform_f(k[2]);
-    c.cy = uniform_f(k[5]);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-#pragma unroll
-        for (int j = 0; j < 3; ++j) c.r[i * 3 + j] = uniform_f(m[i * 4 + j]);
-        c.t[i] = uniform_f(m[i * 4 + 3]);
-    }
-    return c;
-}
 
 // Same operation order as the oracle: ((u - cx) / fx) * d, then R p + t as a dot product in x, y, z order.
 __device__ __forceinline__ void world_point(const Cam& c, float u, float v, float d, float& X, float& Y, float& Z) {
@@ -73,8 +51,8 @@ __global__ __launch_bounds__(NT) void k_backproject(const float* __restrict__ de
 }
 
 // ---- stitched cloud: strided pixels of N frames, depth < max_depth, compacted in order ---------------------------- //
-struct StitchGeom {
-    int H, W, stride, Hs, Ws, per_frame, blocks_per_frame;
+struct StitchGeom : StridedFrame {
+    int per_frame, blocks_per_frame;
 };
 
 __device__ __forceinline__ bool stitch_pixel(const StitchGeom& g, int idx, int& u, int& v) {
@@ -96,25 +74,6 @@ __global__ __launch_bounds__(NT) void k_stitch_count(const float* __restrict__ d
     if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = n;
     __syncthreads();
     if (threadIdx.x == 0) counts[blockIdx.y * g.blocks_per_frame + blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-}
-
-// one workgroup: exclusive scan of `n` block counts in place; total -> *total
-__global__ __launch_bounds__(NT) void k_stitch_scan(int32_t* __restrict__ counts, int n, int32_t* __restrict__ total) {
-    __shared__ int part[NT];
-    const int per = (n + NT - 1) / NT;
-    const int lo = min(threadIdx.x * per, n), hi = min(lo + per, n);
-    int s = 0;
-    for (int i = lo; i < hi; ++i) s += counts[i];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int run = 0;
-        for (int i = 0; i < NT; ++i) { const int t = part[i]; part[i] = run; run += t; }
-        *total = run;
-    }
-    __syncthreads();
-    int run = part[threadIdx.x];
-    for (int i = lo; i < hi; ++i) { const int t = counts[i]; counts[i] = run; run += t; }
 }
 
 __global__ __launch_bounds__(NT) void k_stitch_write(const float* __restrict__ depth, const float* __restrict__ K,
@@ -141,14 +100,15 @@ __global__ __launch_bounds__(NT) void k_stitch_write(const float* __restrict__ d
     o[0] = X; o[1] = Y; o[2] = Z;
 }
 
-bool stitch_geom(int H, int W, int stride, StitchGeom& g) {
-    if (H <= 0 || W <= 0 || stride <= 0) return false;
-    g.H = H; g.W = W; g.stride = stride;
-    g.Hs = (H + stride - 1) / stride;
-    g.Ws = (W + stride - 1) / stride;
+void stitch_tiling(StitchGeom& g) {
     g.per_frame = g.Hs * g.Ws;
-    g.blocks_per_frame = (g.per_frame + NT - 1) / NT;
-    return true;
+    g.blocks_per_frame = blocks_of(g.per_frame, NT);
+}
+
+bool stitch_geom(int N, int H, int W, int stride, StitchGeom& g) {
+    if (!strided_frame(N, H, W, stride, g)) return false;
+    stitch_tiling(g);
+    return (long long)N * g.blocks_per_frame < (1ll << 30);
 }
 
 }  // namespace
@@ -161,15 +121,17 @@ extern "C" int colvo_backproject(const float* depth, const float* K, const float
     COLVO_CHECK_ARG(depth && K && cam2world && points, "colvo_backproject: null pointer argument");
     COLVO_CHECK_ARG(B > 0 && H > 0 && W > 0 && B <= 65535 && (long long)H * W < (1ll << 30),
                     "colvo_backproject: bad shape B=%d H=%d W=%d", B, H, W);
-    colvo::launch(k_backproject, dim3((H * W + NT - 1) / NT, B), dim3(NT), 0, (hipStream_t)stream, depth, K,
-                       cam2world, H, W, points);
+    colvo::launch(k_backproject, dim3(blocks_of(H * W, NT), B), dim3(NT), 0, (hipStream_t)stream, depth, K, cam2world, H, W, points);
     COLVO_CHECK_LAUNCH("k_backproject");
     return 0;
 }
 
 extern "C" size_t colvo_stitch_workspace_ints(int N, int H, int W, int stride) {
+    // answers for all positive arguments, those the call refuses (N > 65535, H * W >= 2^30) included: as it always has
+    if (N <= 0 || H <= 0 || W <= 0 || stride <= 0) return 0;
     StitchGeom g;
-    if (N <= 0 || !stitch_geom(H, W, stride, g)) return 0;
+    static_cast<StridedFrame&>(g) = strided(H, W, stride);
+    stitch_tiling(g);
     return (size_t)N * g.blocks_per_frame;
 }
 
@@ -179,15 +141,12 @@ extern "C" int colvo_stitch_point_cloud(const float* depths, const float* K, con
     COLVO_CHECK_ARG(depths && K && cam2world && workspace && points && n_points,
                     "colvo_stitch_point_cloud: null pointer argument");
     StitchGeom g;
-    COLVO_CHECK_ARG(N > 0 && N <= 65535 && stitch_geom(H, W, stride, g) && (long long)H * W < (1ll << 30) &&
-                        (long long)N * g.blocks_per_frame < (1ll << 30),
-                    "colvo_stitch_point_cloud: bad shape N=%d H=%d W=%d stride=%d", N, H, W, stride);
+    COLVO_CHECK_ARG(stitch_geom(N, H, W, stride, g), "colvo_stitch_point_cloud: bad shape N=%d H=%d W=%d stride=%d", N, H, W, stride);
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid(g.blocks_per_frame, N);
     colvo::launch(k_stitch_count, grid, dim3(NT), 0, s, depths, g, max_depth, workspace);
     COLVO_CHECK_LAUNCH("k_stitch_count");
-    colvo::launch(k_stitch_scan, dim3(1), dim3(NT), 0, s, workspace, N * g.blocks_per_frame, n_points);
-    COLVO_CHECK_LAUNCH("k_stitch_scan");
+    if (int rc = scan_sums(workspace, N * g.blocks_per_frame, n_points, s)) return rc;
     colvo::launch(k_stitch_write, grid, dim3(NT), 0, s, depths, K, cam2world, g, max_depth, workspace, points);
     COLVO_CHECK_LAUNCH("k_stitch_write");
     return 0;

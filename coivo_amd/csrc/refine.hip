@@ -12,7 +12,7 @@
 //
 // Every float32 operation of a sample is individually rounded -- contraction is off for this whole file -- and the order of every
 // float64 addition is fixed by the code: a call's bits do not depend on scheduling or on the stream.
-#include "common.h"
+#include "scene.h"
 #include "tuning.h"
 
 #pragma clang fp contract(off)
@@ -43,8 +43,6 @@ struct Policy {
     int flags;
     double cap_g, cap_p;                   // (gate / sigma)^2 of the float32 quotient's stand-in gate * (1 / sigma)
 };
-
-__device__ __forceinline__ bool valid_depth(float d, float max_depth) { return (int)(d > 0.0f) & (int)(d < max_depth); }
 
 // grid (ceil(HW / NT), N)
 __global__ __launch_bounds__(NT) void k_refine_grey(const float* __restrict__ frames, int HW, float* __restrict__ grey) {
@@ -421,8 +419,6 @@ __global__ __launch_bounds__(NT_SOLVE) void k_refine_solve(const double* __restr
     s32[13] = (float)live_offset[e];
 }
 
-size_t pad16(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
-
 bool shape_ok(int E, int N, int H, int W) {
     return E > 0 && E <= 65535 && N > 0 && N <= 65535 && H > 0 && W > 0 && (long long)H * W < (1ll << 30);
 }
@@ -430,33 +426,28 @@ bool shape_ok(int E, int N, int H, int W) {
 Geom make_geom(int E, int N, int H, int W) {
     Geom g;
     g.N = N; g.H = H; g.W = W; g.E = E;
-    g.tiles_x = (W + TILE - 1) / TILE;
-    g.tiles = g.tiles_x * ((H + TILE - 1) / TILE);
-    g.strips = (g.tiles + TILES_PER_WG - 1) / TILES_PER_WG;
+    g.tiles_x = blocks_of(W, TILE);
+    g.tiles = g.tiles_x * blocks_of(H, TILE);
+    g.strips = blocks_of(g.tiles, TILES_PER_WG);
     return g;
 }
 
 struct Ws {
+    double* rows;                          // [E][strips][ROW]
     float* grey;                           // [N][H*W]
     float* st32;                           // [E][STATE]
     int32_t* status;                       // [E] (colvo_refine_accumulate; the loop uses its own output)
-    double* rows;                          // [E][strips][ROW]
+    size_t bytes;
 };
 
-size_t grey_bytes(int N, int H, int W) { return pad16((size_t)N * H * W * sizeof(float)); }
-size_t st32_bytes(int E) { return pad16((size_t)E * STATE * sizeof(float)); }
-size_t status_bytes(int E) { return pad16((size_t)E * sizeof(int32_t)); }
-
 Ws carve(void* base, const Geom& g) {
+    Carver c(base);
     Ws w;
-    char* p = static_cast<char*>(base);
-    w.rows = reinterpret_cast<double*>(p);
-    p += (size_t)g.E * g.strips * ROW * sizeof(double);
-    w.grey = reinterpret_cast<float*>(p);
-    p += grey_bytes(g.N, g.H, g.W);
-    w.st32 = reinterpret_cast<float*>(p);
-    p += st32_bytes(g.E);
-    w.status = reinterpret_cast<int32_t*>(p);
+    w.rows = c.take<double>((size_t)g.E * g.strips * ROW);
+    w.grey = c.take<float>((size_t)g.N * g.H * g.W);
+    w.st32 = c.take<float>((size_t)g.E * STATE);
+    w.status = c.take<int32_t>(g.E);
+    w.bytes = c.bytes();
     return w;
 }
 
@@ -493,8 +484,7 @@ using namespace colvo;
 
 extern "C" size_t colvo_refine_workspace_bytes(int E, int N, int H, int W, int iterations) {
     if (!shape_ok(E, N, H, W) || iterations < 0 || iterations > 64) return 0;
-    const Geom g = make_geom(E, N, H, W);
-    return (size_t)E * g.strips * ROW * sizeof(double) + grey_bytes(N, H, W) + st32_bytes(E) + status_bytes(E);
+    return carve(nullptr, make_geom(E, N, H, W)).bytes;
 }
 
 extern "C" int colvo_refine_accumulate(const float* depths, const float* frames, const float* K, int N, int H, int W,
@@ -505,15 +495,15 @@ extern "C" int colvo_refine_accumulate(const float* depths, const float* frames,
                     "colvo_refine_accumulate: null pointer argument");
     COLVO_CHECK_ARG(shape_ok(E, N, H, W), "colvo_refine_accumulate: bad shape E=%d N=%d H=%d W=%d", E, N, H, W);
     if (int rc = check_policy("colvo_refine_accumulate", sigma_geo, sigma_photo, gate_geo, gate_photo, max_depth, terms)) return rc;
-    COLVO_CHECK_ARG(((uintptr_t)workspace & 15) == 0, "colvo_refine_accumulate: workspace must be 16-byte aligned");
+    COLVO_CHECK_ARG(aligned16(workspace), "colvo_refine_accumulate: workspace must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     const Geom g = make_geom(E, N, H, W);
     const Ws w = carve(workspace, g);
     const Policy p = make_policy(sigma_geo, sigma_photo, gate_geo, gate_photo, max_depth, terms);
     const int HW = H * W;
-    colvo::launch(k_refine_grey, dim3((HW + NT - 1) / NT, N), dim3(NT), 0, s, frames, HW, w.grey);
+    colvo::launch(k_refine_grey, dim3(blocks_of(HW, NT), N), dim3(NT), 0, s, frames, HW, w.grey);
     COLVO_CHECK_LAUNCH("k_refine_grey");
-    colvo::launch(k_refine_init, dim3((E + NT - 1) / NT), dim3(NT), 0, s, edges, T, gain, offset, E, N, w.st32, w.status,
+    colvo::launch(k_refine_init, dim3(blocks_of(E, NT)), dim3(NT), 0, s, edges, T, gain, offset, E, N, w.st32, w.status,
                   (double*)nullptr, (double*)nullptr, (double*)nullptr);
     COLVO_CHECK_LAUNCH("k_refine_init");
     colvo::launch(k_refine_accum, dim3(g.strips, E), dim3(NT), 0, s, depths, (const float*)w.grey, K, edges, (const float*)w.st32,
@@ -539,16 +529,16 @@ extern "C" int colvo_refine_edges(const float* depths, const float* frames, cons
     if (int rc = check_policy("colvo_refine_edges", sigma_geo, sigma_photo, gate_geo, gate_photo, max_depth, terms)) return rc;
     COLVO_CHECK_ARG(damping >= 0.0 && damping < (double)__builtin_inff() && min_samples >= 1,
                     "colvo_refine_edges: bad damping %g (finite, >= 0) or min_samples %d (>= 1)", damping, min_samples);
-    COLVO_CHECK_ARG(((uintptr_t)workspace & 15) == 0, "colvo_refine_edges: workspace must be 16-byte aligned");
+    COLVO_CHECK_ARG(aligned16(workspace), "colvo_refine_edges: workspace must be 16-byte aligned");
     COLVO_CHECK_ARG(out_T != T_init, "colvo_refine_edges: out_T must not alias T_init");
     hipStream_t s = (hipStream_t)stream;
     const Geom g = make_geom(E, N, H, W);
     const Ws w = carve(workspace, g);
     const Policy p = make_policy(sigma_geo, sigma_photo, gate_geo, gate_photo, max_depth, terms);
     const int HW = H * W;
-    colvo::launch(k_refine_grey, dim3((HW + NT - 1) / NT, N), dim3(NT), 0, s, frames, HW, w.grey);
+    colvo::launch(k_refine_grey, dim3(blocks_of(HW, NT), N), dim3(NT), 0, s, frames, HW, w.grey);
     COLVO_CHECK_LAUNCH("k_refine_grey");
-    colvo::launch(k_refine_init, dim3((E + NT - 1) / NT), dim3(NT), 0, s, edges, T_init, (const double*)nullptr, (const double*)nullptr,
+    colvo::launch(k_refine_init, dim3(blocks_of(E, NT)), dim3(NT), 0, s, edges, T_init, (const double*)nullptr, (const double*)nullptr,
                   E, N, w.st32, status, out_T, out_gain, out_offset);
     COLVO_CHECK_LAUNCH("k_refine_init");
     Solve sv;

@@ -97,6 +97,50 @@ def test_round3_entry_points_validate_their_arguments(lib):
     assert rc != 0 and b"colvo_adam_pack_step" in lib.colvo_last_error()
 
 
+# The size queries of the post-training calls (reconstruct, fuse, localize, consistency, refine, evaluate, cloud): arguments -> bytes
+# (ints for the stitch), recorded from the library before the layouts moved onto the shared workspace carver (csrc/common.h).  Small,
+# ragged and refused arguments for each; a refused shape answers 0 -- except that the stitch query answers for every positive shape.
+# Every array that is not padded in today's layouts has a size that is a multiple of 16 bytes by its element (52 or 8 doubles, 32-byte
+# states, 16-int lines), so the carver's uniform padding cannot move anything: the table pins that, and the 0 answers.
+WORKSPACE_SIZES = {
+    "colvo_stitch_workspace_ints": [((1, 1, 1, 1), 1), ((3, 17, 23, 1), 6), ((8, 256, 320, 4), 160), ((2, 5, 7, 9), 2),
+                                    ((512, 256, 320, 1), 163840), ((70000, 8, 8, 1), 70000), ((0, 8, 8, 1), 0), ((2, 0, 8, 1), 0),
+                                    ((2, 8, -3, 1), 0), ((2, 8, 8, 0), 0)],
+    "colvo_fuse_plan_workspace_bytes": [((1, 1, 1, 1, 8, 8, 8), 16432), ((3, 17, 23, 1, 8, 16, 24), 16464),
+                                        ((4, 64, 96, 2, 40, 24, 16), 16656), ((8, 256, 320, 1, 1024, 1024, 1024), 16795648),
+                                        ((2, 5, 7, 9, 2048, 2048, 512), 33574912), ((3, 17, 23, 1, 12, 8, 8), 0),
+                                        ((3, 17, 23, 1, 8, 8, 0), 0), ((0, 17, 23, 1, 8, 8, 8), 0), ((65536, 17, 23, 1, 8, 8, 8), 0),
+                                        ((3, 17, 23, 0, 8, 8, 8), 0), ((3, 32768, 32768, 1, 8, 8, 8), 0),
+                                        ((65535, 256, 320, 1, 8, 8, 8), 0), ((8, 256, 320, 1, 8192, 8192, 8192), 0)],
+    "colvo_fuse_pool_bytes": [((1,), 16384), ((1066,), 17465344), ((4194303,), 68719460352), ((0,), 0), ((-1,), 0), ((4194304,), 0)],
+    "colvo_fuse_extract_workspace_bytes": [((1,), 32), ((3,), 32), ((4096,), 16400), ((4097,), 16416), ((1066,), 4288),
+                                           ((4194303,), 16781312), ((0,), 0), ((-5,), 0), ((4194304,), 0)],
+    "colvo_localize_workspace_bytes": [((1, 1), 144), ((3, 5), 1952), ((7, 255), 228544), ((65535, 255), 2139586688), ((0, 1), 0),
+                                       ((65536, 1), 0), ((1, 0), 0), ((1, 256), 0)],
+    "colvo_consistency_workspace_bytes": [((1, 1), 608), ((5, 3), 4000), ((7, 16), 14336), ((65535, 16), 134215680), ((0, 1), 0),
+                                          ((65536, 2), 0), ((1, 0), 0), ((1, 17), 0)],
+    "colvo_refine_workspace_bytes": [((1, 2, 8, 8, 1), 1008), ((3, 5, 17, 23, 4), 9280), ((7, 8, 256, 320, 0), 2854880),
+                                     ((5, 3, 33, 47, 64), 23136), ((65535, 2, 9, 9, 1), 31719600), ((0, 2, 8, 8, 1), 0),
+                                     ((1, 65536, 8, 8, 1), 0), ((1, 2, 0, 8, 1), 0), ((1, 2, 32768, 32768, 1), 0), ((1, 2, 8, 8, 65), 0),
+                                     ((1, 2, 8, 8, -1), 0)],
+    "colvo_depth_metrics_workspace_bytes": [((1, 1, 1), 16480), ((3, 17, 23), 49440), ((8, 256, 320), 136448), ((2, 91, 91), 33088),
+                                            ((65535, 5, 7), 1080016800), ((0, 8, 8), 0), ((65536, 8, 8), 0), ((2, 0, 8), 0),
+                                            ((2, 8, -1), 0), ((1, 32768, 32768), 0)],
+    "colvo_cloud_workspace_bytes": [((0, 0), 8423712), ((5, 0), 8423712), ((0, 7), 8423856), ((1000, 1001), 8443744),
+                                    ((3, 1073741823), 21483260176), ((1073741823, 3), 8423776), ((-1, 0), 0), ((0, -1), 0),
+                                    ((1073741824, 0), 0), ((0, 1073741824), 0)],
+}
+
+
+def test_post_training_workspace_sizes_are_the_recorded_ones(lib):
+    """Host-only entries: no GPU.  Every size query include/colvo.h declares for these calls is in the table."""
+    queries = [n for n in _declared_symbols() if re.search(r"_workspace_(bytes|ints)$|_pool_bytes$", n)]
+    assert sorted(queries) == sorted(WORKSPACE_SIZES)
+    for name, rows in WORKSPACE_SIZES.items():
+        for args, size in rows:
+            assert getattr(lib, name)(*args) == size, (name, args)
+
+
 def test_python_ops_refuse_cpu_tensors():
     from coivo_amd import functional as Fh
     t = torch.zeros(1, 3, 8, 8)

@@ -235,12 +235,14 @@ def test_tuning_entries_and_isa(lib, tmp_path):
     asm = open(build.emit_asm("fuse.hip", str(tmp_path / "fuse.s"))).read()
     assert "cmpswap" not in asm
     assert asm.count("global_atomic_add_x2") >= 5 and "ds_add_u64" in asm
-    kernels = re.findall(r"\.name:\s+(\S*k_fuse\S*)", asm)
-    assert len(kernels) >= 9, kernels
-    for key in ("private_segment_fixed_size", "sgpr_spill_count", "vgpr_spill_count"):
-        vals = re.findall(rf"\.{key}:\s+(\d+)", asm)
-        assert len(vals) >= 9 and all(int(v) == 0 for v in vals), (key, vals)
-    assert not re.search(r"\bscratch_(load|store)", asm)
+    # its own five kernels, and the four of the ordered scan it numbers bricks and rows with (csrc/scan.hip)
+    for listing, prefix, n in ((asm, "k_fuse", 5), (open(build.emit_asm("scan.hip", str(tmp_path / "scan.s"))).read(), "k_scan", 4)):
+        kernels = re.findall(rf"\.name:\s+(\S*{prefix}\S*)", listing)
+        assert len(kernels) >= n, kernels
+        for key in ("private_segment_fixed_size", "sgpr_spill_count", "vgpr_spill_count"):
+            vals = re.findall(rf"\.{key}:\s+(\d+)", listing)
+            assert len(vals) >= n and all(int(v) == 0 for v in vals), (key, vals)
+        assert not re.search(r"\bscratch_(load|store)", listing)
 
 
 # ---- Python ------------------------------------------------------------------------------------------------------------ #

@@ -173,6 +173,20 @@ def test_no_two_samples_share_a_voxel():
     _assert_equal(_fuse(depths, colors, K, M, **kw), want)
 
 
+def test_brick_table_of_more_than_256_chunks():
+    """1024^3 voxels are 128^3 = 2 097 152 bricks: 512 chunks of 4096 table entries, so every thread of the scan's one top-level
+    workgroup takes two chunk sums (no other case here has more than 256 chunks, where it takes at most one).  The marked bricks lie
+    in chunks on both sides of entry 256 of the sums."""
+    depths, colors, K, M = _scene(3, 17, 23)
+    kw = dict(stride=1, max_depth=MAX_DEPTH, voxel_size=0.0078125, origin=(-4.0, -4.0, -1.0), dims=(1024, 1024, 1024), min_obs=1)
+    want = _ref(depths, colors, K, M, **kw)
+    assert (want["n_input"], want["n_outside"], want["n_bricks"], want["n_voxels"]) == (1076, 0, 1066, 1076)
+    b = want["voxels"] >> 3
+    chunks = np.unique(((b[:, 2] * 128 + b[:, 1]) * 128 + b[:, 0]) // 4096)
+    assert len(chunks) == 131 and chunks.min() == 90 and chunks.max() == 358
+    _assert_equal(_fuse(depths, colors, K, M, **kw), want)
+
+
 @pytest.mark.parametrize("with_colors", [True, False])
 @pytest.mark.parametrize("rounds,row_adds", [(0, 0), (0, 1), (1, 1), (8, 0), (32, 1), (32, 0)])
 def test_result_does_not_depend_on_how_the_adds_are_issued(rounds, row_adds, with_colors):
