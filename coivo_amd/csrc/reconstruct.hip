@@ -108,7 +108,8 @@ void stitch_tiling(StitchGeom& g) {
 bool stitch_geom(int N, int H, int W, int stride, StitchGeom& g) {
     if (!strided_frame(N, H, W, stride, g)) return false;
     stitch_tiling(g);
-    return (long long)N * g.blocks_per_frame < (1ll << 30);
+    // a block index stays below 2^30; a slot (k_stitch_write: before + popc, and the scan's running sums) is an int up to N * Hs * Ws
+    return (long long)N * g.blocks_per_frame < (1ll << 30) && (long long)N * g.per_frame < (1ll << 31);
 }
 
 }  // namespace
@@ -138,10 +139,10 @@ extern "C" size_t colvo_stitch_workspace_ints(int N, int H, int W, int stride) {
 extern "C" int colvo_stitch_point_cloud(const float* depths, const float* K, const float* cam2world, int N, int H, int W,
                                         int stride, float max_depth, int32_t* workspace, float* points,
                                         int32_t* n_points, colvo_stream_t stream) {
+    StitchGeom g;           // the shape first: a refused shape is reported as one whatever the pointers are
+    COLVO_CHECK_ARG(stitch_geom(N, H, W, stride, g), "colvo_stitch_point_cloud: bad shape N=%d H=%d W=%d stride=%d", N, H, W, stride);
     COLVO_CHECK_ARG(depths && K && cam2world && workspace && points && n_points,
                     "colvo_stitch_point_cloud: null pointer argument");
-    StitchGeom g;
-    COLVO_CHECK_ARG(stitch_geom(N, H, W, stride, g), "colvo_stitch_point_cloud: bad shape N=%d H=%d W=%d stride=%d", N, H, W, stride);
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid(g.blocks_per_frame, N);
     colvo::launch(k_stitch_count, grid, dim3(NT), 0, s, depths, g, max_depth, workspace);

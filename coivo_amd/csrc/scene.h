@@ -1,6 +1,8 @@
 // scene.h -- what the post-training kernels share about depth maps, cameras and frames, and the library's one
-// ordered scan (csrc/scan.hip).  The world-point arithmetic is NOT here: reconstruct.hip, fuse.hip and consistency.hip each pin
-// their own operation order against their own replica under tests/.
+// ordered scan (csrc/scan.hip).  The world-point arithmetic is NOT here: fuse.hip and consistency.hip each pin their own operation
+// order (no FMA contraction) against their own bit-exact replica under tests/.  reconstruct.hip's order is NOT pinned -- the compiler
+// may contract its products and sums --: its world point is held to the float64 replica tests/reconstruct_ref.py within a bound
+// derived from its operation count, 7 u (|r0 px| + |r1 py| + |r2 d| + |t|) with u = 2^-24.
 #pragma once
 #include "common.h"
 

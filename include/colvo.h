@@ -441,7 +441,14 @@ int colvo_backproject(const float* depth, const float* K, const float* cam2world
 /* Every `stride`-th pixel (rows and columns) of N frames whose depth is < max_depth, back-projected and compacted in
  * frame-major, row-major order (deterministic: counts + scan, no atomics).  points must hold
  * N*ceil(H/stride)*ceil(W/stride)*3 floats; n_points[0] receives the number of points written.
- * workspace: colvo_stitch_workspace_ints(N,H,W,stride) int32. */
+ * The comparison is the float32 one, d < max_depth with max_depth as this call receives it: NaN and +inf are dropped; -inf, 0 and
+ * negative depths are kept.  The world point is float32 in an order that is not pinned (products and sums may be contracted): it
+ * lies within 7 u (|r0 px| + |r1 py| + |r2 d| + |t|), u = 2^-24, of the exact value of px = (u - cx) / fx * d, X = r0 px + r1 py +
+ * r2 d + t on the float32 inputs (tests/reconstruct_ref.py).
+ * workspace: colvo_stitch_workspace_ints(N,H,W,stride) int32; on return it holds the exclusive prefix sums of the kept counts of
+ * the 256-sample blocks (ceil(ceil(H/stride)*ceil(W/stride) / 256) per frame, frame-major).
+ * Limits: N <= 65535, H*W < 2^30, N * blocks per frame < 2^30 and N*ceil(H/stride)*ceil(W/stride) < 2^31 (a point's row is an
+ * int32); a shape beyond them is refused before the pointers are looked at. */
 size_t colvo_stitch_workspace_ints(int N, int H, int W, int stride);
 int colvo_stitch_point_cloud(const float* depths, const float* K, const float* cam2world, int N, int H, int W,
                              int stride, float max_depth, int32_t* workspace, float* points, int32_t* n_points,

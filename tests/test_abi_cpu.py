@@ -141,6 +141,21 @@ def test_post_training_workspace_sizes_are_the_recorded_ones(lib):
             assert getattr(lib, name)(*args) == size, (name, args)
 
 
+def test_stitch_refuses_a_cloud_whose_rows_leave_int32(lib):
+    """A point's row is an int in k_stitch_write: N * ceil(H/stride) * ceil(W/stride) >= 2^31 is refused as a shape, and the shape is
+    looked at before the pointers.  All pointers are NULL here: nothing can launch, with the check or without it."""
+    N, H, W = 65535, 1024, 1024                          # 4096 blocks per frame: N * blocks < 2^30 passes, 6.9e10 rows do not fit
+    assert lib.colvo_stitch_workspace_ints(N, H, W, 1) == N * 4096 < 2 ** 30 and N * H * W >= 2 ** 31
+    rc = lib.colvo_stitch_point_cloud(0, 0, 0, N, H, W, 1, 10.0, 0, 0, 0, 0)
+    assert rc != 0 and lib.colvo_last_error().startswith(b"colvo_stitch_point_cloud: bad shape"), lib.colvo_last_error()
+    rc = lib.colvo_stitch_point_cloud(0, 0, 0, 32767, 256, 256, 1, 10.0, 0, 0, 0, 0)         # 2^31 - 65536 rows: the shape is accepted
+    assert rc != 0 and b"null pointer" in lib.colvo_last_error(), lib.colvo_last_error()
+    rc = lib.colvo_stitch_point_cloud(0, 0, 0, 32768, 256, 256, 1, 10.0, 0, 0, 0, 0)         # 2^31 rows exactly
+    assert rc != 0 and b"bad shape" in lib.colvo_last_error(), lib.colvo_last_error()
+    rc = lib.colvo_stitch_point_cloud(0, 0, 0, 32768, 256, 256, 2, 10.0, 0, 0, 0, 0)         # ... a quarter of them at stride 2
+    assert rc != 0 and b"null pointer" in lib.colvo_last_error(), lib.colvo_last_error()
+
+
 def test_python_ops_refuse_cpu_tensors():
     from coivo_amd import functional as Fh
     t = torch.zeros(1, 3, 8, 8)
