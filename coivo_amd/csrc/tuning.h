@@ -119,7 +119,12 @@ namespace tune {
     /* ---- depth consistency (consistency.hip) ---- */                                                                              \
     X(consist_stat_lines, 8, "a workgroup's five integer adds go to one of this many 64-byte counter lines of its frame (1..8; 1: "    \
                              "every workgroup of a frame adds to the same line).  Integer sums: the result does not depend on it.  "  \
-                             "512 frames of 256x320, window 2, whole call: 1 -> 574.6 us, 8 -> 566.0 (tools/bench_consistency.py)")
+                             "512 frames of 256x320, window 2, whole call: 1 -> 574.6 us, 8 -> 566.0 (tools/bench_consistency.py)") \
+    /* ---- cloud rendering (render.hip) ---- */                                                                                     \
+    X(render_load_first, 1, "a splat reads a pixel's key before its 64-bit atomic minimum and skips the atomic when the stored key is "  \
+                            "already <= its own (keys only decrease: a stale read costs an atomic, never skips a needed one).  The "   \
+                            "result does not depend on it.  543 031 points into 512 views of 256x320, whole call, alternating call by "  \
+                            "call: 0 -> 10881.4 us, 1 -> 6122.5 (tools/bench_render.py)")
 
 struct Table {
 #define X(name, dflt, doc) double name = dflt;

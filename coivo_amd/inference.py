@@ -7,7 +7,7 @@ maps of each frame using the colonoscopic trajectory").  filter_depths is the cr
 §3.6f, csrc/consistency.hip).  Spec: oracle/colvo_spec.py integrate_trajectory / backproject /
 stitch_point_cloud (oracle/SPEC.md §6c).  The per-pixel work runs in csrc/reconstruct.hip; the trajectory integration is N
 products of 4x4 matrices and is done on the host in float64 (it is control flow, not a kernel).  The fusion runs in
-csrc/fuse.hip.
+csrc/fuse.hip.  render_cloud / render_fused draw a cloud back into camera views (csrc/render.hip).
 """
 from __future__ import annotations
 
@@ -469,6 +469,93 @@ def refine_trajectory(depths: torch.Tensor, frames: torch.Tensor, K: torch.Tenso
     return torch.stack(out), res
 
 
+class Render(NamedTuple):
+    """What reconstruct_sequence renders when asked: the fused cloud into every frame's own camera (render_fused).  The defaults
+    are choices, not tuned values."""
+    radius: Optional[float] = None   # world half-width of a splat; None: the fused cloud's voxel_size
+    max_splat: int = 8               # largest half-width of a footprint in pixels
+
+
+class RenderedViews(NamedTuple):
+    depth: torch.Tensor              # [N,1,H,W] float32: camera-z of the nearest point, +inf where no point landed
+    index: torch.Tensor              # [N,1,H,W] int32: its row in the cloud, -1 where empty
+    colors: Optional[torch.Tensor]   # [N,3,H,W] float32: its colour, 0 where empty (None without colours)
+    stats: torch.Tensor              # [N,4] int32: points in front, points drawn, points in front and clipped, covered pixels
+
+
+def _check_render(who: str, radius, max_splat, max_depth) -> None:
+    """ValueError for what colvo_render_cloud would refuse of the policy."""
+    if isinstance(max_splat, bool) or not isinstance(max_splat, int):
+        raise ValueError(f"{who}: max_splat must be an int, got {max_splat!r}")
+    if not 0 <= max_splat <= 32:
+        raise ValueError(f"{who}: max_splat must be in 0..32, got {max_splat}")
+    try:
+        ok = math.isfinite(_f32(radius)) and _f32(radius) >= 0.0
+    except (TypeError, ValueError, OverflowError, struct.error):
+        ok = False
+    if not ok:
+        raise ValueError(f"{who}: radius must be finite and >= 0 (as float32), got {radius!r}")
+    if not _finite_pos32(max_depth):
+        raise ValueError(f"{who}: max_depth must be finite and positive (as float32), got {max_depth!r}")
+
+
+def render_cloud(points: torch.Tensor, K: torch.Tensor, cam2world: torch.Tensor, H: int, W: int, *, radius: float,
+                 colors: Optional[torch.Tensor] = None, max_splat: int = 8, max_depth: float = MAX_DEPTH) -> RenderedViews:
+    """A point cloud drawn into N camera views of H x W pixels (contract: include/colvo.h colvo_render_cloud, DESIGN.md §3.6j;
+    csrc/render.hip).  points [M,3] in the world frame, colors [M,3] or None, K [3,3] or [N,3,3], cam2world [N,4,4], float32 on the
+    device.  Every point in front of a camera (1e-3 < P_z < max_depth) is drawn as a screen-aligned square of world half-width
+    `radius`, at most max_splat pixels to each side and at least its nearest pixel; a pixel keeps the nearest point, equal depths
+    the smallest row.  The cameras need not be frames of the sequence.  Pinned float32 arithmetic, an integer minimum and integer
+    sums: identical bits on every call and stream, equal to the NumPy replica tests/render_ref.py.
+
+    A pixel no point landed on gets depth +inf and index -1: stitch_point_cloud, fuse_point_cloud, localize_polyps and
+    filter_depths drop +inf, and `index >= 0` is the mask depth_metrics takes.  A square carries ONE depth: on a wall seen at a
+    grazing angle the square of a nearer neighbour wins the pixel, so the rendered depth is biased towards the camera by about
+    radius x slope (DESIGN.md §3.6j has the figures).  No read-back and no host synchronisation."""
+    who = "render_cloud"
+    _check_render(who, radius, max_splat, max_depth)
+    for name, val in (("H", H), ("W", W)):
+        if isinstance(val, bool) or not isinstance(val, int) or val < 1:
+            raise ValueError(f"{who}: {name} must be a positive int, got {val!r}")
+    if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError(f"{who}: points must be [M,3]")
+    if not isinstance(cam2world, torch.Tensor) or cam2world.dim() != 3:
+        raise ValueError(f"{who}: cam2world must be [N,4,4]")
+    M, N = points.shape[0], cam2world.shape[0]
+    if not 1 <= N <= 65535 or H * W >= 1 << 30 or N * H * W >= 1 << 31 or M >= 1 << 31:
+        raise ValueError(f"{who}: M={M} N={N} H={H} W={W} beyond the kernels' limits (M < 2^31, 1 <= N <= 65535, H*W < 2^30, "
+                         "N*H*W < 2^31)")
+    points = _chk(points, "points", (M, 3))
+    cam2world = _chk(cam2world, "cam2world", (N, 4, 4))
+    if isinstance(K, torch.Tensor) and K.dim() == 2:
+        K = K.unsqueeze(0).expand(N, 3, 3)
+    K = _chk(K, "K", (N, 3, 3))
+    if colors is not None:
+        colors = _chk(colors, "colors", (M, 3))
+    lib = _lib.load()
+    dev = points.device
+    scratch = torch.empty(int(lib.colvo_render_scratch_bytes(N, H, W)), device=dev, dtype=torch.uint8)
+    depth = torch.empty(N, 1, H, W, device=dev, dtype=torch.float32)
+    index = torch.empty(N, 1, H, W, device=dev, dtype=torch.int32)
+    out_colors = torch.empty(N, 3, H, W, device=dev, dtype=torch.float32) if colors is not None else None
+    stats = torch.empty(N, 4, device=dev, dtype=torch.int32)
+    _lib.check(lib.colvo_render_cloud(_lib.ptr(points), _lib.ptr(colors), M, _lib.ptr(K), _lib.ptr(cam2world), N, H, W, float(radius),
+                                      max_splat, float(max_depth), _lib.ptr(scratch), _lib.ptr(depth), _lib.ptr(index),
+                                      _lib.ptr(out_colors), _lib.ptr(stats), _lib.stream_ptr()), "colvo_render_cloud")
+    return RenderedViews(depth, index, out_colors, stats)
+
+
+def render_fused(fused: FusedCloud, K: torch.Tensor, cam2world: torch.Tensor, H: int, W: int, *, radius: Optional[float] = None,
+                 max_splat: int = 8, max_depth: float = MAX_DEPTH) -> RenderedViews:
+    """render_cloud of a FusedCloud's points and colours.  radius defaults to fused.voxel_size: the mean positions of neighbouring
+    voxels are at most two voxels apart per axis, so squares of half-width one voxel close a fronto-parallel wall.  That default
+    is a choice, not a tuned value."""
+    if not isinstance(fused, FusedCloud):
+        raise ValueError("render_fused: fused must be a FusedCloud")
+    return render_cloud(fused.points, K, cam2world, H, W, radius=fused.voxel_size if radius is None else radius,
+                        colors=fused.colors, max_splat=max_splat, max_depth=max_depth)
+
+
 def write_ply(path, points: torch.Tensor, colors: Optional[torch.Tensor] = None) -> None:
     """Binary little-endian PLY: `float x y z` per vertex and, with colours [M,3] in [0,1], `uchar red green blue`
     (rint(c * 255), clamped).  Host code; one device -> host copy."""
@@ -513,23 +600,28 @@ class Reconstruction(_ReconstructionFields):
     of the same depths and trajectory (coivo_amd.localize), else None; and `consistency`: with a Consistency policy the
     ConsistencyResult whose depths points, fused and polyps were computed from (`depths` stays the raw network output), else
     None; and `refinement`: with a Refinement policy the RefinementResult of the consecutive pairs -- `cam2world` is then the
-    refined trajectory, `rel_poses` stays the raw network output -- else None."""
+    refined trajectory, `rel_poses` stays the raw network output -- else None; and `rendered`: with a Render policy the
+    RenderedViews of `fused` in every frame's own camera along `cam2world`, else None."""
     polyps = None               # Optional[PolypLocalization]
     consistency = None          # Optional[ConsistencyResult]
     refinement = None           # Optional[RefinementResult]
+    rendered = None             # Optional[RenderedViews]
 
-    def __new__(cls, depths, rel_poses, cam2world, points, fused=None, polyps=None, consistency=None, refinement=None):
+    def __new__(cls, depths, rel_poses, cam2world, points, fused=None, polyps=None, consistency=None, refinement=None,
+                rendered=None):
         self = super().__new__(cls, depths, rel_poses, cam2world, points, fused)
         self.polyps = polyps
         self.consistency = consistency
         self.refinement = refinement
+        self.rendered = rendered
         return self
 
     def _replace(self, **kw):
         polyps = kw.pop("polyps", self.polyps)
         consistency = kw.pop("consistency", self.consistency)
         refinement = kw.pop("refinement", self.refinement)
-        return type(self)(*super()._replace(**kw), polyps=polyps, consistency=consistency, refinement=refinement)
+        rendered = kw.pop("rendered", self.rendered)
+        return type(self)(*super()._replace(**kw), polyps=polyps, consistency=consistency, refinement=refinement, rendered=rendered)
 
 
 @torch.no_grad()
@@ -552,7 +644,7 @@ def reconstruct_sequence(depth_net, pose_net, frames: torch.Tensor, K: torch.Ten
                          max_depth: float = MAX_DEPTH, chunk: int = 16, voxel_size: Optional[float] = None,
                          min_obs: int = 1, labels: Optional[torch.Tensor] = None,
                          num_labels: Optional[int] = None, consistency: Optional[Consistency] = None,
-                         refine: Optional[Refinement] = None) -> Reconstruction:
+                         refine: Optional[Refinement] = None, render: Optional[Render] = None) -> Reconstruction:
     """frames [N+1,3,H,W] of one sequence, K [3,3] or [N+1,3,3] -> depth of every frame, the pose of every consecutive
     pair (DCDP: PoseNet sees both depth maps), the integrated trajectory and the stitched cloud.  With a voxel_size also
     the fused cloud of the same samples, coloured by the frames (fuse_point_cloud; `fused`, else None).  With labels
@@ -562,7 +654,9 @@ def reconstruct_sequence(depth_net, pose_net, frames: torch.Tensor, K: torch.Ten
     filtered depths, `depths` stays the raw network output and the ConsistencyResult is `consistency` (else None).  With a
     Refinement policy the integrated trajectory first passes refine_trajectory (raw depths, the frames, same K and max_depth): the
     refined trajectory is `cam2world` and is what the filter, the stitching, the fusion and the localisation use; `rel_poses` stays
-    the raw network output and the RefinementResult is `refinement` (else None)."""
+    the raw network output and the RefinementResult is `refinement` (else None).  With a Render policy (needs voxel_size) the fused
+    cloud is drawn back into every frame's own camera along the trajectory the call used (render_fused: same K, max_depth and
+    image size; radius None is the voxel size) and the RenderedViews is `rendered` (else None)."""
     n = frames.shape[0]
     if n < 2:
         raise ValueError("reconstruct_sequence: need at least two frames")
@@ -574,6 +668,11 @@ def reconstruct_sequence(depth_net, pose_net, frames: torch.Tensor, K: torch.Ten
     if refine is not None:
         refine = Refinement(*refine)
         _check_refinement("reconstruct_sequence", refine, max_depth)
+    if render is not None:
+        render = Render(*render)
+        if voxel_size is None:
+            raise ValueError("reconstruct_sequence: render needs voxel_size (it draws the fused cloud)")
+        _check_render("reconstruct_sequence", voxel_size if render.radius is None else render.radius, render.max_splat, max_depth)
     if K.dim() == 2:
         K = K.unsqueeze(0).expand(n, 3, 3)
     K = K.to(frames.device, torch.float32).contiguous()
@@ -597,4 +696,8 @@ def reconstruct_sequence(depth_net, pose_net, frames: torch.Tensor, K: torch.Ten
     if labels is not None:
         from . import localize                       # (localize imports this module)
         polyps = localize.localize_polyps(depths, labels, K, traj32, num_labels=num_labels, stride=1, max_depth=max_depth)
-    return Reconstruction(raw, rel, traj, cloud, fused, polyps, checked, refined)
+    rendered = None
+    if render is not None:
+        rendered = render_fused(fused, K, traj32, int(frames.shape[2]), int(frames.shape[3]), radius=render.radius,
+                                max_splat=render.max_splat, max_depth=max_depth)
+    return Reconstruction(raw, rel, traj, cloud, fused, polyps, checked, refined, rendered)

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define COLVO_ABI_VERSION 19
+#define COLVO_ABI_VERSION 20
 
 typedef void* colvo_stream_t; /* hipStream_t */
 
@@ -565,6 +565,36 @@ size_t colvo_consistency_workspace_bytes(int N, int window);
 int colvo_consistency_filter(const float* depths, const float* K, const float* cam2world, int N, int H, int W, int window, int step,
                              float rel_tol, int min_agree, int max_violated, float max_depth, void* workspace, float* out_depths,
                              uint8_t* out_votes, int32_t* out_stats, colvo_stream_t stream);
+
+/* Point cloud into camera views: z-buffered, screen-aligned square splats.  points [M,3] float32 in the world frame,
+ * colors [M,3] float32 or NULL, K [N,3,3] (per frame), cam2world [N,4,4] float32 (the rotation block r is taken as orthonormal, t its
+ * translation), images of H x W pixels, radius in world units, max_splat the largest half-width of a footprint in pixels.  Float32,
+ * every operation individually rounded in the order written (no FMA contraction), plain divisions.  Per frame n and point i (X):
+ *   camera      q_a = X_a - t_a,  P_a = (r_0a * q_0 + r_1a * q_1) + r_2a * q_2  (the transposed rotation applied to X - t).
+ *   front       iff P_z > 1e-3f and P_z < max_depth (NaN falls out).
+ *   centre      x = (fx * P_x) / P_z + cx, y = (fy * P_y) / P_z + cy;  hx = (fx * radius) / P_z, hy = (fy * radius) / P_z;
+ *               clipped iff hx > max_splat or hy > max_splat; then hx = hx > max_splat ? max_splat : hx, the same for hy.
+ *   on screen   iff x >= -(max_splat + 1), x <= (float)(W + max_splat), y >= -(max_splat + 1), y <= (float)(H + max_splat): NaN and
+ *               infinities fail, and what passes converts to an integer safely.
+ *   footprint   uc = floor(x + 0.5f), u_lo = max((int)min(ceil(x - hx), uc), 0), u_hi = min((int)max(floor(x + hx), uc), W - 1)
+ *               (the inner min / max on floats, the outer on integers), the same in v with y, hy, H: a splat smaller than a pixel
+ *               still lands on its nearest pixel.  The point is drawn iff front, on screen, u_lo <= u_hi and v_lo <= v_hi.
+ *   key         (uint64(bits(P_z)) << 32) | uint32(i); P_z is positive, so its bits order as unsigned integers.  Every pixel of the
+ *               footprint takes the minimum key: the nearest point wins, equal depths go to the smallest index.
+ *   outputs     out_depth [N,1,H,W] float32: the winning P_z, +inf where no point landed (dropped by the `d < max_depth` of
+ *               colvo_stitch_point_cloud and the `0 < d < max_depth` of the fusion, the localisation and the consistency filter);
+ *               out_index [N,1,H,W] int32: the winning point, -1 where empty;  out_colors [N,3,H,W] float32: colors[index], 0 where
+ *               empty -- written iff out_colors is given; colors must then be given too (it may be NULL when M = 0) and must be
+ *               NULL otherwise;  out_stats [N,4] int32 per frame: points in front, points drawn, points in front and clipped,
+ *               covered pixels.  Integer sums and a minimum: identical bits on every call and stream.
+ * scratch: colvo_render_scratch_bytes(N, H, W) bytes, 16-byte aligned: the key buffer (N * H * W 64-bit words) and the per-frame
+ * counter lines, both written by the call.  0 for a shape the call refuses.  No read-back and no host synchronisation.
+ * Limits: 0 <= M < 2^31 (points may be NULL when M = 0), 1 <= N <= 65535, H, W >= 1, H*W < 2^30, N*H*W < 2^31, radius finite and
+ * >= 0, max_splat in 0..32, max_depth finite and positive. */
+size_t colvo_render_scratch_bytes(int N, int H, int W);
+int colvo_render_cloud(const float* points, const float* colors, int M, const float* K, const float* cam2world, int N, int H, int W,
+                       float radius, int max_splat, float max_depth, void* scratch, float* out_depth, int32_t* out_index,
+                       float* out_colors, int32_t* out_stats, colvo_stream_t stream);
 
 /* Pose refinement by dense depth and intensity alignment: a few Gauss-Newton steps per edge on the per-pixel geometric
  * and photometric residuals of the two frames it connects, starting from the pose given.  depths [N,1,H,W], frames [N,3,H,W], K [N,3,3]
