@@ -60,7 +60,7 @@ struct Bwd16K {
     const float* dpre;   // [B][H][W] fp32
     const float* head_w; // [9][16] fp32
     // HEAD form, optional: the head's own weight / bias gradient as well -- dWh[t][c] = sum_p dpre[p] y[p + t - 1][c], db_h = sum_p dpre[p]
-    // -- as one partial row of 9 * 16 + 1 floats per WAVE (4 rows per workgroup) for the table reduction of csrc/misc.hip
+    // -- as one partial row of 9 * 16 + 1 floats per WAVE (4 rows per workgroup) for the table reduction of csrc/heads.hip
     float* head_partials;
     // SLAB way-out (colvo_conv_bwd_fused_det): workgroup r stores its sums into row r of [gridDim.x][16 * 9 * 16] weight slabs followed by
     // [gridDim.x][16] bias slabs (the layout of ColvoWgradSlabs, include/colvo.h) instead of adding them to dw / db
@@ -179,7 +179,7 @@ __global__ __launch_bounds__(NT, MODE == 2 ? 3 : MODE == 1 ? COLVO_BWD16_HEAD_WG
         }
     };
     // HEAD: the gradient g[p][c] = (y[p][c] > 0) * sum_t head_w[t][c] * dpre[p + 1 - t] on the 180 patch pixels, rounded to bf16 as
-    // csrc/misc.hip k_depth_head_dgrad16 stores it -- BY MFMA (round 5).  Round 4 made it on the VALU, a thread per staged granule: 9
+    // csrc/heads.hip k_depth_head_dgrad16 stores it -- BY MFMA (round 5).  Round 4 made it on the VALU, a thread per staged granule: 9
     // d(pre) reads and 72 fp32 FMAs per granule from 72 registers of head weights -- 195 of the tile loop's 324 VALU instructions in a
     // kernel that is issue-bound, and the registers that kept the MFMA phases from being pipelined.  As a product it is tiny:
     // [16 c] x [K = 9 taps] per pixel; both factors are fp32, so each is split into bf16 hi + lo and K carries the three products that
@@ -477,7 +477,7 @@ __global__ __launch_bounds__(NT, MODE == 2 ? 3 : MODE == 1 ? COLVO_BWD16_HEAD_WG
 
 // ---- the depth head's weight / bias gradient by MFMA (colvo_depth_head_wgrad_mfma) ----
 // dWh[t][c] = sum_p dpre[p] y[p + t - 1][c] = sum_q y[q][c] dpre[q + 1 - t], db = sum_p dpre[p]: a [16 c] x [9 t] product over the pixels.
-// The VALU kernel of csrc/misc.hip (thread = strided pixels, 48 accumulators, nine scattered d(pre) loads per pixel) runs at 26 + 5 us
+// The VALU kernel of csrc/heads.hip (thread = strided pixels, 48 accumulators, nine scattered d(pre) loads per pixel) runs at 26 + 5 us
 // for a 47 MB read at 16 frames -- on the weight-gradient streams, which are what ends the backward pass at 8 pairs.  Here a workgroup
 // walks 8 x 16 tiles: y tile (256 granules, one per thread) and the 10 x 18 d(pre) patch in LDS, wave w takes the 32 pixels of k-step
 // w: A = y^T by transposed reads, B[q][t] = dpre[q + 1 - t] rounded to bf16 (as y is), ONE MFMA per wave and tile; one partial row per
@@ -586,7 +586,7 @@ __global__ __launch_bounds__(NT, 4) void k_head_wgrad_mfma(const HeadWgradK a) {
 
 // ---- input gradient of a stride-2 3x3 layer w.r.t. TWO input channels, as fp32 planes, by MFMA (colvo_conv_dgrad_planes) ----
 // PoseNet's first layer (8 -> 16, stride 2): only the two depth channels of its input gradient are wanted, as planes for DepthNet's
-// backward pass; the kernel sits between the two networks' backward passes on the main chain.  The VALU form (csrc/misc.hip: thread =
+// backward pass; the kernel sits between the two networks' backward passes on the main chain.  The VALU form (csrc/dgrad_planes.hip: thread =
 // pixel pair, weights read from LDS once per FMA) took 13-24 us there for a 5 MB read and a 5 MB write.  Here a 2 x 2 block of input
 // pixels (2Y + py, 2X + px) is ONE row of a small product: it sees the four gradient pixels g[Y .. Y+1][X .. X+1] (16 channels each:
 // K = 64) and its 4 classes x 2 channels are 8 of the 16 output columns,
@@ -673,7 +673,7 @@ __global__ __launch_bounds__(NT) void k_dgrad_planes_s2_mfma(const PlanesK a) {
 
 using namespace colvo;
 
-// (called by colvo_conv_dgrad_planes, csrc/misc.hip, for the shapes this form covers)
+// (called by colvo_conv_dgrad_planes, csrc/dgrad_planes.hip, for the shapes this form covers)
 int colvo::launch_dgrad_planes_s2_mfma(const void* g, const float* w, int Cin, int c_begin, int B, int Hi, int Wi, int Ho, int Wo,
                                        float* dst, int accumulate, hipStream_t stream) {
     PlanesK k{};

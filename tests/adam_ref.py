@@ -1,7 +1,7 @@
 """The Adam update of include/colvo.h (a8) in float64, and how far a float32 evaluation of it may lie from that.
 
 Nothing here touches a GPU: tests/test_adam_ref_cpu.py holds this file to torch.optim.Adam in float64 and to a float32 emulation
-of the kernel's arithmetic; tests/test_adam_exact_gpu.py holds csrc/misc.hip's k_adam, k_adam_multi and k_adam_pack to it.
+of the kernel's arithmetic; tests/test_adam_exact_gpu.py holds csrc/adam.hip's k_adam, k_adam_multi and k_adam_pack to it.
 
 adam_step_f64  the operation the kernel is asked to do: float64 arithmetic on the float32 state and on the float32-ROUNDED
                hyperparameters that the C ABI carries (float lr, beta1, beta2, eps, grad_scale).
@@ -61,7 +61,7 @@ COEF_U = 22.5
 
 def coef_allowance_pow(t, b1, b2):
     """The coefficient allowance, in units of U and in place of COEF_U, for a kernel that computes the bias corrections as
-    1 - powf(b, t) -- what csrc/misc.hip's adam_coef does.  pow is held to the OpenCL limit of 16 ulp; 1 - b^t is an exact
+    1 - powf(b, t) -- what csrc/adam.hip's adam_coef does.  pow is held to the OpenCL limit of 16 ulp; 1 - b^t is an exact
     subtraction (Sterbenz, b^t >= 1/2) or absorbs it, so a relative error e of b^t becomes e b^t / (1 - b^t) of the correction:
     16 U b^t / (1 - b^t) per coefficient.  Plus the three roundings behind the corrections (lr / bc1; sqrt and 1 / of bc2), 3 U,
     which that figure does not count and which are all that is left once b^t has vanished.  At t = 1, b2 = 0.999 this is
@@ -110,7 +110,7 @@ def adam_bounds(ref, coef_u=COEF_U):
 
 
 def adam_emulate_f32(p, g, m, v, t, lr, b1, b2, eps, gscale, coef="expm1"):
-    """adam_one of csrc/misc.hip in NumPy float32, plain operation order, no fused multiply-add.  coef: 'expm1' -- the
+    """adam_one of csrc/adam.hip in NumPy float32, plain operation order, no fused multiply-add.  coef: 'expm1' -- the
     coefficients as -expm1f(t logf(b)); 'pow' -- as 1 - powf(b, t), the cancelling form.  -> (p', m', v', upd) float32."""
     f = np.float32
     p, g, m, v = (np.asarray(x, dtype=f) for x in (p, g, m, v))

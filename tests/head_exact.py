@@ -17,7 +17,7 @@ Exact bounds (sums of |terms| in quanta, below 2^22 = conv_exact.BOUND, so every
     head weight grad.   X_MAX * 2 * (non-zero d(pre)) -- conv_exact.bound_wgrad at conv_exact.dy_density(B * H * W)
     HEAD-form gradient  g = (y > 0) * (d(pre) (*) head weights) <= 9 * 2 * 8 = 144 quanta of 2^-3 * QH: exact in bf16 (8 bits)
     ... through the layer  its weight gradient sums X_MAX * 8 * 9 * 2 per non-zero d(pre) (head_g_density keeps it below the bound)
-Rounding bounds (U = 2^-24; the kernels' formulas are csrc/misc.hip k_depth_head_fwd* / head_dpre / k_depth_head_dgrad* /
+Rounding bounds (U = 2^-24; the kernels' formulas are csrc/heads.hip k_depth_head_fwd* / head_dpre / k_depth_head_dgrad* /
 k_pose_head_*, csrc/fwd16.hip's epilogue): see depth_rel_bound, dpre_bound, dgrad_bound, pose_ref, pose_bwd_bounds."""
 import math
 

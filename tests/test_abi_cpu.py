@@ -174,7 +174,7 @@ def test_product_package_does_not_import_the_oracle():
             if f.endswith((".py", ".hip", ".h")):
                 txt = open(os.path.join(dirpath, f)).read()
                 assert not re.search(r"^\s*(from|import)\s+oracle\b", txt, flags=re.M), f
-                assert "colvo_spec" not in txt or f in ("nn.py", "functional.py", "optim.py", "inference.py", "data.py", "frames.hip", "misc.hip",
+                assert "colvo_spec" not in txt or f in ("nn.py", "functional.py", "optim.py", "inference.py", "data.py", "frames.hip", "heads.hip", "adam.hip",
                                                        "conv.hip", "conv_rt.hip", "wgrad_rt.hip", "warp_loss.hip", "reconstruct.hip"), f   # docstring citations only
     for f in ("nn.py", "functional.py", "optim.py", "ops.py", "ddp.py", "synth.py", "_lib.py", "build.py"):
         txt = open(os.path.join(pkg, f)).read()

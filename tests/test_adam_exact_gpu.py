@@ -1,4 +1,4 @@
-"""-m gpu: every Adam entry point of csrc/misc.hip (k_adam, k_adam_multi, k_adam_pack<ES>) against float64, one step at a time.
+"""-m gpu: every Adam entry point of csrc/adam.hip (k_adam, k_adam_multi, k_adam_pack<ES>) against float64, one step at a time.
 
 Each case builds float32 state on the host, runs ONE kernel step and compares parameters and both moments with
 tests/adam_ref.adam_step_f64 of the same state under the derived per-element bounds of adam_bounds (a few float32 roundings; a
@@ -175,6 +175,34 @@ def test_k_adam_multi_three_steps():
             _hold("k_adam_multi", f"step {it + 1} of 3, n={n}", got, st, it + 1, gscale)
             nxt.append((got[0].copy(), st[1], got[1].copy(), got[2].copy()))
         cur = nxt
+
+
+def test_k_adam_multi_three_arenas_equals_three_single_launches():
+    """k_adam and k_adam_multi walk an arena with the same function: tail only, body and tail, body only -- bit for bit."""
+    from coivo_amd import ops
+    sizes, t, gscale = (3, 1029, 4), 3, 0.125
+    states = [_state(n, 80 + i, gscale) for i, n in enumerate(sizes)]
+    multi, single = [_Arena(*st) for st in states], [_Arena(*st) for st in states]
+    ops.adam_step_multi([tuple(a.views()) for a in multi], t, **_kw(gscale))
+    for a in single:
+        ops.adam_step_t(*a.views(), t, **_kw(gscale))
+    for n, a, b in zip(sizes, multi, single):
+        for name, x, y in zip("pmv", a.read(), b.read()):
+            assert np.array_equal(_bits(x), _bits(y)), f"n={n}: {name} of the three-arena launch differs from the single launch"
+
+
+def test_zero_multi_three_buffers_between_canaries():
+    """colvo_zero_multi shares k_adam_multi's arena table: 16, 4112 and 48 bytes, each between four canary words."""
+    from coivo_amd import _lib, ops
+    canary, words = 0x5A5A5A5A, [n // 4 for n in (16, 4112, 48)]
+    bufs = [torch.full((4 + n + 4,), canary, dtype=torch.int32, device=dev()) for n in words]
+    inner = [b[4:4 + n] for b, n in zip(bufs, words)]
+    assert len(inner) <= _lib.MAX_ARENAS and all(v.data_ptr() % 16 == 0 for v in inner)      # the one-launch path of ops.zero_multi
+    ops.zero_multi(inner)
+    for b, n in zip(bufs, words):
+        h = b.cpu().numpy()
+        assert not h[4:4 + n].any(), f"{4 * n} bytes: not zero"
+        assert (h[:4] == canary).all() and (h[4 + n:] == canary).all(), f"{4 * n} bytes: written outside the buffer"
 
 
 # ---------------------------------------------------------------- k_adam_pack ------------------------------------------- #

@@ -183,6 +183,33 @@ def test_depth_head_dpre_and_input_gradient(shape, dtype):
     _free()
 
 
+def _same_bits(a, b):
+    return a.dtype == b.dtype and torch.equal(a.contiguous().view(torch.uint8), b.contiguous().view(torch.uint8))
+
+
+@pytest.mark.parametrize("shape,dtype", [(s, dt) for s in [(2, 5, 7), (2, 13, 37)] for dt in DTYPES])
+def test_depth_head_bwd_equals_bwd_parts(shape, dtype):
+    """Both entry points make d(pre) and hand it to one input-gradient launch: with the incoming gradient as the two halves and no
+    raw parts, scratch and dx are the same bits -- granule form, generic form by its switch, and C = 8."""
+    from coivo_amd import ops
+    B, H, W = shape
+    d, g = dev(), _gen("bwd = parts", shape)
+    dd = HX.make_d_depth((B, 1, H, W), g, d)
+    for form, C, sw in (("granule", 16, {"head_dgrad_generic": 0}), ("generic (switch)", 16, {"head_dgrad_generic": 1}), ("C=8", 8, {})):
+        y, w, b = _head_inputs(B, H, W, C, g, d)
+        yk = y.to(dtype)
+        depth = torch.empty(B, 1, H, W, device=d)
+        ops.depth_head_fwd(yk, w, b, depth)
+        s1, s2 = torch.full((B * H * W,), 7.0, device=d), torch.full((B * H * W,), 9.0, device=d)
+        dx1, dx2 = torch.full_like(yk, 5.0), torch.full_like(yk, 3.0)
+        with tuned(**sw):
+            ops.depth_head_bwd(yk, w, depth, dd, s1, dx1, None, None)
+            ops.depth_head_bwd_parts(yk, w, depth, dd[:B // 2].contiguous(), dd[B // 2:].contiguous(), None, None, None, s2, dx2)
+        lab = f"{form} {_label(B, H, W, dtype)}"
+        assert _same_bits(s1, s2), f"d(pre) of depth_head_bwd and depth_head_bwd_parts differ: {lab}"
+        assert _same_bits(dx1, dx2), f"dx of depth_head_bwd and depth_head_bwd_parts differ: {lab}"
+
+
 # --------------------------------------------------------------------------------------------------------------------------- #
 # the head's weight gradient                                                                                                   #
 # --------------------------------------------------------------------------------------------------------------------------- #
@@ -433,6 +460,27 @@ def test_pose_head(shape, dtype):
     gs = 0.5 * 0.125
     for a, c in zip(results[(0.5, True)], results[(None, True)]):
         assert torch.equal(a.float(), (c.float() * gs)), "pose head: a power-of-two scale is not exact"
+
+
+@pytest.mark.parametrize("C,dtype", [(C, dt) for C in (8, 264) for dt in DTYPES])
+def test_pose_head_backward_forms_share_dx(C, dtype):
+    """The atomic and the ordered form run one per-channel function: dx bit-equal; dw, db of the ordered form repeatable.  C = 264
+    is the smallest multiple of 8 past one 256-thread pass: a second workgroup (ordered), a second trip of the channel loop (atomic)."""
+    from coivo_amd import ops
+    B, H, W = 3, 1, 5
+    d, g = dev(), _gen("pose forms", C)
+    xk = CX.make_source((B, H, W, C), g, d).to(dtype)
+    w = CX._ints(-CX.W_MAX, CX.W_MAX, (8, 1, C), g, d) * CX.QW
+    dout = CX._ints(-4, 4, (B, 8), g, d) * 2.0 ** -4
+    outs = []
+    for det in (False, True, True):
+        dx = torch.full_like(xk, 5.0)
+        dw, db = torch.zeros(8, 1, C, device=d), torch.zeros(8, device=d)
+        ops.pose_head_bwd(xk, w, dout[:, :6].contiguous(), dout[:, 6:7].contiguous(), dout[:, 7:8].contiguous(), dx, dw, db, None, None,
+                          deterministic=det)
+        outs.append((dx, dw, db))
+    assert _same_bits(outs[0][0], outs[1][0]), "pose head: dx of the atomic and of the ordered form differ"
+    assert all(_same_bits(a, c) for a, c in zip(outs[1], outs[2])), "ordered pose head: not repeatable"
 
 
 # --------------------------------------------------------------------------------------------------------------------------- #
