@@ -1,6 +1,7 @@
 // scene.h -- what the post-training kernels share about depth maps, cameras and frames, and the library's one
-// ordered scan (csrc/scan.hip).  The world-point arithmetic is NOT here: fuse.hip and consistency.hip each pin their own operation
-// order (no FMA contraction) against their own bit-exact replica under tests/.  reconstruct.hip's order is NOT pinned -- the compiler
+// ordered scan (csrc/scan.hip).  The world-point arithmetic is NOT here: the fusion (voxel_grid.h, shared by fuse.hip and normals.hip)
+// and consistency.hip each pin their own operation order (no FMA contraction) against their own bit-exact replica under tests/; the
+// renderers' camera point and footprint are in render_common.h.  reconstruct.hip's order is NOT pinned -- the compiler
 // may contract its products and sums --: its world point is held to the float64 replica tests/reconstruct_ref.py within a bound
 // derived from its operation count, 7 u (|r0 px| + |r1 py| + |r2 d| + |t|) with u = 2^-24.
 #pragma once

@@ -214,6 +214,68 @@ def fuse_point_cloud(depths: torch.Tensor, K: torch.Tensor, cam2world: torch.Ten
     return FusedCloud(points, out_colors, counts, voxels, origin, dims, vs, n_input, n_outside, n_bricks, n_voxels)
 
 
+class CloudNormals(NamedTuple):
+    normals: torch.Tensor           # [M,3] float32: unit normal of each row of the cloud in the world frame, facing the cameras; 0 without one
+    counts: torch.Tensor            # [M]   int32: samples that gave the row a normal
+    coherence: torch.Tensor         # [M]   float32: |sum of the samples' unit normals| / count: 1 where they agree, towards 0 as they do not
+    stats: torch.Tensor             # [4]   int32: samples kept, with a normal, ... in a row of the cloud, ... in no row
+
+
+def cloud_normals(fused: FusedCloud, depths: torch.Tensor, K: torch.Tensor, cam2world: torch.Tensor, *, stride: int = 1,
+                  max_depth: float = MAX_DEPTH, rel_edge: float = 0.05) -> CloudNormals:
+    """Surface normals of a fused cloud (contract: include/colvo.h colvo_cloud_normals; csrc/normals.hip).  Every
+    sample the fusion walked gets a finite-difference normal from its own depth map -- neighbours one pixel away, one-sided at the
+    image border and wherever the relative depth difference |d_b - d_c| / (d_b + d_c) reaches `rel_edge`, so that no normal is taken
+    across an occlusion edge --, faced to its camera, turned into the world frame and quantised to 2^-14.  The normals of the samples
+    of a voxel are summed as integers in the voxel's row; the row's normal is the sum's direction and its coherence the sum's length
+    per sample: 1 where all observations agree on the orientation, falling towards 0 at floaters, fold edges and bad poses.
+
+    `depths`, `K`, `cam2world`, `stride` and `max_depth` MUST be those given to fuse_point_cloud (the grid comes from `fused`):
+    a sample is matched to its row by the fusion's own voxel arithmetic, and samples of other depths, strides or poses end in the
+    unmatched count stats[3] -- as do the samples of voxels below the cloud's min_obs and those outside the grid.  `rel_edge = 0.05`
+    is a choice, not a tuned value.  Integer sums: identical bits on every call, stream and frame order, equal to the NumPy replica
+    tests/normals_ref.py.  No read-back and no host synchronisation."""
+    who = "cloud_normals"
+    if not isinstance(fused, FusedCloud):
+        raise ValueError(f"{who}: fused must be a FusedCloud")
+    if not isinstance(depths, torch.Tensor) or depths.dim() != 4:
+        raise ValueError(f"{who}: depths must be [N,1,H,W]")
+    if isinstance(stride, bool) or not isinstance(stride, int) or stride < 1:
+        raise ValueError(f"{who}: stride must be an int >= 1, got {stride!r}")
+    if not _finite_pos32(max_depth):
+        raise ValueError(f"{who}: max_depth must be finite and positive (as float32), got {max_depth!r}")
+    if not _finite_pos32(rel_edge):
+        raise ValueError(f"{who}: rel_edge must be finite and positive (as float32), got {rel_edge!r}")
+    N, _, H, W = depths.shape
+    origin = tuple(_f32(o) for o in fused.origin)
+    dims = tuple(int(d) for d in fused.dims)
+    vs = _f32(fused.voxel_size)
+    if len(origin) != 3 or len(dims) != 3 or any(d <= 0 or d % 8 for d in dims) or not (vs > 0.0 and math.isfinite(vs)):
+        raise ValueError(f"{who}: fused carries no valid grid (origin {origin}, dims {dims}, voxel_size {vs})")
+    lib = _lib.load()
+    if int(lib.colvo_fuse_plan_workspace_bytes(N, H, W, stride, *dims)) == 0:
+        raise ValueError(f"{who}: shape N={N} H={H} W={W} stride={stride} or grid {dims} beyond the kernels' limits")
+    depths = _chk(depths, "depths", (N, 1, H, W))
+    K = _chk(K, "K", (N, 3, 3))
+    cam2world = _chk(cam2world, "cam2world", (N, 4, 4))
+    m = int(fused.voxels.shape[0])
+    voxels = fused.voxels
+    if voxels.dtype != torch.int32 or tuple(voxels.shape) != (m, 3) or voxels.device != depths.device:
+        raise ValueError(f"{who}: fused.voxels must be [M,3] int32 on the device of depths")
+    voxels = voxels.contiguous()
+    dev = depths.device
+    scratch = torch.empty(int(lib.colvo_cloud_normals_scratch_bytes(m)), device=dev, dtype=torch.uint8)
+    normals = torch.empty(m, 3, device=dev, dtype=torch.float32)
+    counts = torch.empty(m, device=dev, dtype=torch.int32)
+    coherence = torch.empty(m, device=dev, dtype=torch.float32)
+    stats = torch.empty(4, device=dev, dtype=torch.int32)
+    _lib.check(lib.colvo_cloud_normals(_lib.ptr(depths), _lib.ptr(K), _lib.ptr(cam2world), N, H, W, stride, float(max_depth), *origin,
+                                       vs, *dims, _lib.ptr(voxels), m, float(rel_edge), _lib.ptr(scratch), _lib.ptr(normals),
+                                       _lib.ptr(counts), _lib.ptr(coherence), _lib.ptr(stats), _lib.stream_ptr()),
+               "colvo_cloud_normals")
+    return CloudNormals(normals, counts, coherence, stats)
+
+
 class Consistency(NamedTuple):
     """The policy of filter_depths; also what reconstruct_sequence takes.  The defaults are choices, not tuned values."""
     window: int = 2          # neighbours i +/- k*step, k = 1..window, that exist in [0, N)
@@ -469,11 +531,28 @@ def refine_trajectory(depths: torch.Tensor, frames: torch.Tensor, K: torch.Tenso
     return torch.stack(out), res
 
 
-class Render(NamedTuple):
-    """What reconstruct_sequence renders when asked: the fused cloud into every frame's own camera (render_fused).  The defaults
-    are choices, not tuned values."""
+class _RenderFields(NamedTuple):
     radius: Optional[float] = None   # world half-width of a splat; None: the fused cloud's voxel_size
     max_splat: int = 8               # largest half-width of a footprint in pixels
+
+
+class Render(_RenderFields):
+    """What reconstruct_sequence renders when asked: the fused cloud into every frame's own camera (render_fused).  The defaults
+    are choices, not tuned values.  Behind the two fields -- it still unpacks into two -- `surfels`: True has the cloud's normals
+    computed (cloud_normals) and the cloud drawn as oriented discs (render_surfels) instead of squares."""
+    surfels = False
+
+    def __new__(cls, radius=None, max_splat=8, surfels=False):
+        self = super().__new__(cls, radius, max_splat)
+        self.surfels = surfels
+        return self
+
+    def _replace(self, **kw):
+        surfels = kw.pop("surfels", self.surfels)
+        return type(self)(*super()._replace(**kw), surfels=surfels)
+
+    def __repr__(self):
+        return f"Render(radius={self.radius!r}, max_splat={self.max_splat!r}, surfels={self.surfels!r})"
 
 
 class RenderedViews(NamedTuple):
@@ -545,41 +624,118 @@ def render_cloud(points: torch.Tensor, K: torch.Tensor, cam2world: torch.Tensor,
     return RenderedViews(depth, index, out_colors, stats)
 
 
+class SurfelViews(NamedTuple):
+    depth: torch.Tensor              # [N,1,H,W] float32: camera-z where the pixel's ray meets the nearest disc, +inf where nothing landed
+    index: torch.Tensor              # [N,1,H,W] int32: that point's row in the cloud, -1 where empty
+    colors: Optional[torch.Tensor]   # [N,3,H,W] float32: its colour, 0 where empty (None without colours)
+    normal: Optional[torch.Tensor]   # [N,3,H,W] float32: its normal in the camera frame, 0 where empty or without one (None unless asked)
+    stats: torch.Tensor              # [N,6] int32: points in front, drawn, in front and clipped, covered pixels, culled, flat
+
+
+def render_surfels(points: torch.Tensor, normals: torch.Tensor, K: torch.Tensor, cam2world: torch.Tensor, H: int, W: int, *,
+                   radius: float, colors: Optional[torch.Tensor] = None, max_splat: int = 8, max_depth: float = MAX_DEPTH,
+                   want_normals: bool = False) -> SurfelViews:
+    """render_cloud with normals [M,3] in the world frame (contract: include/colvo.h colvo_render_surfels, DESIGN.md §3.6k;
+    csrc/surfels.hip): a point is a disc of world radius `radius` perpendicular to its normal.  Each pixel of the point's footprint --
+    the same rectangle as render_cloud's -- whose ray meets the disc's plane within `radius` of the point offers the depth of that
+    meeting; the nearest pixel, when not hit, offers the point's own depth, so a point in front still lands somewhere.  The rendered
+    depth of a wall seen at a grazing angle then lies on the wall instead of being biased towards the camera by radius x slope.  A
+    point whose normal faces away from the camera is culled; a point whose normal is zero (or NaN) is drawn as render_cloud draws it
+    and counted as flat.  want_normals: also the winner's camera-frame normal per pixel, to shade a preview with.  Pinned float32
+    arithmetic, an integer minimum and integer sums: identical bits on every call and stream, equal to tests/surfel_ref.py.  A
+    pixel only the nearest-pixel fallback reaches keeps the square's bias.  No read-back and no host synchronisation."""
+    who = "render_surfels"
+    _check_render(who, radius, max_splat, max_depth)
+    for name, val in (("H", H), ("W", W)):
+        if isinstance(val, bool) or not isinstance(val, int) or val < 1:
+            raise ValueError(f"{who}: {name} must be a positive int, got {val!r}")
+    if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError(f"{who}: points must be [M,3]")
+    if not isinstance(normals, torch.Tensor) or tuple(normals.shape) != tuple(points.shape):
+        raise ValueError(f"{who}: normals must have the shape of points")
+    if not isinstance(cam2world, torch.Tensor) or cam2world.dim() != 3:
+        raise ValueError(f"{who}: cam2world must be [N,4,4]")
+    M, N = points.shape[0], cam2world.shape[0]
+    if not 1 <= N <= 65535 or H * W >= 1 << 30 or N * H * W >= 1 << 31 or M >= 1 << 31:
+        raise ValueError(f"{who}: M={M} N={N} H={H} W={W} beyond the kernels' limits (M < 2^31, 1 <= N <= 65535, H*W < 2^30, "
+                         "N*H*W < 2^31)")
+    points = _chk(points, "points", (M, 3))
+    normals = _chk(normals, "normals", (M, 3))
+    cam2world = _chk(cam2world, "cam2world", (N, 4, 4))
+    if isinstance(K, torch.Tensor) and K.dim() == 2:
+        K = K.unsqueeze(0).expand(N, 3, 3)
+    K = _chk(K, "K", (N, 3, 3))
+    if colors is not None:
+        colors = _chk(colors, "colors", (M, 3))
+    lib = _lib.load()
+    dev = points.device
+    scratch = torch.empty(int(lib.colvo_render_scratch_bytes(N, H, W)), device=dev, dtype=torch.uint8)
+    depth = torch.empty(N, 1, H, W, device=dev, dtype=torch.float32)
+    index = torch.empty(N, 1, H, W, device=dev, dtype=torch.int32)
+    out_colors = torch.empty(N, 3, H, W, device=dev, dtype=torch.float32) if colors is not None else None
+    out_normal = torch.empty(N, 3, H, W, device=dev, dtype=torch.float32) if want_normals else None
+    stats = torch.empty(N, 6, device=dev, dtype=torch.int32)
+    _lib.check(lib.colvo_render_surfels(_lib.ptr(points), _lib.ptr(normals), _lib.ptr(colors), M, _lib.ptr(K), _lib.ptr(cam2world), N,
+                                        H, W, float(radius), max_splat, float(max_depth), _lib.ptr(scratch), _lib.ptr(depth),
+                                        _lib.ptr(index), _lib.ptr(out_colors), _lib.ptr(out_normal), _lib.ptr(stats),
+                                        _lib.stream_ptr()), "colvo_render_surfels")
+    return SurfelViews(depth, index, out_colors, out_normal, stats)
+
+
 def render_fused(fused: FusedCloud, K: torch.Tensor, cam2world: torch.Tensor, H: int, W: int, *, radius: Optional[float] = None,
-                 max_splat: int = 8, max_depth: float = MAX_DEPTH) -> RenderedViews:
+                 max_splat: int = 8, max_depth: float = MAX_DEPTH, normals=None, want_normals: bool = False):
     """render_cloud of a FusedCloud's points and colours.  radius defaults to fused.voxel_size: the mean positions of neighbouring
     voxels are at most two voxels apart per axis, so squares of half-width one voxel close a fronto-parallel wall.  That default
-    is a choice, not a tuned value."""
+    is a choice, not a tuned value.  With `normals` -- the CloudNormals of cloud_normals(fused, ...) or an [M,3] tensor -- it is
+    render_surfels of the same and returns SurfelViews (want_normals as there); with None it returns RenderedViews."""
     if not isinstance(fused, FusedCloud):
         raise ValueError("render_fused: fused must be a FusedCloud")
-    return render_cloud(fused.points, K, cam2world, H, W, radius=fused.voxel_size if radius is None else radius,
-                        colors=fused.colors, max_splat=max_splat, max_depth=max_depth)
+    radius = fused.voxel_size if radius is None else radius
+    if normals is None:
+        if want_normals:
+            raise ValueError("render_fused: want_normals needs normals")
+        return render_cloud(fused.points, K, cam2world, H, W, radius=radius, colors=fused.colors, max_splat=max_splat,
+                            max_depth=max_depth)
+    if isinstance(normals, CloudNormals):
+        normals = normals.normals
+    return render_surfels(fused.points, normals, K, cam2world, H, W, radius=radius, colors=fused.colors, max_splat=max_splat,
+                          max_depth=max_depth, want_normals=want_normals)
 
 
-def write_ply(path, points: torch.Tensor, colors: Optional[torch.Tensor] = None) -> None:
-    """Binary little-endian PLY: `float x y z` per vertex and, with colours [M,3] in [0,1], `uchar red green blue`
-    (rint(c * 255), clamped).  Host code; one device -> host copy."""
+def write_ply(path, points: torch.Tensor, colors: Optional[torch.Tensor] = None, normals: Optional[torch.Tensor] = None) -> None:
+    """Binary little-endian PLY: `float x y z` per vertex, with normals [M,3] `float nx ny nz` behind them (viewers shade by them)
+    and, with colours [M,3] in [0,1], `uchar red green blue` (rint(c * 255), clamped).  Without normals the bytes are what they were
+    before normals existed.  Host code; one device -> host copy."""
     import numpy as np
     if points.dim() != 2 or points.shape[1] != 3:
         raise ValueError("write_ply: points must be [M,3]")
     if colors is not None and tuple(colors.shape) != tuple(points.shape):
         raise ValueError("write_ply: colors must have the shape of points")
-    both = points.detach().to(torch.float32) if colors is None else torch.cat(
-        [points.detach().to(torch.float32), colors.detach().to(points.device, torch.float32)], dim=1)
-    host = both.cpu().numpy()
+    if normals is not None and (not isinstance(normals, torch.Tensor) or tuple(normals.shape) != tuple(points.shape)):
+        raise ValueError("write_ply: normals must be a tensor of the shape of points")
+    parts = [points.detach().to(torch.float32)]
+    if normals is not None:
+        parts.append(normals.detach().to(points.device, torch.float32))
+    if colors is not None:
+        parts.append(colors.detach().to(points.device, torch.float32))
+    host = (parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)).cpu().numpy()
     m = host.shape[0]
     fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
     header = ["ply", "format binary_little_endian 1.0", f"element vertex {m}", "property float x", "property float y",
               "property float z"]
+    if normals is not None:
+        fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+        header += ["property float nx", "property float ny", "property float nz"]
     if colors is not None:
         fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
         header += ["property uchar red", "property uchar green", "property uchar blue"]
     header.append("end_header")
     rows = np.empty(m, dtype=np.dtype(fields))
-    for a, name in enumerate("xyz"):
+    n_float = 3 if normals is None else 6
+    for a, name in enumerate(("x", "y", "z", "nx", "ny", "nz")[:n_float]):
         rows[name] = host[:, a]
     if colors is not None:
-        q = np.clip(np.rint(np.nan_to_num(host[:, 3:6], nan=0.0) * 255.0), 0, 255).astype(np.uint8)
+        q = np.clip(np.rint(np.nan_to_num(host[:, n_float:n_float + 3], nan=0.0) * 255.0), 0, 255).astype(np.uint8)
         for k, name in enumerate(("red", "green", "blue")):
             rows[name] = q[:, k]
     with open(path, "wb") as f:
@@ -601,19 +757,22 @@ class Reconstruction(_ReconstructionFields):
     ConsistencyResult whose depths points, fused and polyps were computed from (`depths` stays the raw network output), else
     None; and `refinement`: with a Refinement policy the RefinementResult of the consecutive pairs -- `cam2world` is then the
     refined trajectory, `rel_poses` stays the raw network output -- else None; and `rendered`: with a Render policy the
-    RenderedViews of `fused` in every frame's own camera along `cam2world`, else None."""
+    RenderedViews of `fused` in every frame's own camera along `cam2world`, else None; and `normals`: with Render(surfels=True) the
+    CloudNormals of `fused` (`rendered` is then the SurfelViews drawn with them), else None."""
     polyps = None               # Optional[PolypLocalization]
     consistency = None          # Optional[ConsistencyResult]
     refinement = None           # Optional[RefinementResult]
-    rendered = None             # Optional[RenderedViews]
+    rendered = None             # Optional[RenderedViews], or SurfelViews with Render(surfels=True)
+    normals = None              # Optional[CloudNormals]
 
     def __new__(cls, depths, rel_poses, cam2world, points, fused=None, polyps=None, consistency=None, refinement=None,
-                rendered=None):
+                rendered=None, normals=None):
         self = super().__new__(cls, depths, rel_poses, cam2world, points, fused)
         self.polyps = polyps
         self.consistency = consistency
         self.refinement = refinement
         self.rendered = rendered
+        self.normals = normals
         return self
 
     def _replace(self, **kw):
@@ -621,7 +780,9 @@ class Reconstruction(_ReconstructionFields):
         consistency = kw.pop("consistency", self.consistency)
         refinement = kw.pop("refinement", self.refinement)
         rendered = kw.pop("rendered", self.rendered)
-        return type(self)(*super()._replace(**kw), polyps=polyps, consistency=consistency, refinement=refinement, rendered=rendered)
+        normals = kw.pop("normals", self.normals)
+        return type(self)(*super()._replace(**kw), polyps=polyps, consistency=consistency, refinement=refinement, rendered=rendered,
+                          normals=normals)
 
 
 @torch.no_grad()
@@ -656,7 +817,9 @@ def reconstruct_sequence(depth_net, pose_net, frames: torch.Tensor, K: torch.Ten
     refined trajectory is `cam2world` and is what the filter, the stitching, the fusion and the localisation use; `rel_poses` stays
     the raw network output and the RefinementResult is `refinement` (else None).  With a Render policy (needs voxel_size) the fused
     cloud is drawn back into every frame's own camera along the trajectory the call used (render_fused: same K, max_depth and
-    image size; radius None is the voxel size) and the RenderedViews is `rendered` (else None)."""
+    image size; radius None is the voxel size) and the RenderedViews is `rendered` (else None).  With Render(surfels=True) the cloud's
+    normals are first computed from the depths, stride, max_depth and trajectory it was fused with (cloud_normals; `normals`, else
+    None) and the cloud is drawn as oriented discs: `rendered` is then a SurfelViews."""
     n = frames.shape[0]
     if n < 2:
         raise ValueError("reconstruct_sequence: need at least two frames")
@@ -669,10 +832,12 @@ def reconstruct_sequence(depth_net, pose_net, frames: torch.Tensor, K: torch.Ten
         refine = Refinement(*refine)
         _check_refinement("reconstruct_sequence", refine, max_depth)
     if render is not None:
-        render = Render(*render)
+        render = Render(*render, surfels=getattr(render, "surfels", False))
         if voxel_size is None:
             raise ValueError("reconstruct_sequence: render needs voxel_size (it draws the fused cloud)")
         _check_render("reconstruct_sequence", voxel_size if render.radius is None else render.radius, render.max_splat, max_depth)
+        if not isinstance(render.surfels, bool):
+            raise ValueError(f"reconstruct_sequence: render.surfels must be a bool, got {render.surfels!r}")
     if K.dim() == 2:
         K = K.unsqueeze(0).expand(n, 3, 3)
     K = K.to(frames.device, torch.float32).contiguous()
@@ -696,8 +861,10 @@ def reconstruct_sequence(depth_net, pose_net, frames: torch.Tensor, K: torch.Ten
     if labels is not None:
         from . import localize                       # (localize imports this module)
         polyps = localize.localize_polyps(depths, labels, K, traj32, num_labels=num_labels, stride=1, max_depth=max_depth)
-    rendered = None
+    rendered = normals = None
     if render is not None:
+        if render.surfels:
+            normals = cloud_normals(fused, depths, K, traj32, stride=stride, max_depth=max_depth)
         rendered = render_fused(fused, K, traj32, int(frames.shape[2]), int(frames.shape[3]), radius=render.radius,
-                                max_splat=render.max_splat, max_depth=max_depth)
-    return Reconstruction(raw, rel, traj, cloud, fused, polyps, checked, refined, rendered)
+                                max_splat=render.max_splat, max_depth=max_depth, normals=normals)
+    return Reconstruction(raw, rel, traj, cloud, fused, polyps, checked, refined, rendered, normals)

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define COLVO_ABI_VERSION 20
+#define COLVO_ABI_VERSION 21
 
 typedef void* colvo_stream_t; /* hipStream_t */
 
@@ -489,6 +489,43 @@ int colvo_fuse_write(const void* workspace, const void* pool, int n_bricks, int 
                      float voxel_size, int nx, int ny, int nz, const void* extract_ws, int n_rows, float* points, float* colors,
                      int32_t* counts, int32_t* voxels, colvo_stream_t stream);
 
+/* Surface normals of a fused cloud: a finite-difference normal per sample of the depth maps, summed per voxel as
+ * integers in the row the voxel has in the cloud.  depths, K, cam2world, N, H, W, stride, max_depth and the grid are the ones the
+ * cloud was fused with (else samples end in stats[3]); voxels [M,3] int32 are the cloud's voxel indices in its ascending (brick,
+ * voxel in brick) order; rel_edge is the largest relative depth difference a finite difference may span.  Float32, every operation
+ * individually rounded in the order written (no FMA contraction), correctly rounded divisions and square roots; float32 denormals
+ * are kept (the library is built with HIP's default float_denorm_mode_32 = 3), as NumPy keeps them.  cam2world's rotation block r is
+ * taken as orthonormal and finite.  Per walked sample c = (u, v) of frame b with 0 < d_c < max_depth (the fusion's walk and rule):
+ *   points     for c and its four neighbours, ONE pixel away in the full-resolution map whatever the stride:
+ *              P = (((u - cx) / fx) * d, ((v - cy) / fy) * d, d).
+ *   usable     a neighbour b is usable iff it lies inside the image, 0 < d_b < max_depth and |d_b - d_c| < rel_edge * (d_b + d_c).
+ *   tangents   along u: P(u+1) - P(u-1) if both neighbours are usable, P(u+1) - P(c) if only the right one, P(c) - P(u-1) if only
+ *              the left one, else none; along v likewise.  No tangent on either axis: no normal.
+ *   normal     n = t_u x t_v, each component two products and one subtraction (n_x = t_u.y * t_v.z - t_u.z * t_v.y, cyclic); negated
+ *              iff (n_x * P_x + n_y * P_y) + n_z * P_z > 0 with P = P(c), so that it faces the camera.
+ *   length     L = sqrtf((n_x^2 + n_y^2) + n_z^2); the sample has a normal iff L > 0 and L < inf (NaN falls out).
+ *   world      e = n / L;  N_a = (r_a0 * e_x + r_a1 * e_y) + r_a2 * e_z;  q_a = (int) rintf(N_a * 16384.0f).
+ *   voxel      the fusion's routine on (u, v, d_c): brick and local index; the row is the one whose key brick * 512 + local equals
+ *              the sample's, found by binary search among the rows' keys (computed from `voxels`).
+ *   sums       per row four 64-bit integers: sum q_x, sum q_y, sum q_z, n (native integer atomics: bit-identical between calls,
+ *              streams and frame orders).  With n < 2^24 no sum exceeds 2^39.
+ * Write-out in float64, every operation individually rounded: len = sqrt((sx * sx + sy * sy) + sz * sz); normals[m][a] =
+ * float(s_a / len); coherence[m] = float(len / (16384.0 * n)) -- 1 where all observations agree on the orientation, towards 0 as they
+ * disagree --; counts[m] = n; with n = 0 or len = 0 the normal and the coherence are 0.
+ * stats (device int32[4]): samples walked and kept; of those, samples with a normal; of those, samples whose voxel is a row of the
+ * cloud; and samples whose voxel is not (below the cloud's min_obs, or outside the grid).
+ * `voxels` that are not sorted or not the cloud's: unspecified values, but no index leaves the arrays.
+ * scratch: colvo_cloud_normals_scratch_bytes(M) bytes, 16-byte aligned (32 bytes of sums and an 8-byte key per row, 16 KiB of counter
+ * lines), written by the call; 0 for M < 0.  No read-back and no host synchronisation.
+ * Limits: those of colvo_fuse_* (N <= 65535, H*W < 2^30, fewer than 2^31 samples, fewer than 2^28 bricks in the grid, voxel_size
+ * finite and positive), 0 <= M < 2^31 (voxels and the three outputs may be NULL when M = 0), max_depth and rel_edge finite and
+ * positive; refused before any HIP call with a message that starts `colvo_cloud_normals:`. */
+size_t colvo_cloud_normals_scratch_bytes(int M);
+int colvo_cloud_normals(const float* depths, const float* K, const float* cam2world, int N, int H, int W, int stride, float max_depth,
+                        float ox, float oy, float oz, float voxel_size, int nx, int ny, int nz, const int32_t* voxels, int M,
+                        float rel_edge, void* scratch, float* normals, int32_t* counts, float* coherence, int32_t* stats,
+                        colvo_stream_t stream);
+
 /* Polyp localisation: labelled pixels + depth maps + trajectory -> where each polyp lies, in the camera frame of
  * every frame that shows it and in the world frame, and how large it is.  labels [N,1,H,W] uint8: 0 background, 1..num_labels a
  * polyp id (the same polyp in every frame: association is the detector's or tracker's job), anything above num_labels is ignored
@@ -595,6 +632,28 @@ size_t colvo_render_scratch_bytes(int N, int H, int W);
 int colvo_render_cloud(const float* points, const float* colors, int M, const float* K, const float* cam2world, int N, int H, int W,
                        float radius, int max_splat, float max_depth, void* scratch, float* out_depth, int32_t* out_index,
                        float* out_colors, int32_t* out_stats, colvo_stream_t stream);
+
+/* Point cloud with normals into camera views: z-buffered oriented discs.  colvo_render_cloud's contract holds --
+ * camera, front, centre, clipped, on screen, footprint, the minimum key, outputs, scratch and limits --, with one more input, normals
+ * [M,3] float32 in the world frame (any length), and the following differences.  Per frame n and point i (X, N):
+ *   has a normal   iff (N_0^2 + N_1^2) + N_2^2 > 0 (NaN fails).  A point without a normal is drawn exactly as colvo_render_cloud draws
+ *                  it, a square with one depth, and is counted as flat when it is in front.
+ *   camera normal  m_a = (r_0a * N_0 + r_1a * N_1) + r_2a * N_2;  num = (m_x * P_x + m_y * P_y) + m_z * P_z.  A point in front that has
+ *                  a normal and num >= 0 faces away from the camera: it draws nothing and is counted as culled.
+ *   per pixel      (u, v) of the footprint (the same rectangle) of a point that has a normal and is not culled:
+ *                  dx = (float(u) - cx) / fx, dy = (float(v) - cy) / fy;  den = (m_x * dx + m_y * dy) + m_z;  z = num / den;
+ *                  e_x = dx * z - P_x, e_y = dy * z - P_y, e_z = z - P_z;  hit iff den < 0, z > 1e-3f, z < max_depth and
+ *                  (e_x^2 + e_y^2) + e_z^2 <= radius * radius, all four evaluated (NaN and infinities fail).  A hit offers the key
+ *                  (bits(z) << 32) | i.  The nearest pixel (uc, vc), when it lies inside the image and is not hit, offers
+ *                  (bits(P_z) << 32) | i: a point in front still lands on at least its nearest pixel.  Any other pixel offers nothing.
+ *                  With all normals zero the outputs equal colvo_render_cloud's; with radius = 0 they do unless a point is culled.
+ *   outputs        out_depth, out_index, out_colors as there;  out_normal [N,3,H,W] float32 or NULL: the winner's camera normal m,
+ *                  0 where the pixel is empty or the winner has no normal;  out_stats [N,6] int32 per frame: points in front, points
+ *                  drawn (offered at least one key), points in front and clipped, covered pixels, culled, flat.
+ * scratch: colvo_render_scratch_bytes(N, H, W) bytes.  Refusals start `colvo_render_surfels:`; normals may be NULL when M = 0. */
+int colvo_render_surfels(const float* points, const float* normals, const float* colors, int M, const float* K, const float* cam2world,
+                         int N, int H, int W, float radius, int max_splat, float max_depth, void* scratch, float* out_depth,
+                         int32_t* out_index, float* out_colors, float* out_normal, int32_t* out_stats, colvo_stream_t stream);
 
 /* Pose refinement by dense depth and intensity alignment: a few Gauss-Newton steps per edge on the per-pixel geometric
  * and photometric residuals of the two frames it connects, starting from the pose given.  depths [N,1,H,W], frames [N,3,H,W], K [N,3,3]
