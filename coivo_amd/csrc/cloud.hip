@@ -15,44 +15,21 @@
 // Every hand-off between phases is a kernel boundary.  The minimum of a set does not depend on the order it is taken in and every
 // sum is an unsigned integer, so a call's bits do not depend on scheduling or on the stream.  The arithmetic that decides a distance,
 // a cell or a quantum is pinned: float32, every operation individually rounded -- contraction is off for this whole file.
-#include <float.h>
-
 #include "scene.h"
 
 #pragma clang fp contract(off)
 
+#include "cloud_grid.h"
+
 namespace colvo {
 namespace {
 
+using namespace cloud_grid;                              // Header, Grid, load_grid, grid_coord, nearest_key, the workspace's layout
+
 constexpr int NT = 256;
-constexpr int AXIS_LIMIT = 128;                          // cells per axis, at most
-constexpr float AXIS_DIV = 126.0f;                       // edge >= extent / AXIS_DIV: floor(126 * (1 + 3 * 2^-24)) + 1 <= 128
-constexpr int MAX_CELLS = AXIS_LIMIT * AXIS_LIMIT * AXIS_LIMIT;
-constexpr float EDGE_MARGIN = 1.0f + 1.0f / 1024.0f;     // edge >= max_dist * (1 + 2^-10): DESIGN.md §3.6h
-constexpr int SCAN_ENTRIES = MAX_CELLS + 1;              // the cells and one entry behind them: its prefix is the record count
-constexpr int COUNTER_LINES = 256;                       // the query's statistics: this many rows of N_STATS 64-bit words,
-constexpr int COUNTER_PITCH = 16;                        // ... 128 bytes apart (one hot address measured 41 x slower: §3.6c (c))
 constexpr int N_STATS = 12;
 constexpr int MAX_THRESHOLDS = 8;
 constexpr int BOUNDS_MAX_BLOCKS = 1024;
-constexpr int MAX_POINTS = 1 << 30;
-
-struct Header {                            // the head of the workspace: written by the build, read by the query
-    uint32_t key[6];                       // ordered keys: ~min x, y, z and max x, y, z (all of them gathered with atomicMax)
-    uint32_t n_valid;                      // valid reference points
-    uint32_t single;                       // the box has no finite grid: one cell, searched whole
-    float o[3];                            // the box's lower corner
-    float inv;                             // float32(1) / edge
-    int n[3];                              // cells per axis
-    int cells;                             // 0: no valid reference point
-};
-static_assert(sizeof(Header) == 64, "Header is 64 B");
-
-struct Grid {                              // the header's geometry, wave-uniform
-    float o[3], inv;
-    int n[3], cells;
-    bool single;
-};
 
 struct Thresholds {
     float t2[MAX_THRESHOLDS];              // float32(tau) * float32(tau)
@@ -62,29 +39,6 @@ struct Thresholds {
 struct Sim3 {
     float r[9], t[3], s;
 };
-
-__device__ __forceinline__ bool finite_f(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
-
-__device__ __forceinline__ Grid load_grid(const Header* __restrict__ h) {
-    Grid G;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        G.o[a] = uniform_f(h->o[a]);
-        G.n[a] = __builtin_amdgcn_readfirstlane(h->n[a]);
-    }
-    G.inv = uniform_f(h->inv);
-    G.cells = __builtin_amdgcn_readfirstlane(h->cells);
-    G.single = __builtin_amdgcn_readfirstlane((int)h->single) != 0;
-    // whatever the header holds, no index below leaves the cell arrays
-    G.cells = min(max(G.cells, 0), MAX_CELLS);
-#pragma unroll
-    for (int a = 0; a < 3; ++a) G.n[a] = min(max(G.n[a], 1), AXIS_LIMIT);
-    if ((long long)G.n[0] * G.n[1] * G.n[2] > (long long)G.cells) G.cells = 0;
-    return G;
-}
-
-// The pinned cell coordinate of one axis: ((x - o) * inv), floored by the callers.
-__device__ __forceinline__ float grid_coord(const Grid& G, int a, float x) { return (x - G.o[a]) * G.inv; }
 
 // cell of a VALID reference point; the clamp never acts on a point of the box the grid was made from (the dims come from the same
 // routine, which is monotone) and turns the NaN of an unbounded box (G.single: inf * 0) into cell 0
@@ -209,40 +163,8 @@ __global__ __launch_bounds__(NT) void k_cloud_query(const float* __restrict__ Q,
         for (int a = 0; a < 3; ++a) q[a] = Q[i * 3 + a];
     }
     const bool valid = in && finite_f(q[0]) && finite_f(q[1]) && finite_f(q[2]);
-    unsigned long long best = ((unsigned long long)__float_as_uint(md2) << 32) | 0xffffffffull;
     unsigned long long examined = 0ull;
-    bool walk = valid && G.cells > 0;
-    int c[3] = {0, 0, 0};
-    if (walk && !G.single) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const float g = grid_coord(G, a, q[a]);
-            // more than a cell outside the box: nothing within reach (and no integer is made of a coordinate out of range)
-            walk = walk && g >= -1.0f && g < (float)G.n[a] + 1.0f;
-            c[a] = walk ? (int)floorf(g) : 0;                   // -1 .. n
-        }
-    }
-    if (walk) {
-        const int x0 = max(c[0] - 1, 0), x1 = min(c[0] + 1, G.n[0] - 1);
-        const int y0 = max(c[1] - 1, 0), y1 = min(c[1] + 1, G.n[1] - 1);
-        const int z0 = max(c[2] - 1, 0), z1 = min(c[2] + 1, G.n[2] - 1);
-        if (x0 <= x1) {
-            for (int z = z0; z <= z1; ++z) {
-                for (int y = y0; y <= y1; ++y) {
-                    const int base = (z * G.n[1] + y) * G.n[0];          // < cells <= MAX_CELLS
-                    const int b = max(start[base + x0], 0), e = min(start[base + x1 + 1], M);
-                    for (int j = b; j < e; ++j) {
-                        const float4 r = rec[j];
-                        const float dx = q[0] - r.x, dy = q[1] - r.y, dz = q[2] - r.z;
-                        const float d2 = ((dx * dx + dy * dy) + dz * dz);
-                        const unsigned long long key = ((unsigned long long)__float_as_uint(d2) << 32) | (uint32_t)__float_as_int(r.w);
-                        if (d2 < md2 && key < best) best = key;
-                    }
-                    if (e > b) examined += (unsigned long long)(e - b);
-                }
-            }
-        }
-    }
+    const unsigned long long best = nearest_key(G, q, valid, start, rec, M, md2, examined);
     const float d2v = __uint_as_float((uint32_t)(best >> 32));
     const float dv = sqrtf(d2v);                             // correctly rounded (the build keeps HIP's default for sqrt and division)
     const int idx = (int)(uint32_t)best;
@@ -282,44 +204,11 @@ __global__ __launch_bounds__(NT) void k_cloud_transform(const float* P, int N, S
     for (int a = 0; a < 3; ++a) out[i * 3 + a] = o[a];
 }
 
-// ---- host side --------------------------------------------------------------------------------------------------------------- //
-struct Ws {                                // header, counter lines, cell starts, chunk sums, records [M], ranks [M]
-    Header* header;
-    unsigned long long* counters;
-    int32_t* cells;
-    int32_t* sums;
-    float4* rec;
-    int32_t* rank;
-    size_t bytes;
-};
-
-Ws layout(void* base, int M) {
-    Carver c(base);
-    Ws w;
-    w.header = c.take<Header>(1, 256);
-    w.counters = c.take<unsigned long long>((size_t)COUNTER_LINES * COUNTER_PITCH);
-    w.cells = c.take<int32_t>(SCAN_ENTRIES);
-    w.sums = c.take<int32_t>(scan_chunks(SCAN_ENTRIES));
-    w.rec = c.take<float4>(M);
-    w.rank = c.take<int32_t>(M);
-    w.bytes = c.bytes();
-    return w;
-}
-
-bool good_sizes(int N, int M) { return N >= 0 && M >= 0 && N < MAX_POINTS && M < MAX_POINTS; }
-
-// max_dist finite and positive with a finite, normal square; md2 and the quantum scale, each rounded once
-bool good_max_dist(float max_dist, float& md2, float& scale) {
-    if (!(max_dist > 0.0f) || !(max_dist < __builtin_inff())) return false;
-    md2 = max_dist * max_dist;
-    scale = 1048576.0f / max_dist;
-    return md2 >= FLT_MIN && md2 < __builtin_inff() && scale < __builtin_inff();
-}
-
 }  // namespace
 }  // namespace colvo
 
 using namespace colvo;
+using namespace colvo::cloud_grid;
 
 extern "C" size_t colvo_cloud_workspace_bytes(int N, int M) {
     if (!good_sizes(N, M)) return 0;

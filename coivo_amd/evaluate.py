@@ -48,9 +48,19 @@ Point clouds (csrc/cloud.hip; these definitions are the contra
   measures  cloud_metrics(pred, gt): accuracy = mean truncated distance pred -> gt, completeness = the same gt -> pred, chamfer
             their mean; per threshold precision = the fraction of the valid pred points with dist2 < tau^2, recall = that of the
             valid gt points, fscore = 2 p r / (p + r), 0 when both are 0.  A side without a valid point gives NaN for the
-            measures that divide by its count.  No ICP and no surface meshing: the clouds are compared as given (after the
-            optional Sim(3) of align_trajectory).
+            measures that divide by its count.  No surface meshing: the clouds are compared as given, after the optional
+            Sim(3) of align_trajectory and, with a Registration policy, its refinement by register_clouds (below).
   limits    N, M < 2^30; max_dist finite and positive with a finite positive float32 square; at most 8 thresholds.
+
+Registration (csrc/register.hip; the contract is include/colvo.h colvo_register_*)
+  register_clouds(source, target)  a few Gauss-Newton steps of point-to-plane ICP (metric "plane", the default; "point" is point to
+            point, which crawls on a tube: the points slide along the wall) that refine a Sim(3) ("sim3") or SE(3) ("se3") moving
+            source onto target, x' = s R x + t.  Every iteration is one nearest-neighbour pass of the transformed source over the
+            target's index -- nearest_neighbors' own walk, rule for rule -- and 37 float64 sums in a fixed order; the 6x6 / 7x7 step is
+            solved on the device.  No read-back and no host synchronisation; identical bits on every call and stream.
+  status    REGISTER_OK; REGISTER_TOO_FEW (fewer than min_pairs pairs used), REGISTER_NOT_PD (a surface with a free motion: an exact
+            cylinder) and REGISTER_REVERTED (the final truncated cost per valid point is above the initial one) return the initial
+            state to the bit.  There is no convergence test and no early exit.
 """
 from __future__ import annotations
 
@@ -252,7 +262,7 @@ class CloudNN(NamedTuple):
     thresholds: Tuple[float, ...]   # as float32
 
 
-class CloudMetrics(NamedTuple):
+class _CloudMetricsFields(NamedTuple):
     accuracy: float             # mean truncated distance pred -> gt
     completeness: float         # mean truncated distance gt -> pred
     chamfer: float              # (accuracy + completeness) / 2
@@ -265,6 +275,21 @@ class CloudMetrics(NamedTuple):
     n_gt_reached: int           # ... with a pred point within max_dist
     pred_to_gt: CloudNN
     gt_to_pred: CloudNN
+
+
+class CloudMetrics(_CloudMetricsFields):
+    """The twelve fields above -- it still unpacks into twelve -- and, behind them, `registration`: with a Registration policy the
+    RegistrationResult whose transform the clouds were compared under, else None."""
+    registration = None         # Optional[RegistrationResult]
+
+    def __new__(cls, *args, registration=None, **kw):
+        self = super().__new__(cls, *args, **kw)
+        self.registration = registration
+        return self
+
+    def _replace(self, **kw):
+        registration = kw.pop("registration", self.registration)
+        return type(self)(*super()._replace(**kw), registration=registration)
 
 
 def _f32(x) -> float:
@@ -369,39 +394,232 @@ def metrics_from_stats(pred_stats: Sequence[int], gt_stats: Sequence[int], max_d
 
 
 def cloud_metrics(pred: torch.Tensor, gt: torch.Tensor, *, max_dist: float, thresholds: Sequence[float],
-                  transform=None) -> CloudMetrics:
+                  transform=None, register: Optional["Registration"] = None, gt_normals: Optional[torch.Tensor] = None) -> CloudMetrics:
     """Accuracy, completeness, Chamfer distance and per-threshold precision / recall / F-score of pred [N,3] against gt [M,3]
     (module docstring), from one search each way.  transform = (R, t, s), as align_trajectory returns it, is applied to pred
     first.  The per-point results of both searches are returned (pred_to_gt.dist colours pred by its error).  Reads the 24
-    statistics back once, at the end."""
+    statistics back once, at the end.
+    With a Registration policy `register`, transform (the identity without one) is the start of register_clouds(pred, gt,
+    target_normals=gt_normals), whose refined transform -- one more read-back of 13 values -- is what the clouds are compared under; the
+    RegistrationResult is `.registration`.  The policy's max_dist None means this call's max_dist.  A registration that froze or
+    was reverted returns its start, so the measures are then those of the plain call.  register=None: every bit as without it."""
+    if register is not None:
+        _chk_registration("cloud_metrics", register)
     pred = _chk_cloud(pred, "pred")
     gt = _chk_cloud(gt, "gt")
     md, th = _chk_reach("cloud_metrics", max_dist, thresholds)
+    registration = None
+    if register is not None:
+        kw = register._asdict()
+        if kw["max_dist"] is None:
+            kw["max_dist"] = md
+        registration = register_clouds(pred, gt, target_normals=gt_normals, init=transform, **kw)
+        transform = registration.transform()
     if transform is not None:
         R, t, s = transform
         pred = transform_cloud(pred, R, t, s)
     a = nearest_neighbors(pred, gt, max_dist=md, thresholds=th)
     b = nearest_neighbors(gt, pred, max_dist=md, thresholds=th)
     both = torch.stack([a.stats, b.stats]).tolist()
-    return CloudMetrics(**metrics_from_stats(both[0], both[1], md, len(th)), pred_to_gt=a, gt_to_pred=b)
+    return CloudMetrics(**metrics_from_stats(both[0], both[1], md, len(th)), pred_to_gt=a, gt_to_pred=b, registration=registration)
 
 
 def reconstruction_metrics(pred_cloud, pred_cam2world, gt_depths: torch.Tensor, K: torch.Tensor, gt_cam2world, *,
                            voxel_size: float, max_dist: Optional[float] = None, thresholds: Optional[Sequence[float]] = None,
-                           align: str = "sim3", stride: int = 1, max_depth: float = MAX_DEPTH, min_obs: int = 1) -> CloudMetrics:
+                           align: str = "sim3", stride: int = 1, max_depth: float = MAX_DEPTH, min_obs: int = 1,
+                           register: Optional["Registration"] = None) -> CloudMetrics:
     """A reconstruction against ground truth: pred_cloud (an inference.FusedCloud or [M,3] points) in the frame of the
     trajectory pred_cam2world [N,4,4], against the cloud fused from gt_depths [N,1,H,W] along gt_cam2world [N,4,4] by
     inference.fuse_point_cloud at the same voxel_size (stride, max_depth, min_obs as there).  pred is moved by
     align_trajectory(pred_cam2world, gt_cam2world, align) and the two are compared by cloud_metrics.
-    max_dist defaults to 4 * voxel_size and thresholds to (voxel_size, 2 * voxel_size): choices, not tuned.  No ICP and no
-    surface meshing: the alignment is the trajectories', the comparison is point to point."""
+    max_dist defaults to 4 * voxel_size and thresholds to (voxel_size, 2 * voxel_size): choices, not tuned.  No surface meshing: the
+    comparison is point to point.  The alignment is the trajectories' -- a fit to N camera centres, which carries the predicted
+    trajectory's drift into the score -- unless a Registration policy `register` is given: the trajectories' alignment is then the
+    start of register_clouds(pred, ground truth) (point to plane by default, against the normals inference.cloud_normals gives the
+    ground-truth cloud from the very depths, stride and trajectory it was fused with), the refined transform is what the clouds are
+    compared under, and the RegistrationResult is the result's `.registration`."""
+    if register is not None:
+        _chk_registration("reconstruction_metrics", register)
     points = pred_cloud.points if isinstance(pred_cloud, inference.FusedCloud) else pred_cloud
     points = _chk_cloud(points, "pred_cloud")
     G = _poses(gt_cam2world, "gt_cam2world")
-    gt = inference.fuse_point_cloud(gt_depths, K, G.to(gt_depths.device, torch.float32), voxel_size=voxel_size, stride=stride,
-                                    max_depth=max_depth, min_obs=min_obs)
+    G32 = G.to(gt_depths.device, torch.float32)
+    gt = inference.fuse_point_cloud(gt_depths, K, G32, voxel_size=voxel_size, stride=stride, max_depth=max_depth, min_obs=min_obs)
     R, t, s = align_trajectory(pred_cam2world, G, align)
     vs = _f32(voxel_size)
+    gt_normals = None
+    if register is not None and register.metric == "plane":
+        gt_normals = inference.cloud_normals(gt, gt_depths, K, G32, stride=stride, max_depth=max_depth).normals
     return cloud_metrics(points, gt.points, max_dist=4.0 * vs if max_dist is None else max_dist,
                          thresholds=(vs, 2.0 * vs) if thresholds is None else thresholds,
-                         transform=None if align == "none" else (R, t, s))
+                         transform=None if align == "none" else (R, t, s), register=register, gt_normals=gt_normals)
+
+
+# ---- registration (csrc/register.hip) ------------------------------------------------------------------------------------- #
+REGISTER_MODES = ("se3", "sim3")          # the C ABI's 0 and 1
+REGISTER_METRICS = ("plane", "point")
+REGISTER_OK, REGISTER_TOO_FEW, REGISTER_NOT_PD, REGISTER_REVERTED = 0, 1, 2, 3
+REGISTER_HISTORY = ("n_valid", "n_reached", "n_used", "cost", "sum_r2")
+
+
+class Registration(NamedTuple):
+    """The policy of register_clouds.  Choices, not tuned values: sim3 because monocular scale is unobservable, plane because point
+    to point crawls on a tube, 20 iterations where the test scenes converge in 3, a damping that only keeps a well-posed system
+    away from a zero pivot, and 64 pairs as the least a 7-parameter fit should rest on."""
+    mode: str = "sim3"              # "sim3" or "se3" (s is then left as given)
+    metric: str = "plane"           # "plane" (needs the target's normals) or "point"
+    iterations: int = 20            # 1 .. 64 Gauss-Newton steps; there is no early exit
+    max_dist: Optional[float] = None    # reach of the nearest-neighbour search; None: the metrics' own max_dist
+    damping: float = 1e-9           # H_kk <- H_kk + damping * H_kk
+    min_pairs: int = 64             # fewer used pairs freeze the state (REGISTER_TOO_FEW)
+
+
+class RegistrationResult(NamedTuple):
+    R: torch.Tensor                 # [3,3] float64 on the device
+    t: torch.Tensor                 # [3]   float64
+    s: torch.Tensor                 # []    float64: x' = s R x + t
+    history: torch.Tensor           # [iterations+1,5] float64: REGISTER_HISTORY of every evaluation
+    status: torch.Tensor            # []    int32: REGISTER_*
+    normal_matrix: torch.Tensor     # [7,7] float64: sum J^T J of the final evaluation (v, omega, sigma), undamped
+
+    def transform(self) -> Tuple[torch.Tensor, torch.Tensor, float]:
+        """(R [3,3], t [3], s) on the host, float64, as align_trajectory returns it and cloud_metrics(transform=...) and
+        transform_cloud take it.  The one read-back."""
+        v = torch.cat([self.R.reshape(9), self.t.reshape(3), self.s.reshape(1)]).to("cpu")
+        return v[:9].reshape(3, 3).clone(), v[9:12].clone(), float(v[12])
+
+
+def _chk_registration(who: str, policy) -> "Registration":
+    if not isinstance(policy, Registration):
+        raise ValueError(f"{who}: register must be a Registration or None, got {type(policy).__name__}")
+    if policy.mode not in REGISTER_MODES:
+        raise ValueError(f"{who}: mode must be one of {REGISTER_MODES}, got {policy.mode!r}")
+    if policy.metric not in REGISTER_METRICS:
+        raise ValueError(f"{who}: metric must be one of {REGISTER_METRICS}, got {policy.metric!r}")
+    it = policy.iterations
+    if isinstance(it, bool) or not isinstance(it, int) or not 1 <= it <= 64:
+        raise ValueError(f"{who}: iterations must be an int in 1 .. 64, got {it!r}")
+    mp = policy.min_pairs
+    if isinstance(mp, bool) or not isinstance(mp, int) or not 1 <= mp < 2 ** 31:
+        raise ValueError(f"{who}: min_pairs must be an int >= 1, got {mp!r}")
+    try:
+        d = float(policy.damping)
+    except (TypeError, ValueError):
+        d = math.nan
+    if not (d >= 0.0 and math.isfinite(d)):
+        raise ValueError(f"{who}: damping must be finite and >= 0, got {policy.damping!r}")
+    if policy.max_dist is not None:
+        _chk_reach(who, policy.max_dist, ())
+    return policy
+
+
+def _register_inputs(who: str, source, target, target_normals, init, pivot, max_dist, metric):
+    """Checked inputs of the registration calls: (source, target, normals or None, state [13] float64 on the device, pivot [3] float32
+    on the device, max_dist as float32, index workspace with the target's index enqueued)."""
+    source = _chk_cloud(source, "source")
+    target = _chk_cloud(target, "target")
+    dev = source.device
+    if target.device != dev:
+        raise ValueError(f"{who}: target is on {target.device}, source on {dev}")
+    if metric not in REGISTER_METRICS:
+        raise ValueError(f"{who}: metric must be one of {REGISTER_METRICS}, got {metric!r}")
+    if target_normals is None:
+        if metric == "plane":
+            raise ValueError(f"{who}: metric 'plane' needs target_normals [M,3] (inference.cloud_normals(...).normals)")
+    else:
+        target_normals = _chk_cloud(target_normals, "target_normals")
+        if target_normals.shape != target.shape or target_normals.device != dev:
+            raise ValueError(f"{who}: target_normals {tuple(target_normals.shape)} on {target_normals.device} do not match target "
+                             f"{tuple(target.shape)} on {dev}")
+    md, _ = _chk_reach(who, max_dist, ())
+    if init is None:
+        state = torch.tensor([1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0], dtype=torch.float64)
+    else:
+        try:
+            R, t, s = init
+            R = torch.as_tensor(R).detach().to("cpu", torch.float64)
+            t = torch.as_tensor(t).detach().to("cpu", torch.float64)
+            s = torch.as_tensor(s).detach().to("cpu", torch.float64)
+        except (TypeError, ValueError, RuntimeError):
+            raise ValueError(f"{who}: init must be (R [3,3], t [3], s), as align_trajectory returns it") from None
+        if tuple(R.shape) != (3, 3) or tuple(t.shape) != (3,) or s.numel() != 1:
+            raise ValueError(f"{who}: init must be (R [3,3], t [3], s), got shapes {tuple(R.shape)}, {tuple(t.shape)}, {tuple(s.shape)}")
+        state = torch.cat([R.reshape(9), t, s.reshape(1)])
+        if not bool(torch.isfinite(state).all()):
+            raise ValueError(f"{who}: init must be finite")
+    M = target.shape[0]
+    if pivot is None:
+        # the centre of the box of the target's finite points: amin / amax are exact and order-free; no read-back
+        if M == 0:
+            pv = torch.zeros(3, device=dev, dtype=torch.float32)
+        else:
+            fin = torch.isfinite(target).all(dim=1, keepdim=True)
+            lo = torch.where(fin, target, torch.full_like(target, math.inf)).amin(dim=0)
+            hi = torch.where(fin, target, torch.full_like(target, -math.inf)).amax(dim=0)
+            pv = 0.5 * lo + 0.5 * hi
+            pv = torch.where(torch.isfinite(pv), pv, torch.zeros_like(pv))
+    else:
+        try:
+            pv = torch.as_tensor(pivot).detach().to(torch.float32).reshape(-1)
+        except (TypeError, ValueError, RuntimeError):
+            raise ValueError(f"{who}: pivot must be three numbers") from None
+        if pv.numel() != 3:
+            raise ValueError(f"{who}: pivot must be three numbers, got {pv.numel()}")
+        pv = pv.to(dev).contiguous()
+    lib = _lib.load()
+    nbytes = int(lib.colvo_cloud_workspace_bytes(0, M))
+    if nbytes == 0 or int(lib.colvo_register_scratch_bytes(source.shape[0])) == 0:
+        raise ValueError(f"{who}: {source.shape[0]} source and {M} target points: each cloud must hold fewer than 2^30")
+    index = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    _lib.check(lib.colvo_cloud_index_build(_lib.ptr(target), M, md, _lib.ptr(index), _lib.stream_ptr()), "colvo_cloud_index_build")
+    return source, target, target_normals, state.to(dev), pv, md, index
+
+
+def register_accumulate(source: torch.Tensor, target: torch.Tensor, *, target_normals: Optional[torch.Tensor] = None, init=None,
+                        pivot=None, max_dist: float, metric: str = "plane") -> Tuple[torch.Tensor, torch.Tensor]:
+    """One evaluation of the registration's sums at the state `init` (contract: include/colvo.h colvo_register_accumulate):
+    (sums [40] float64: the 28 upper-triangle entries of sum J^T J, the 7 of sum J^T r, the truncated cost C, sum r^2, three zeros;
+    counts [4] int64: n_valid, n_reached, n_used, 0), on the device.  The test hook of register_clouds."""
+    who = "register_accumulate"
+    source, target, normals, state, pv, md, index = _register_inputs(who, source, target, target_normals, init, pivot, max_dist, metric)
+    lib = _lib.load()
+    dev = source.device
+    N, M = source.shape[0], target.shape[0]
+    ws = torch.empty(int(lib.colvo_register_scratch_bytes(N)), device=dev, dtype=torch.uint8)
+    sums = torch.empty(40, device=dev, dtype=torch.float64)
+    counts = torch.empty(4, device=dev, dtype=torch.int64)
+    _lib.check(lib.colvo_register_accumulate(_lib.ptr(source), N, _lib.ptr(target), _lib.ptr(normals), M, md, _lib.ptr(index),
+                                             _lib.ptr(state), _lib.ptr(pv), REGISTER_METRICS.index(metric), _lib.ptr(ws),
+                                             _lib.ptr(sums), _lib.ptr(counts), _lib.stream_ptr()), "colvo_register_accumulate")
+    return sums, counts
+
+
+def register_clouds(source: torch.Tensor, target: torch.Tensor, *, target_normals: Optional[torch.Tensor] = None, init=None,
+                    pivot=None, max_dist: float, mode: str = "sim3", metric: str = "plane", iterations: int = 20,
+                    damping: float = 1e-9, min_pairs: int = 64) -> RegistrationResult:
+    """Register source [N,3] onto target [M,3] (float32 clouds on the GPU): `iterations` Gauss-Newton steps of point-to-plane ICP
+    against target_normals [M,3] (a zero normal: the point takes no part), or of point-to-point ICP, on the (R, t, s) of
+    x' = s R x + t (module docstring; contract: include/colvo.h colvo_register_clouds).
+    init = (R, t, s) as align_trajectory returns it (None: the identity); the source itself is never pre-transformed, so a sample is
+    rounded to float32 once.  pivot: the point the update turns and scales about -- it conditions the problem and does not change
+    what is minimised --, by default the centre of the box of the target's finite points.  max_dist is the reach of the search; pairs
+    further apart do not exist.  The defaults are Registration's: choices, not tuned.
+    Builds the target's index, enqueues everything on the current stream and returns device tensors: no read-back and no host
+    synchronisation (RegistrationResult.transform() is the read-back).  Check `status`: anything but REGISTER_OK returned init."""
+    who = "register_clouds"
+    policy = _chk_registration(who, Registration(mode, metric, iterations, None, damping, min_pairs))
+    source, target, normals, state, pv, md, index = _register_inputs(who, source, target, target_normals, init, pivot, max_dist, metric)
+    lib = _lib.load()
+    dev = source.device
+    N, M = source.shape[0], target.shape[0]
+    ws = torch.empty(int(lib.colvo_register_scratch_bytes(N)), device=dev, dtype=torch.uint8)
+    out = torch.empty(13, device=dev, dtype=torch.float64)
+    history = torch.empty(policy.iterations + 1, 5, device=dev, dtype=torch.float64)
+    status = torch.empty(1, device=dev, dtype=torch.int32)
+    normal = torch.empty(7, 7, device=dev, dtype=torch.float64)
+    _lib.check(lib.colvo_register_clouds(_lib.ptr(source), N, _lib.ptr(target), _lib.ptr(normals), M, md, _lib.ptr(index),
+                                         _lib.ptr(state), _lib.ptr(pv), REGISTER_MODES.index(policy.mode),
+                                         REGISTER_METRICS.index(policy.metric), policy.iterations, float(policy.damping),
+                                         int(policy.min_pairs), _lib.ptr(ws), _lib.ptr(out), _lib.ptr(history), _lib.ptr(status),
+                                         _lib.ptr(normal), _lib.stream_ptr()), "colvo_register_clouds")
+    return RegistrationResult(out[:9].view(3, 3), out[9:12], out[12], history, status[0], normal)

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define COLVO_ABI_VERSION 21
+#define COLVO_ABI_VERSION 22
 
 typedef void* colvo_stream_t; /* hipStream_t */
 
@@ -768,6 +768,64 @@ int colvo_cloud_index_build(const float* ref, int M, float max_dist, void* works
 int colvo_cloud_query(const float* query, int N, int M, float max_dist, const float* thresholds, int n_thresholds, void* workspace,
                       float* dist, float* dist2, int32_t* nearest, uint64_t* stats, colvo_stream_t stream);
 int colvo_cloud_transform(const float* points, int N, const float* Rts, float* out, colvo_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------- *
+ * Registration of two point clouds: point-to-plane (or point-to-point) ICP over the index of    *
+ * colvo_cloud_index_build (NumPy replica tests/register_ref.py).               *
+ * ------------------------------------------------------------------------------------------- */
+/* source Q [N,3], target P [M,3] and the target's normals Nrm [M,3] (world frame; a zero normal means "none", as
+ * colvo_cloud_normals delivers it; NULL with the point metric), float32, contiguous.  index: the workspace
+ * colvo_cloud_index_build(P, M, max_dist, ...) wrote, with the same M and max_dist; it is only read.  state: 13 float64 values on the
+ * device, R row-major, t, s, with x' = s R x + t.  pivot c: float32[3] on the device.
+ *   per point  float32, every operation individually rounded (no FMA contraction), the state rounded to float32 first:
+ *              x'_a = ((s * ((r_a0 * x + r_a1 * y) + r_a2 * z)) + t_a)   -- colvo_cloud_transform's formula;
+ *              the nearest target point p by colvo_cloud_query's rule UNCHANGED (the same routine, csrc/cloud_grid.h): x' is valid
+ *              iff its coordinates are finite, reach is strict (d2 < md2), the minimum is taken over the keys (bits(d2) << 32) | index,
+ *              so ties go to the smallest original index; the grid walk, its clamps and the cell margin are the query's.
+ *              e = x' - p, y = x' - c, per component.
+ *   plane      with n = Nrm[index of p]: the pair is USED iff x' is valid and reached and (n_x*n_x + n_y*n_y) + n_z*n_z > 0 (NaN fails);
+ *              r = (n_x*e_x + n_y*e_y) + n_z*e_z;  J = [n_x, n_y, n_z, (y x n)_x, (y x n)_y, (y x n)_z, (n_x*y_x + n_y*y_y) + n_z*y_z],
+ *              y x n = ((y_y * n_z) - (y_z * n_y), (y_z * n_x) - (y_x * n_z), (y_x * n_y) - (y_y * n_x)).
+ *   point      used iff valid and reached; three rows with r_a = e_a:
+ *              (1,0,0, 0, y_z, -y_y, y_x), (0,1,0, -y_z, 0, y_x, y_y), (0,0,1, y_y, -y_x, 0, y_z).
+ *   cost       of a valid x': plane, used: min(double(r)^2, double(md2)); point, used: double(d2); valid and not used: double(md2).
+ *              C is their sum and F = C / n_valid the call's own measure.
+ *   sums       float64: the 28 upper-triangle entries of sum J^T J (row-major: (0,0) .. (0,6), (1,1) ..), the 7 of sum J^T r, C, and
+ *              sum r^2 over the used rows -- 37 values -- and the integers n_valid, n_reached, n_used.  Rows and residuals are
+ *              float32, so every product is exact in float64; every term enters by one rounded addition, in an order fixed by the
+ *              kernels and a function of N alone (per thread over its 4 points, a fixed reduction over the wave and the workgroup, the
+ *              workgroups' rows in a fixed order; no floating-point atomics): identical bits on every call and stream.
+ *   step       float64, one thread: the unknowns are (v, omega) and, in mode sim3, sigma -- 6 or 7; H + damping * diag(H), Cholesky,
+ *              delta = -H^-1 sum J^T r; about the pivot: R <- Exp(omega) R, t <- e^sigma Exp(omega) (t - c) + c + v, s <- e^sigma s,
+ *              Exp by the closed form (Rodrigues; its series below |omega|^2 = 1e-8).  In mode se3 sigma = 0 and s is not touched.
+ *   loop       `iterations` times sums and step, then the sums of the final state.  history [iterations + 1][5] float64 holds
+ *              n_valid, n_reached, n_used, C, sum r^2 of every evaluation.  The state FREEZES -- it is the initial one, to the bit, for
+ *              the rest of the call -- with status 1 (too few) if n_used < min_pairs at an evaluation a step follows, and with
+ *              status 2 (not positive definite) at a pivot of the Cholesky factor that is not positive.  A call whose F_final >
+ *              F_initial is REVERTED to its initial state, to the bit, status 3.  Status 0: registered.  normal_matrix [7][7]: the
+ *              undamped sum J^T J of the final evaluation, symmetric -- a surface with a free motion (a perfect cylinder) shows there
+ *              as a vanishing pivot, and gives status 2 where the pivot is exactly zero; a nearly singular problem may step far and
+ *              is caught by the revert.  There is no convergence test and no early exit: both would need a read-back.
+ * mode: 0 se3, 1 sim3.  metric: 0 plane, 1 point.
+ * colvo_register_accumulate: the sums of one evaluation at the state given: out_sums [40] float64 (the 37 and three zeros),
+ * out_counts [4] int64 (n_valid, n_reached, n_used, 0).
+ * colvo_register_clouds: the whole loop; out_state [13] float64 (it must not alias state_init), status [1] int32.  No read-back and no
+ * host synchronisation.
+ * workspace: colvo_register_scratch_bytes(N) bytes, 16-byte aligned, written by the call (one row of 40 doubles per 1024 source points,
+ * the float32 state); 0 for an N the calls refuse.  The index is not written: several registrations may share one.
+ * Whatever the index's header, its cell starts, its records or the normals hold, no address leaves its array: the cell counts and
+ * dims are clamped as the query clamps them, record positions to [0, M), and P and Nrm are read only at a record's index in [0, M).
+ * Limits: N, M < 2^30 (0 is legal: an empty side launches nothing that indexes; the pointers of an empty cloud may be NULL);
+ * max_dist as colvo_cloud_index_build takes it; 1 <= iterations <= 64; damping finite and >= 0; min_pairs >= 1; workspace and
+ * index 16-byte aligned.  Everything is refused before any HIP call with a message that starts `colvo_register_`. */
+size_t colvo_register_scratch_bytes(int N);
+int colvo_register_accumulate(const float* source, int N, const float* target, const float* normals, int M, float max_dist,
+                              const void* index, const double* state, const float* pivot, int metric, void* workspace,
+                              double* out_sums, int64_t* out_counts, colvo_stream_t stream);
+int colvo_register_clouds(const float* source, int N, const float* target, const float* normals, int M, float max_dist,
+                          const void* index, const double* state_init, const float* pivot, int mode, int metric, int iterations,
+                          double damping, int min_pairs, void* workspace, double* out_state, double* history, int32_t* status,
+                          double* normal_matrix, colvo_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------- *
  * SURVEY.md §8f-4  frames as a decoder delivers them -> the path's input format.                *
