@@ -5,10 +5,13 @@
 //   k_refine_init    one thread per edge: checks the edge, rounds its float64 state to the float32 the per-pixel pass reads.
 //   k_refine_accum   grid (strips, E), a wave per 8x8 tile, TILES_PER_WAVE tiles per wave: projection and taps as k_consist_filter, the
 //                    two whitened rows and residuals in float32, the 46 sums in float64 per thread (products of two float32 values are
-//                    exact in float64, so every fma below is an exact product and one rounded addition), a fixed butterfly over the
+//                    exact in float64, so every fma is an exact product and one rounded addition), a fixed butterfly over the
 //                    wave, the four waves added in a fixed tree: one row of 52 doubles per workgroup.  No atomics.
 //   k_refine_solve   one workgroup per edge: the rows summed in a fixed order; then one thread: damped normal equations, Cholesky in
 //                    LDS, closed-form SE(3) exponential, the update, the history row, freeze and revert.
+//
+// The sums' layout and reduction, the row summation, the solve and the rotation are gauss_newton.h's, shared with register.hip; the
+// per-sample arithmetic, the history, the cost in the revert test and the state update are this file's.
 //
 // Every float32 operation of a sample is individually rounded -- contraction is off for this whole file -- and the order of every
 // float64 addition is fixed by the code: a call's bits do not depend on scheduling or on the stream.
@@ -16,6 +19,8 @@
 #include "tuning.h"
 
 #pragma clang fp contract(off)
+
+#include "gauss_newton.h"
 
 namespace colvo {
 namespace {
@@ -30,9 +35,8 @@ constexpr int STATE = 16;                  // values per edge state: R row-major
 constexpr int NT_SOLVE = 512;
 constexpr int GROUPS = NT_SOLVE / 64;
 constexpr float Z_EPS = 1e-3f;
-enum { ST_OK = 0, ST_TOO_FEW = 1, ST_NOT_PD = 2, ST_REVERTED = 3, ST_BAD_EDGE = 4 };
+constexpr int ST_BAD_EDGE = 4;             // beside gn::OK .. gn::REVERTED
 enum { FLAG_GEO = 1, FLAG_PHOTO = 2, FLAG_BRIGHT = 4 };
-enum { MODE_SUMS = 0, MODE_STEP = 1, MODE_FINAL = 2 };
 
 struct Geom {
     int N, H, W, E, tiles_x, tiles, strips;
@@ -61,7 +65,7 @@ __global__ __launch_bounds__(NT) void k_refine_init(const int32_t* __restrict__ 
     const int e = blockIdx.x * NT + threadIdx.x;
     if (e >= E) return;
     const int i = edges[2 * e], j = edges[2 * e + 1];
-    status[e] = (i >= 0 && i < N && j >= 0 && j < N && i != j) ? ST_OK : ST_BAD_EDGE;
+    status[e] = (i >= 0 && i < N && j >= 0 && j < N && i != j) ? gn::OK : ST_BAD_EDGE;
     const double* t = T + (size_t)e * 16;
     float* s = st32 + (size_t)e * STATE;
 #pragma unroll
@@ -97,24 +101,6 @@ __device__ __forceinline__ void cross_P(float Px, float Py, float Pz, float* row
     row[3] = (Py * row[2]) - (Pz * row[1]);
     row[4] = (Pz * row[0]) - (Px * row[2]);
     row[5] = (Px * row[1]) - (Py * row[0]);
-}
-
-template <int NC>                          // the NC x NC upper triangle and the NC products with e, into the 8 x 8 layout
-__device__ __forceinline__ void add_row(const float* J, float e, double* acc) {
-    double Jd[NC];
-#pragma unroll
-    for (int k = 0; k < NC; ++k) Jd[k] = (double)J[k];
-    const double ed = (double)e;
-    int idx = 0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-#pragma unroll
-        for (int l = k; l < 8; ++l, ++idx) {
-            if (k < NC && l < NC) acc[idx] = __builtin_fma(Jd[k], Jd[l], acc[idx]);      // exact product, one rounded addition
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < NC; ++k) acc[36 + k] = __builtin_fma(Jd[k], ed, acc[36 + k]);
 }
 
 // grid (strips, E)
@@ -200,7 +186,7 @@ __global__ __launch_bounds__(NT) void k_refine_accum(const float* __restrict__ d
 #pragma unroll
             for (int q = 0; q < 6; ++q) J[q] = use ? J[q] * p.inv_sg : 0.0f;
             n_geo += (int)__popcll(__ballot(use));
-            add_row<6>(J, use ? eg : 0.0f, acc);                 // an unused sample adds exact zeros; a branch around this
+            gn::add_row<6, 8>(J, use ? eg : 0.0f, acc);          // an unused sample adds exact zeros; a branch around this
                                                                  // cost 116 AGPRs of copies at the join
             const double e2 = (double)eg * (double)eg;
             acc[44] += visible ? fmin(e2, p.cap_g) : 0.0;
@@ -220,33 +206,14 @@ __global__ __launch_bounds__(NT) void k_refine_accum(const float* __restrict__ d
 #pragma unroll
             for (int q = 0; q < 8; ++q) J[q] = use ? J[q] * p.inv_sp : 0.0f;
             n_photo += (int)__popcll(__ballot(use));
-            add_row<8>(J, use ? ep : 0.0f, acc);
+            gn::add_row<8, 8>(J, use ? ep : 0.0f, acc);
             const double e2 = (double)ep * (double)ep;
             acc[45] += visible ? fmin(e2, p.cap_p) : 0.0;
         }
     }
 
-#pragma unroll
-    for (int k = 0; k < N_SUMS; ++k) {
-        double v = acc[k];
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-        if (lane == 0) red[wave][k] = v;
-    }
-    if (lane == 0) {
-        cnt[wave][0] = n_vis;
-        cnt[wave][1] = n_geo;
-        cnt[wave][2] = n_photo;
-    }
-    __syncthreads();
-    double* row = rows + ((size_t)e * g.strips + blockIdx.x) * ROW;
-    const int m = threadIdx.x;
-    if (m < N_SUMS) {
-        row[m] = (red[0][m] + red[1][m]) + (red[2][m] + red[3][m]);
-    } else if (m < N_SUMS + 3) {
-        const int q = m - N_SUMS;
-        row[m] = __longlong_as_double((long long)((cnt[0][q] + cnt[1][q]) + (cnt[2][q] + cnt[3][q])));
-    }
+    gn::write_partial_row<N_SUMS>(acc, n_vis, n_geo, n_photo, red, cnt, rows + ((size_t)e * g.strips + blockIdx.x) * ROW,
+                                  gn::XorButterfly());
 }
 
 struct Solve {
@@ -254,9 +221,9 @@ struct Solve {
     double damping;
 };
 
-// grid E, NT_SOLVE threads: group w of 64 lanes sums the rows w, w + GROUPS, ... of entry `lane` in order; the GROUPS partial totals are
-// added in order; thread 0 does the rest.  MODE_SUMS: the totals to out_sums [E][48] / out_counts [E][4].  MODE_STEP: history row `it`,
-// one Gauss-Newton step on the live state.  MODE_FINAL: history row `iterations`, the revert test.
+// grid E, NT_SOLVE threads: the rows of the edge summed by gn::sum_rows (none of a bad edge); thread 0 does the rest.  gn::SUMS: the
+// totals to out_sums [E][48] / out_counts [E][4].  gn::STEP: history row `it`, one Gauss-Newton step on the live state.  gn::FINAL:
+// history row `iterations`, the revert test.
 __global__ __launch_bounds__(NT_SOLVE) void k_refine_solve(const double* __restrict__ rows, int strips, int mode, Solve sv,
                                                             const double* __restrict__ T_init, double* __restrict__ live_T,
                                                             double* __restrict__ live_gain, double* __restrict__ live_offset,
@@ -268,36 +235,8 @@ __global__ __launch_bounds__(NT_SOLVE) void k_refine_solve(const double* __restr
     __shared__ double A[8][8];                                   // the normal matrix, then its Cholesky factor (lower)
     __shared__ double xs[8];
     const int e = blockIdx.x;
-    const int grp = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const bool bad = status[e] == ST_BAD_EDGE;
-    if (lane < N_SUMS + 3) {
-        const double* r = rows + (size_t)e * strips * ROW + lane;
-        if (lane < N_SUMS) {
-            double v = 0.0;
-            if (!bad)
-                for (int c = grp; c < strips; c += GROUPS) v += r[(size_t)c * ROW];
-            part[grp][lane] = v;
-        } else {
-            long long v = 0;
-            if (!bad)
-                for (int c = grp; c < strips; c += GROUPS) v += __double_as_longlong(r[(size_t)c * ROW]);
-            part[grp][lane] = __longlong_as_double(v);
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < N_SUMS) {
-        double v = part[0][threadIdx.x];
-#pragma unroll
-        for (int w = 1; w < GROUPS; ++w) v += part[w][threadIdx.x];
-        tot[threadIdx.x] = v;
-    } else if (threadIdx.x < N_SUMS + 3) {
-        long long v = 0;
-#pragma unroll
-        for (int w = 0; w < GROUPS; ++w) v += __double_as_longlong(part[w][threadIdx.x]);
-        tot[threadIdx.x] = (double)v;                            // a count is below 2^30: exact
-    }
-    __syncthreads();
-    if (mode == MODE_SUMS) {
+    gn::sum_rows<N_SUMS, ROW, GROUPS>(rows + (size_t)e * strips * ROW, strips, status[e] == ST_BAD_EDGE, part, tot);
+    if (mode == gn::SUMS) {
         if (threadIdx.x < 48) out_sums[(size_t)e * 48 + threadIdx.x] = threadIdx.x < N_SUMS ? tot[threadIdx.x] : 0.0;
         if (threadIdx.x < 4) out_counts[(size_t)e * 4 + threadIdx.x] = threadIdx.x < 3 ? (int)tot[N_SUMS + threadIdx.x] : 0;
         return;
@@ -312,78 +251,30 @@ __global__ __launch_bounds__(NT_SOLVE) void k_refine_solve(const double* __restr
     h[3] = tot[N_SUMS + 2];
     h[4] = tot[45];
     int st = status[e];
-    if (st != ST_OK) return;                                     // frozen: the state is the initial one already
+    if (st != gn::OK) return;                                    // frozen: the state is the initial one already
 
     double* Tl = live_T + (size_t)e * 16;
     bool restore = false;
-    if (mode == MODE_FINAL) {
+    if (mode == gn::FINAL) {
         const double* h0 = history + (size_t)e * (sv.iterations + 1) * 5;
         const double F1 = (tot[44] + tot[45]) / n_vis, F0 = (h0[2] + h0[4]) / h0[0];
         if (F1 > F0) {                                           // (NaN: no revert)
-            st = ST_REVERTED;
+            st = gn::REVERTED;
             restore = true;
         }
     } else if (n_vis < (double)sv.min_samples) {
-        st = ST_TOO_FEW;
+        st = gn::TOO_FEW;
         restore = true;
     } else {
         const int n = ((sv.flags & FLAG_PHOTO) && (sv.flags & FLAG_BRIGHT)) ? 8 : 6;
-        int idx = 0;
-        for (int k = 0; k < 8; ++k)
-            for (int l = k; l < 8; ++l, ++idx) A[k][l] = tot[idx];                 // upper: the matrix; the factor goes below
-        for (int k = 0; k < n; ++k) A[k][k] = A[k][k] + sv.damping * A[k][k];
-        bool pd = true;
-        for (int k = 0; k < n && pd; ++k) {
-            double s = A[k][k];
-            for (int m = 0; m < k; ++m) s -= A[k][m] * A[k][m];
-            if (!(s > 0.0)) { pd = false; break; }
-            const double lkk = sqrt(s);
-            for (int r = k + 1; r < n; ++r) {
-                double q = A[k][r];
-                for (int m = 0; m < k; ++m) q -= A[r][m] * A[k][m];
-                A[r][k] = q / lkk;
-            }
-            A[k][k] = lkk;                                       // (the diagonal of the matrix is not read again)
-        }
-        if (!pd) {
-            st = ST_NOT_PD;
+        if (!gn::solve_damped<8>(A, xs, tot, n, sv.damping)) {
+            st = gn::NOT_PD;
             restore = true;
         } else {
-            for (int k = 0; k < n; ++k) {                        // L y = -g
-                double q = -tot[36 + k];
-                for (int m = 0; m < k; ++m) q -= A[k][m] * xs[m];
-                xs[k] = q / A[k][k];
-            }
-            for (int k = n - 1; k >= 0; --k) {                   // L^T x = y
-                double q = xs[k];
-                for (int m = k + 1; m < n; ++m) q -= A[m][k] * xs[m];
-                xs[k] = q / A[k][k];
-            }
             // T <- exp(delta_1..6) T
-            const double u0 = xs[0], u1 = xs[1], u2 = xs[2], w0 = xs[3], w1 = xs[4], w2 = xs[5];
-            const double th2 = (w0 * w0 + w1 * w1) + w2 * w2;
-            double ca, cb, cc;
-            if (th2 < 1e-8) {
-                ca = 1.0 - th2 / 6.0;
-                cb = 0.5 - th2 / 24.0;
-                cc = 1.0 / 6.0 - th2 / 120.0;
-            } else {
-                const double th = sqrt(th2);
-                ca = sin(th) / th;
-                cb = (1.0 - cos(th)) / th2;
-                cc = (th - sin(th)) / (th2 * th);
-            }
-            const double Wm[3][3] = {{0.0, -w2, w1}, {w2, 0.0, -w0}, {-w1, w0, 0.0}};
-            double W2[3][3], Rx[3][3], V[3][3];
-#pragma unroll
-            for (int r = 0; r < 3; ++r)
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    W2[r][c] = (Wm[r][0] * Wm[0][c] + Wm[r][1] * Wm[1][c]) + Wm[r][2] * Wm[2][c];
-                    const double id = r == c ? 1.0 : 0.0;
-                    Rx[r][c] = (id + ca * Wm[r][c]) + cb * W2[r][c];
-                    V[r][c] = (id + cb * Wm[r][c]) + cc * W2[r][c];
-                }
+            const double u0 = xs[0], u1 = xs[1], u2 = xs[2];
+            double Rx[3][3], V[3][3];
+            gn::rot_exp(xs[3], xs[4], xs[5], Rx, V);
             double Tn[12];
 #pragma unroll
             for (int r = 0; r < 3; ++r) {
@@ -510,7 +401,7 @@ extern "C" int colvo_refine_accumulate(const float* depths, const float* frames,
                   (const int32_t*)w.status, g, p, w.rows);
     COLVO_CHECK_LAUNCH("k_refine_accum");
     Solve sv{};
-    colvo::launch(k_refine_solve, dim3(E), dim3(NT_SOLVE), 0, s, (const double*)w.rows, g.strips, (int)MODE_SUMS, sv,
+    colvo::launch(k_refine_solve, dim3(E), dim3(NT_SOLVE), 0, s, (const double*)w.rows, g.strips, gn::SUMS, sv,
                   (const double*)nullptr, (double*)nullptr, (double*)nullptr, (double*)nullptr, (float*)nullptr, (double*)nullptr,
                   w.status, out_sums, out_counts);
     COLVO_CHECK_LAUNCH("k_refine_solve");
@@ -525,10 +416,8 @@ extern "C" int colvo_refine_edges(const float* depths, const float* frames, cons
     COLVO_CHECK_ARG(depths && frames && K && edges && T_init && workspace && out_T && out_gain && out_offset && history && status,
                     "colvo_refine_edges: null pointer argument");
     COLVO_CHECK_ARG(shape_ok(E, N, H, W), "colvo_refine_edges: bad shape E=%d N=%d H=%d W=%d", E, N, H, W);
-    COLVO_CHECK_ARG(iterations >= 1 && iterations <= 64, "colvo_refine_edges: bad iterations %d (1 .. 64)", iterations);
     if (int rc = check_policy("colvo_refine_edges", sigma_geo, sigma_photo, gate_geo, gate_photo, max_depth, terms)) return rc;
-    COLVO_CHECK_ARG(damping >= 0.0 && damping < (double)__builtin_inff() && min_samples >= 1,
-                    "colvo_refine_edges: bad damping %g (finite, >= 0) or min_samples %d (>= 1)", damping, min_samples);
+    if (int rc = gn::check_loop("colvo_refine_edges", iterations, damping, "min_samples", min_samples)) return rc;
     COLVO_CHECK_ARG(aligned16(workspace), "colvo_refine_edges: workspace must be 16-byte aligned");
     COLVO_CHECK_ARG(out_T != T_init, "colvo_refine_edges: out_T must not alias T_init");
     hipStream_t s = (hipStream_t)stream;
@@ -552,7 +441,7 @@ extern "C" int colvo_refine_edges(const float* depths, const float* frames, cons
         COLVO_CHECK_LAUNCH("k_refine_accum");
         sv.it = it;
         colvo::launch(k_refine_solve, dim3(E), dim3(NT_SOLVE), 0, s, (const double*)w.rows, g.strips,
-                      (int)(it < iterations ? MODE_STEP : MODE_FINAL), sv, T_init, out_T, out_gain, out_offset, w.st32, history, status,
+                      it < iterations ? gn::STEP : gn::FINAL, sv, T_init, out_T, out_gain, out_offset, w.st32, history, status,
                       (double*)nullptr, (int32_t*)nullptr);
         COLVO_CHECK_LAUNCH("k_refine_solve");
     }

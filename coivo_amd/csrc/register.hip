@@ -7,10 +7,13 @@
 //   k_register_accum   one lane per source point, PER_LANE points per lane: the transform by k_cloud_transform's formula, the nearest
 //                      target point by k_cloud_query's walk (cloud_grid.h nearest_key: the one routine), the Jacobian rows and residuals
 //                      in float32, the 37 sums in float64 per thread (products of two float32 values are exact in float64, so every fma
-//                      below is an exact product and one rounded addition), a fixed reduction over the wave, the four waves added in a
+//                      is an exact product and one rounded addition), a fixed reduction over the wave, the four waves added in a
 //                      fixed tree: one row of 40 doubles per workgroup.  No atomics.
 //   k_register_solve   one workgroup: the rows summed in a fixed order; then one thread: damped normal equations, Cholesky in LDS,
 //                      closed-form rotation, the update about the pivot, the history row, freeze and revert.
+//
+// The sums' layout and reduction, the row summation, the solve and the rotation are gauss_newton.h's, shared with refine.hip; the
+// per-point arithmetic, the history, the cost in the revert test and the state update are this file's.
 //
 // Every float32 operation of a sample is individually rounded -- contraction is off for this whole file -- and the order of every
 // float64 addition is fixed by the code and a function of N alone: a call's bits do not depend on scheduling or on the stream.
@@ -19,6 +22,7 @@
 #pragma clang fp contract(off)
 
 #include "cloud_grid.h"
+#include "gauss_newton.h"
 
 namespace colvo {
 namespace {
@@ -35,10 +39,8 @@ constexpr int STATE = 13;                  // R row-major, t, s
 constexpr int ST32 = 16;                   // ... rounded to float32, padded
 constexpr int NT_SOLVE = 256;
 constexpr int GROUPS = NT_SOLVE / 64;
-enum { ST_OK = 0, ST_TOO_FEW = 1, ST_NOT_PD = 2, ST_REVERTED = 3 };
 enum { UNKNOWNS_SE3 = 0, UNKNOWNS_SIM3 = 1 };
 enum { METRIC_PLANE = 0, METRIC_POINT = 1 };
-enum { MODE_SUMS = 0, MODE_STEP = 1, MODE_FINAL = 2 };
 
 // one thread
 __global__ void k_register_init(const double* __restrict__ state, double* __restrict__ live, float* __restrict__ st32,
@@ -50,36 +52,13 @@ __global__ void k_register_init(const double* __restrict__ state, double* __rest
         if (live) live[k] = state[k];
     }
     st32[13] = st32[14] = st32[15] = 0.0f;
-    if (status) status[0] = ST_OK;
+    if (status) status[0] = gn::OK;
 }
 
-// the 7 x 7 upper triangle and the 7 products with r
+// a row of 7 into the sums, and r^2 into the last of them
 __device__ __forceinline__ void add_row(const float* J, float r, double* acc) {
-    double Jd[7];
-#pragma unroll
-    for (int k = 0; k < 7; ++k) Jd[k] = (double)J[k];
-    const double rd = (double)r;
-    int idx = 0;
-#pragma unroll
-    for (int k = 0; k < 7; ++k) {
-#pragma unroll
-        for (int l = k; l < 7; ++l, ++idx) acc[idx] = __builtin_fma(Jd[k], Jd[l], acc[idx]);      // exact product, one rounded addition
-    }
-#pragma unroll
-    for (int k = 0; k < 7; ++k) acc[28 + k] = __builtin_fma(Jd[k], rd, acc[28 + k]);
-    acc[36] = __builtin_fma(rd, rd, acc[36]);
-}
-
-// Sum over the 64 lanes in a fixed order, valid in lanes 0, 16, 32 and 48: row rotations by DPP on the two halves of the value, then
-// the four row totals through scalar registers.
-__device__ __forceinline__ double wave_sum_fixed(double v) {
-    v += __longlong_as_double(row_ror<8>(__double_as_longlong(v)));
-    v += __longlong_as_double(row_ror<4>(__double_as_longlong(v)));
-    v += __longlong_as_double(row_ror<2>(__double_as_longlong(v)));
-    v += __longlong_as_double(row_ror<1>(__double_as_longlong(v)));
-    const long long b = __double_as_longlong(v);
-    return (__longlong_as_double(lane_value(b, 0)) + __longlong_as_double(lane_value(b, 16))) +
-           (__longlong_as_double(lane_value(b, 32)) + __longlong_as_double(lane_value(b, 48)));
+    gn::add_row<7, 7>(J, r, acc);
+    acc[36] = __builtin_fma((double)r, (double)r, acc[36]);
 }
 
 // grid ceil(N / PER_WG).  P [M,3] and Nrm [M,3] are read at the index a record carries, and only where it lies in [0, M).
@@ -92,7 +71,6 @@ __global__ __launch_bounds__(NT) void k_register_accum(const float* __restrict__
     __shared__ double red[NT / 64][N_SUMS];
     __shared__ int cnt[NT / 64][3];
     const Grid G = load_grid(h);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const float* T = st32;
     const float s = T[12];
     const float c[3] = {pivot[0], pivot[1], pivot[2]};
@@ -170,25 +148,7 @@ __global__ __launch_bounds__(NT) void k_register_accum(const float* __restrict__
         }
     }
 
-#pragma unroll
-    for (int k = 0; k < N_SUMS; ++k) {
-        const double v = wave_sum_fixed(acc[k]);
-        if (lane == 0) red[wave][k] = v;
-    }
-    if (lane == 0) {
-        cnt[wave][0] = n_valid;
-        cnt[wave][1] = n_reached;
-        cnt[wave][2] = n_used;
-    }
-    __syncthreads();
-    double* row = rows + (size_t)blockIdx.x * ROW;
-    const int m = threadIdx.x;
-    if (m < N_SUMS) {
-        row[m] = (red[0][m] + red[1][m]) + (red[2][m] + red[3][m]);
-    } else if (m < N_SUMS + 3) {
-        const int q = m - N_SUMS;
-        row[m] = __longlong_as_double((long long)((cnt[0][q] + cnt[1][q]) + (cnt[2][q] + cnt[3][q])));
-    }
+    gn::write_partial_row<N_SUMS>(acc, n_valid, n_reached, n_used, red, cnt, rows + (size_t)blockIdx.x * ROW, gn::RowRotations());
 }
 
 struct Solve {
@@ -196,9 +156,9 @@ struct Solve {
     double damping;
 };
 
-// one workgroup of NT_SOLVE threads: group w of 64 lanes sums the rows w, w + GROUPS, ... of entry `lane` in order; the GROUPS partial
-// totals are added in order; thread 0 does the rest.  MODE_SUMS: the totals to out_sums [40] / out_counts [4].  MODE_STEP: history row
-// `it`, one Gauss-Newton step on the live state.  MODE_FINAL: history row `iterations`, the normal matrix, the revert test.
+// one workgroup of NT_SOLVE threads: the rows summed by gn::sum_rows; thread 0 does the rest.  gn::SUMS: the totals to out_sums [40] /
+// out_counts [4].  gn::STEP: history row `it`, one Gauss-Newton step on the live state.  gn::FINAL: history row `iterations`, the
+// normal matrix, the revert test.
 __global__ __launch_bounds__(NT_SOLVE) void k_register_solve(const double* __restrict__ rows, int nrows, int mode, Solve sv,
                                                               const double* __restrict__ init, double* __restrict__ live,
                                                               float* __restrict__ st32, const float* __restrict__ pivot,
@@ -209,33 +169,8 @@ __global__ __launch_bounds__(NT_SOLVE) void k_register_solve(const double* __res
     __shared__ double tot[ROW];
     __shared__ double A[7][7];                                   // the normal matrix, then its Cholesky factor (lower)
     __shared__ double xs[7];
-    const int grp = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (lane < N_SUMS + 3) {
-        const double* r = rows + lane;
-        if (lane < N_SUMS) {
-            double v = 0.0;
-            for (int c = grp; c < nrows; c += GROUPS) v += r[(size_t)c * ROW];
-            part[grp][lane] = v;
-        } else {
-            long long v = 0;
-            for (int c = grp; c < nrows; c += GROUPS) v += __double_as_longlong(r[(size_t)c * ROW]);
-            part[grp][lane] = __longlong_as_double(v);
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < N_SUMS) {
-        double v = part[0][threadIdx.x];
-#pragma unroll
-        for (int w = 1; w < GROUPS; ++w) v += part[w][threadIdx.x];
-        tot[threadIdx.x] = v;
-    } else if (threadIdx.x < N_SUMS + 3) {
-        long long v = 0;
-#pragma unroll
-        for (int w = 0; w < GROUPS; ++w) v += __double_as_longlong(part[w][threadIdx.x]);
-        tot[threadIdx.x] = (double)v;                            // a count is below 2^30: exact
-    }
-    __syncthreads();
-    if (mode == MODE_SUMS) {
+    gn::sum_rows<N_SUMS, ROW, GROUPS>(rows, nrows, false, part, tot);
+    if (mode == gn::SUMS) {
         if (threadIdx.x < OUT_SUMS) out_sums[threadIdx.x] = threadIdx.x < N_SUMS ? tot[threadIdx.x] : 0.0;
         if (threadIdx.x < 4) out_counts[threadIdx.x] = threadIdx.x < 3 ? (long long)tot[N_SUMS + threadIdx.x] : 0ll;
         return;
@@ -249,81 +184,36 @@ __global__ __launch_bounds__(NT_SOLVE) void k_register_solve(const double* __res
     h[2] = n_used;
     h[3] = tot[35];
     h[4] = tot[36];
-    if (mode == MODE_FINAL) {
+    if (mode == gn::FINAL) {
         int idx = 0;
         for (int k = 0; k < 7; ++k)
             for (int l = k; l < 7; ++l, ++idx) normal[k * 7 + l] = normal[l * 7 + k] = tot[idx];
     }
     int st = status[0];
-    if (st != ST_OK) return;                                     // frozen: the state is the initial one already
+    if (st != gn::OK) return;                                    // frozen: the state is the initial one already
 
     bool restore = false;
-    if (mode == MODE_FINAL) {
+    if (mode == gn::FINAL) {
         const double F1 = tot[35] / n_valid, F0 = history[3] / history[0];
         if (F1 > F0) {                                           // (NaN: no revert)
-            st = ST_REVERTED;
+            st = gn::REVERTED;
             restore = true;
         }
     } else if (n_used < (double)sv.min_pairs) {
-        st = ST_TOO_FEW;
+        st = gn::TOO_FEW;
         restore = true;
     } else {
         const int n = sv.unknowns == UNKNOWNS_SIM3 ? 7 : 6;
-        int idx = 0;
-        for (int k = 0; k < 7; ++k)
-            for (int l = k; l < 7; ++l, ++idx) A[k][l] = tot[idx];                 // upper: the matrix; the factor goes below
-        for (int k = 0; k < n; ++k) A[k][k] = A[k][k] + sv.damping * A[k][k];
-        bool pd = true;
-        for (int k = 0; k < n && pd; ++k) {
-            double q0 = A[k][k];
-            for (int m = 0; m < k; ++m) q0 -= A[k][m] * A[k][m];
-            if (!(q0 > 0.0)) { pd = false; break; }
-            const double lkk = sqrt(q0);
-            for (int r = k + 1; r < n; ++r) {
-                double q = A[k][r];
-                for (int m = 0; m < k; ++m) q -= A[r][m] * A[k][m];
-                A[r][k] = q / lkk;
-            }
-            A[k][k] = lkk;                                       // (the diagonal of the matrix is not read again)
-        }
-        if (!pd) {
-            st = ST_NOT_PD;
+        if (!gn::solve_damped<7>(A, xs, tot, n, sv.damping)) {
+            st = gn::NOT_PD;
             restore = true;
         } else {
-            for (int k = 0; k < n; ++k) {                        // L y = -g
-                double q = -tot[28 + k];
-                for (int m = 0; m < k; ++m) q -= A[k][m] * xs[m];
-                xs[k] = q / A[k][k];
-            }
-            for (int k = n - 1; k >= 0; --k) {                   // L^T x = y
-                double q = xs[k];
-                for (int m = k + 1; m < n; ++m) q -= A[m][k] * xs[m];
-                xs[k] = q / A[k][k];
-            }
             // R <- Exp(omega) R, t <- e^sigma Exp(omega) (t - c) + c + v, s <- e^sigma s
-            const double v0 = xs[0], v1 = xs[1], v2 = xs[2], w0 = xs[3], w1 = xs[4], w2 = xs[5];
-            const double th2 = (w0 * w0 + w1 * w1) + w2 * w2;
-            double ca, cb;
-            if (th2 < 1e-8) {
-                ca = 1.0 - th2 / 6.0;
-                cb = 0.5 - th2 / 24.0;
-            } else {
-                const double th = sqrt(th2);
-                ca = sin(th) / th;
-                cb = (1.0 - cos(th)) / th2;
-            }
-            const double Wm[3][3] = {{0.0, -w2, w1}, {w2, 0.0, -w0}, {-w1, w0, 0.0}};
             double Rx[3][3];
-#pragma unroll
-            for (int r = 0; r < 3; ++r)
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const double W2 = (Wm[r][0] * Wm[0][c] + Wm[r][1] * Wm[1][c]) + Wm[r][2] * Wm[2][c];
-                    Rx[r][c] = ((r == c ? 1.0 : 0.0) + ca * Wm[r][c]) + cb * W2;
-                }
+            gn::rot_exp(xs[3], xs[4], xs[5], Rx, nullptr);
             const double es = n == 7 ? exp(xs[6]) : 1.0;
             const double piv[3] = {(double)pivot[0], (double)pivot[1], (double)pivot[2]};
-            const double vv[3] = {v0, v1, v2};
+            const double vv[3] = {xs[0], xs[1], xs[2]};
             double Rn[9], tn[3];
             const double d[3] = {live[9] - piv[0], live[10] - piv[1], live[11] - piv[2]};
 #pragma unroll
@@ -425,7 +315,7 @@ extern "C" int colvo_register_accumulate(const float* source, int N, const float
     COLVO_CHECK_LAUNCH("k_register_init");
     if (int rc = launch_accum(a, md2, w, s)) return rc;
     Solve sv{};
-    colvo::launch(k_register_solve, dim3(1), dim3(NT_SOLVE), 0, s, (const double*)w.rows, blocks_of(N, PER_WG), (int)MODE_SUMS, sv,
+    colvo::launch(k_register_solve, dim3(1), dim3(NT_SOLVE), 0, s, (const double*)w.rows, blocks_of(N, PER_WG), gn::SUMS, sv,
                   (const double*)nullptr, (double*)nullptr, (float*)nullptr, pivot, (double*)nullptr, w.status, (double*)nullptr,
                   out_sums, reinterpret_cast<long long*>(out_counts));
     COLVO_CHECK_LAUNCH("k_register_solve");
@@ -441,9 +331,7 @@ extern "C" int colvo_register_clouds(const float* source, int N, const float* ta
     float md2;
     if (int rc = check_clouds("colvo_register_clouds", a, workspace, md2)) return rc;
     COLVO_CHECK_ARG(mode == UNKNOWNS_SE3 || mode == UNKNOWNS_SIM3, "colvo_register_clouds: bad mode %d (0 se3, 1 sim3)", mode);
-    COLVO_CHECK_ARG(iterations >= 1 && iterations <= 64, "colvo_register_clouds: bad iterations %d (1 .. 64)", iterations);
-    COLVO_CHECK_ARG(damping >= 0.0 && damping < (double)__builtin_inff() && min_pairs >= 1,
-                    "colvo_register_clouds: bad damping %g (finite, >= 0) or min_pairs %d (>= 1)", damping, min_pairs);
+    if (int rc = gn::check_loop("colvo_register_clouds", iterations, damping, "min_pairs", min_pairs)) return rc;
     COLVO_CHECK_ARG(out_state != state_init, "colvo_register_clouds: out_state must not alias state_init");
     hipStream_t s = (hipStream_t)stream;
     const Scratch w = carve(workspace, N);
@@ -458,7 +346,7 @@ extern "C" int colvo_register_clouds(const float* source, int N, const float* ta
         if (int rc = launch_accum(a, md2, w, s)) return rc;
         sv.it = it;
         colvo::launch(k_register_solve, dim3(1), dim3(NT_SOLVE), 0, s, (const double*)w.rows, blocks_of(N, PER_WG),
-                      (int)(it < iterations ? MODE_STEP : MODE_FINAL), sv, state_init, out_state, w.st32, pivot, history, status,
+                      it < iterations ? gn::STEP : gn::FINAL, sv, state_init, out_state, w.st32, pivot, history, status,
                       normal_matrix, (double*)nullptr, (long long*)nullptr);
         COLVO_CHECK_LAUNCH("k_register_solve");
     }

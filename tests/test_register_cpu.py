@@ -175,6 +175,21 @@ def test_register_entry_points_validate_their_arguments(lib):
     _refused(lib, acc(source=0, N=0, target=0, normals=0, M=0, max_dist=0.0), b"bad max_dist")
 
 
+def test_kernels_use_no_scratch(lib, tmp_path):
+    """The resource metadata of the four kernels (init, solve, and k_register_accum for each metric): no private segment, no spilled
+    register -- the 37 float64 accumulators of k_register_accum stay in registers."""
+    import re
+    from coivo_amd import build
+    asm = open(build.emit_asm("register.hip", str(tmp_path / "register.s"))).read()
+    kernels = set(re.findall(r"\.name:\s+(\S*k_register_\w+)", asm))
+    assert len(kernels) == 4 and all(any(f"k_register_{n}" in k for k in kernels) for n in ("init", "accum", "solve")), kernels
+    assert sum("k_register_accum" in k for k in kernels) == 2
+    for key in ("private_segment_fixed_size", "sgpr_spill_count", "vgpr_spill_count"):
+        vals = re.findall(rf"\.{key}:\s+(\d+)", asm)
+        assert len(vals) == 4 and all(int(v) == 0 for v in vals), (key, vals)
+    assert re.findall(r"\.agpr_count:\s+(\d+)", asm) in ([], ["0"] * 4)      # ... and are not parked in accumulation registers
+
+
 def test_python_wrappers_refuse_bad_arguments_before_any_native_call():
     from coivo_amd import evaluate as E
     assert E.Registration._fields == ("mode", "metric", "iterations", "max_dist", "damping", "min_pairs")
