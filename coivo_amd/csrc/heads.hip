@@ -488,6 +488,111 @@ __global__ __launch_bounds__(NT) void k_pose_head_bwd_det(const void* __restrict
     if (c < 8) db[c] += dbacc[c];
 }
 
+// The same sums with the loads side by side (tuning.h: pose_head_det_parallel).  The kernel above is one workgroup whose threads each
+// walk B x HW pixels with ONE load in flight: 48 dependent round trips at 8 images of 6 pixels, 24 us between the loss and PoseNet's
+// backward pass.  Here a workgroup owns PH_CS channels and thread (bl, cl) the pair (image b0 + bl, channel c0 + cl): the pixel
+// loads of different pairs are independent and a pair's own come PH_U at a time.  A pair parks its sum of x and its image's eight
+// gradients in LDS; thread (0, cl) then adds the images' terms to dw[.][c] / db with b ascending, group after group of PH_NB images
+// -- the order of the serial walk.  Bits: every rounding step of the kernel above is written out (its listing fuses go[j] * w[j]
+// into g and (go[j] * sx) * inv into dwacc[j], and nothing else), with contraction off so that none is added.
+constexpr int PH_CS = 32;                  // channels of a workgroup
+constexpr int PH_NB = NT / PH_CS;          // images of a group
+constexpr int PH_U = 8;                    // pixel loads a pair has in flight
+template <int ES>
+__global__ __launch_bounds__(NT) void k_pose_head_bwd_det_par(const void* __restrict__ x, const float* __restrict__ w,
+                                                              const float* __restrict__ d_pose, const float* __restrict__ d_a,
+                                                              const float* __restrict__ d_b, const float* __restrict__ sa,
+                                                              const float* __restrict__ sb, int B, int HW, int C, float pose_scale,
+                                                              float lcc_scale, void* __restrict__ dx, float* __restrict__ dw,
+                                                              float* __restrict__ db) {
+#pragma clang fp contract(off)
+    __shared__ float s_sx[PH_NB][PH_CS];
+    __shared__ float s_go[PH_NB][8];
+    const int cl = threadIdx.x % PH_CS, bl = threadIdx.x / PH_CS;
+    const int c = blockIdx.x * PH_CS + cl;
+    const bool owner = bl == 0 && c < C;                       // adds channel c's terms; c < 8: db[c] as well
+    const float gs = (sa ? sa[0] : 1.0f) * (sb ? sb[0] : 1.0f);
+    pose_scale = pose_scale * gs;
+    lcc_scale = lcc_scale * gs;
+    const float inv = 1.0f / (float)HW;
+    float wv[8], dw0[8], dwacc[8], dbacc[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        wv[j] = c < C ? w[j * C + c] : 0.0f;
+        dw0[j] = owner ? dw[j * C + c] : 0.0f;
+        dwacc[j] = 0.0f;
+        dbacc[j] = 0.0f;
+    }
+    const float db0 = owner && c < 8 ? db[c] : 0.0f;
+    for (int b0 = 0; b0 < B; b0 += PH_NB) {
+        const int b = b0 + bl;
+        if (b < B) {
+            float go[8];                                       // (the loads first, side by side; then the products)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) go[j] = 0.0f;
+            if (d_pose) {
+#pragma unroll
+                for (int j = 0; j < 6; ++j) go[j] = d_pose[(size_t)b * 6 + j];
+            }
+            if (d_a) go[6] = d_a[b];
+            if (d_b) go[7] = d_b[b];
+#pragma unroll
+            for (int j = 0; j < 6; ++j) go[j] = d_pose ? go[j] * pose_scale : 0.0f;
+            go[6] = d_a ? go[6] * lcc_scale : 0.0f;
+            go[7] = d_b ? go[7] * lcc_scale : 0.0f;
+            if (cl == 0) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) s_go[bl][j] = go[j];
+            }
+            if (c < C) {
+                float g = __builtin_fmaf(go[0], wv[0], 0.0f);
+#pragma unroll
+                for (int j = 1; j < 8; ++j) g = __builtin_fmaf(go[j], wv[j], g);
+                g = g * inv;
+                float sx = 0.0f;
+                for (int p0 = 0; p0 < HW; p0 += PH_U) {
+                    const size_t o = ((size_t)b * HW + p0) * C + c;
+                    float xv[PH_U];
+#pragma unroll
+                    for (int u = 0; u < PH_U; ++u) xv[u] = Elem<ES>::ld(x, o + (size_t)min(u, HW - 1 - p0) * C);   // past the end: the last pixel again, unused
+#pragma unroll
+                    for (int u = 0; u < PH_U; ++u) {
+                        const bool in = p0 + u < HW;
+                        const float gv = xv[u] > 0.0f ? g : 0.0f;
+                        sx = in ? sx + xv[u] : sx;                 // (a select: a load used only under a branch sinks into it)
+                        if (in) Elem<ES>::st(dx, o + (size_t)u * C, gv);
+                    }
+                }
+                s_sx[bl][cl] = sx;
+            }
+        }
+        __syncthreads();
+        if (owner) {
+            const int nb = min(PH_NB, B - b0);
+            for (int i = 0; i < nb; ++i) {
+                const float sx = s_sx[i][cl];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const float go = s_go[i][j];
+                    dbacc[j] = dbacc[j] + go;
+                    dwacc[j] = __builtin_fmaf(inv, go * sx, dwacc[j]);
+                }
+            }
+        }
+        __syncthreads();
+    }
+    if (owner) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) dw[j * C + c] = dwacc[j] + dw0[j];
+        if (c < 8) {
+            float t = dbacc[0];
+#pragma unroll
+            for (int j = 1; j < 8; ++j) t = c == j ? dbacc[j] : t;
+            db[c] = t + db0;
+        }
+    }
+}
+
 inline bool head_dgrad_generic() { return TUNE(head_dgrad_generic) != 0; }   // A/B switch
 
 }  // namespace
@@ -657,9 +762,12 @@ extern "C" int colvo_pose_head_bwd_det(int dtype, const void* x, const float* w,
                                        const float* d_b, const float* scale_a, const float* scale_b, int B, int HW, int C,
                                        float pose_scale, float lcc_scale, void* dx, float* dw, float* db, colvo_stream_t stream) {
     COLVO_CHECK_ARG(x && w && dx && dw && db && B >= 1 && HW >= 1 && C >= 8, "colvo_pose_head_bwd_det: bad arguments");
+    const bool par = TUNE(pose_head_det_parallel) != 0;
     COLVO_DISPATCH_ES(dtype, "colvo_pose_head_bwd_det",
-                      colvo::launch((k_pose_head_bwd_det<ES>), dim3((C + NT - 1) / NT), dim3(NT), 0, (hipStream_t)stream, x, w,
-                                    d_pose, d_a, d_b, scale_a, scale_b, B, HW, C, pose_scale, lcc_scale, dx, dw, db));
+                      if (par) colvo::launch((k_pose_head_bwd_det_par<ES>), dim3((C + PH_CS - 1) / PH_CS), dim3(NT), 0, (hipStream_t)stream,
+                                             x, w, d_pose, d_a, d_b, scale_a, scale_b, B, HW, C, pose_scale, lcc_scale, dx, dw, db);
+                      else colvo::launch((k_pose_head_bwd_det<ES>), dim3((C + NT - 1) / NT), dim3(NT), 0, (hipStream_t)stream, x, w,
+                                         d_pose, d_a, d_b, scale_a, scale_b, B, HW, C, pose_scale, lcc_scale, dx, dw, db));
     COLVO_CHECK_LAUNCH("k_pose_head_bwd_det");
     return 0;
 }

@@ -90,6 +90,15 @@ namespace tune {
     X(wgrad_teams, 4, "pixel-tile teams per workgroup on the full-resolution layers (1 = off)")                                     \
     X(wgrad_team_max_slabs, 2, "... for layers with at most this many (co tile, chunk) slabs")                                      \
     X(wgrad_team_wgs, 256, "... grid size of the team form")                                                                        \
+    X(wgrad_reduce_staged, 0, "second launch of the deterministic form as k_wgrad_reduce_staged: a workgroup fetches every split's row of a "  \
+                              "run of elements with all loads in flight and parks the values in LDS, one thread per float4 adds them in "    \
+                              "split order (the bits of k_wgrad_reduce, eight loads at a time).  OFF: 7.4 -> 6.6 us a launch alone in the "   \
+                              "listing, but the step is level at 8 pairs (1.4071-1.4175 ms against 1.4059-1.4099) and 1.0 % SLOWER at 64 "    \
+                              "(3.5369-3.5518 against 3.5100-3.5263): profiles/det_second_launch_ab.md")                                       \
+    X(wgrad_reduce_staged_min, 9, "... when on, from this many splits on: up to eight, k_wgrad_reduce is a single round of loads already "    \
+                                  "(with every layer staged the 590 K-element layers went 4.0-5.2 -> 4.2-5.3 us a launch at 16 frames)")        \
+    X(wgrad_reduce_chunk, 128, "... splits staged at a time (1..256; 32 KB of LDS hold chunk x run); more splits carry the sum from chunk "  \
+                               "to chunk in the same order")                                                                              \
     X(bwd16, 1, "input + weight gradient of the 16 -> 16 full-resolution layer in one pass (k_bwd16, csrc/bwd16.hip)")                \
     X(bwd16_wgs, 768, "... its grid: every workgroup ends with 2320 atomics on the same addresses")                                  \
     X(head_wgrad_wgs, 1024, "grid of k_head_wgrad_mfma (one partial row per workgroup)") \
@@ -102,6 +111,10 @@ namespace tune {
     X(head_wgrad_rows, 1, "tap rows per thread of the depth-head weight gradient (1: three workgroups per pixel range)")            \
     X(head_fwd_lds, 1, "depth-head forward stages its tile in LDS (24.7 -> 18.5 us)")                                               \
     X(head_dgrad_generic, 0, "depth-head input gradient: generic form instead of the 16-channel granule form")                      \
+    X(pose_head_det_parallel, 1, "deterministic PoseNet head backward with threads over (image, channel) pairs and 32-channel workgroups "  \
+                                 "(k_pose_head_bwd_det_par); 0: one thread per channel walks every image and pixel, one load in flight "  \
+                                 "(same bits; 20.9 -> 7.9 us at 8 pairs, step -1.0 % at 8 pairs and -0.4 % at 64: "                       \
+                                 "profiles/det_second_launch_ab.md)")                                                                     \
     X(march_rows_fwd, 0, "rows per strip segment of the fused-loss forward march (0: chosen to fill the wave slots in whole rounds)") \
     X(march_rows_bwd, 0, "... of the one-pass loss + gradient march")                                                               \
     X(fork_stop_event, 1, "a FORK waits on the producing kernel's own completion (hipExtLaunchKernel stopEvent) instead of a recorded marker") \

@@ -486,6 +486,63 @@ __global__ __launch_bounds__(NT) void k_wgrad_reduce(const float* __restrict__ s
     else reduce_slabs(bslabs, nsplit, nb, bdst, (size_t)(blockIdx.x - wblocks) * NT + threadIdx.x, (size_t)(gridDim.x - wblocks) * NT);
 }
 
+// The same sums with every split's load in flight at once (tuning.h: wgrad_reduce_staged).  k_wgrad_reduce above is a chain of
+// ceil(nsplit / 8) dependent round trips per element; here a workgroup takes a run of 2^lc vectors of V floats, its threads fetch the
+// rows [split][vector] of that run -- up to RS_K loads a thread, none waiting for another -- and park the VALUES in LDS in the same
+// [split][vector] order; thread c of the first 2^lc then adds its column with the split ascending: t = 0, t += slab[q][i], dst[i] += t,
+// the adds of k_wgrad_reduce in its order, so the bits are its bits.  More than `chunk` splits: the same t goes on from chunk to chunk.
+// The host sizes a run so that rows x vectors <= RS_ITEMS (reduce_run_lc): no thread sees a second element.
+constexpr int RS_K = 8;                    // loads a thread has in flight
+constexpr int RS_ITEMS = RS_K * NT;        // vectors staged at a time: 32 KB of LDS at V = 4
+struct ReducePart {
+    const float* slabs;
+    float* dst;
+    size_t n;                 // elements of the tensor = floats between two splits' rows
+    int lc;                   // a workgroup's run: 2^lc vectors
+    int vec;                  // 16-byte vectors (n % 4 == 0, slabs and dst 16-byte aligned), else single floats
+};
+template <int V> struct RVec { typedef f32x4 type; };
+template <> struct RVec<1> { typedef float type; };
+template <int V>
+__device__ __forceinline__ void reduce_staged(const ReducePart p, int nsplit, int chunk, unsigned blk, float* lds) {
+    typedef typename RVec<V>::type vec_t;
+    const int tid = threadIdx.x, cols = 1 << p.lc;
+    const size_t nv = p.n / V, v0 = (size_t)blk << p.lc;            // vectors of the tensor, first vector of this run
+    const vec_t* src = reinterpret_cast<const vec_t*>(p.slabs);
+    vec_t* out = reinterpret_cast<vec_t*>(p.dst);
+    vec_t* stage = reinterpret_cast<vec_t*>(lds);
+    const bool adder = tid < cols && v0 + tid < nv;
+    vec_t d = vec_t(0.0f), t = vec_t(0.0f);
+    for (int q0 = 0; q0 < nsplit; q0 += chunk) {
+        const int rows = min(chunk, nsplit - q0), total = rows << p.lc;          // <= RS_ITEMS
+        vec_t v[RS_K];
+#pragma unroll
+        for (int k = 0; k < RS_K; ++k) {
+            const int idx = tid + k * NT, r = idx >> p.lc, c = idx & (cols - 1);
+            v[k] = idx < total && v0 + c < nv ? src[(size_t)(q0 + r) * nv + v0 + c] : vec_t(0.0f);
+        }
+        if (q0 == 0 && adder) d = out[v0 + tid];                                 // dst rides with the first chunk's loads
+        if (q0) __syncthreads();                                                 // the adders have read the chunk before
+#pragma unroll
+        for (int k = 0; k < RS_K; ++k) {
+            const int idx = tid + k * NT;
+            if (idx < total) stage[idx] = v[k];
+        }
+        __syncthreads();
+        if (adder)
+            for (int r = 0; r < rows; ++r) t += stage[(r << p.lc) + tid];
+    }
+    if (adder) out[v0 + tid] = d + t;
+}
+__global__ __launch_bounds__(NT) void k_wgrad_reduce_staged(const ReducePart wp, const ReducePart bp, int nsplit, int chunk, unsigned wblocks) {
+    __shared__ __attribute__((aligned(16))) float lds[RS_ITEMS * 4];
+    const bool bias = blockIdx.x >= wblocks;
+    const ReducePart p = bias ? bp : wp;
+    const unsigned blk = bias ? blockIdx.x - wblocks : blockIdx.x;
+    if (p.vec) reduce_staged<4>(p, nsplit, chunk, blk, lds);
+    else reduce_staged<1>(p, nsplit, chunk, blk, lds);
+}
+
 // ---- grouped second launch (colvo_wgrad_reduce_group): dst += slabs[0] + slabs[1] + ... for up to 2 x COLVO_WGRAD_GROUP_MAX tensors ----
 // One entry per tensor (a layer's weights, a layer's bias).  An entry's work is cut into float4 columns x SP split partitions:
 // thread (s, q) of a block loads the float4 column q of the splits s, s + SP, s + 2 SP, ... (at most 8: all in flight), the SP
@@ -627,7 +684,29 @@ inline int wgrad_resolve(const WgradRequest& r, int Cout, int nsplit, WgradSink&
 }
 
 // the second launch of a launch into slabs that are not left to the caller
+// one tensor of the staged form: vector width, run length and its workgroups.  A run is a power of two of vectors: at most NT (one
+// adder thread each), at most what RS_ITEMS hold of `rows` splits, at least 8 (128-byte rows), and in between short enough that a
+// small tensor still spreads over ~512 workgroups.
+inline ReducePart reduce_part(const float* slabs, float* dst, size_t n, int rows, unsigned& blocks) {
+    ReducePart p{slabs, dst, n, 3, n % 4 == 0 && ((uintptr_t)slabs | (uintptr_t)dst) % 16 == 0};
+    const size_t nv = p.vec ? n / 4 : n;
+    while (p.lc < 8 && (rows << (p.lc + 1)) <= RS_ITEMS && ((size_t)512 << p.lc) < nv) ++p.lc;
+    blocks = (unsigned)((nv + ((size_t)1 << p.lc) - 1) >> p.lc);
+    return p;
+}
+inline int wgrad_reduce_staged(const WgradSink& o, int Cout, int nsplit, hipStream_t s) {
+    const int chunk = (int)std::min<long>(std::max<long>(TUNE(wgrad_reduce_chunk), 1), RS_ITEMS / 8);
+    const int rows = std::min(nsplit, chunk);
+    unsigned blocks = 0, bblocks = 0;
+    const ReducePart wp = reduce_part(o.slabs, o.dw, (size_t)Cout * 9 * o.Ctot, rows, blocks);
+    ReducePart bp{nullptr, nullptr, 0, 3, 0};
+    if (o.bias) bp = reduce_part(o.db_slabs, o.db, (size_t)Cout, rows, bblocks);
+    colvo::launch(k_wgrad_reduce_staged, dim3(blocks + bblocks), dim3(NT), 0, s, wp, bp, nsplit, chunk, blocks);
+    COLVO_CHECK_LAUNCH("k_wgrad_reduce_staged");
+    return 0;
+}
 inline int wgrad_reduce(const WgradSink& o, int Cout, int nsplit, hipStream_t s) {
+    if (TUNE(wgrad_reduce_staged) && nsplit >= TUNE(wgrad_reduce_staged_min)) return wgrad_reduce_staged(o, Cout, nsplit, s);
     const size_t wsize = (size_t)Cout * 9 * o.Ctot;
     const unsigned blocks = (unsigned)std::min<size_t>((wsize + NT - 1) / NT, 2048);
     const unsigned bblocks = o.bias ? (unsigned)((Cout + NT - 1) / NT) : 0;
