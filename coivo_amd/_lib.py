@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("COLVO_LIB_PATH") or os.path.join(_HERE, "lib", "libcolvo.so")
 
 F32, BF16 = 0, 1
-ABI_VERSION = 22
+ABI_VERSION = 23
 
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 
@@ -135,6 +135,13 @@ SIGNATURES = {
     "colvo_fuse_write": (_i, [_vp, _vp, _i, _i] + [_f] * 4 + [_i] * 3 + [_vp, _i] + [_vp] * 5),
     "colvo_cloud_normals_scratch_bytes": (_sz, [_i]),
     "colvo_cloud_normals": (_i, [_vp] * 3 + [_i] * 4 + [_f] * 5 + [_i] * 3 + [_vp, _i, _f] + [_vp] * 6),
+    "colvo_tsdf_plan_scratch_bytes": (_sz, [_i] * 7),
+    "colvo_tsdf_plan": (_i, [_vp] * 3 + [_i] * 4 + [_f] * 5 + [_i] * 4 + [_vp] * 5),
+    "colvo_tsdf_integrate": (_i, [_vp] * 4 + [_i] * 3 + [_f] * 5 + [_i] * 4 + [_vp, _i] + [_vp] * 4),
+    "colvo_tsdf_mesh_scratch_bytes": (_sz, [_i]),
+    "colvo_tsdf_mesh_count": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "colvo_tsdf_mesh_vertices": (_i, [_vp] * 4 + [_i, _i] + [_f] * 4 + [_i] * 3 + [_vp, _i] + [_vp] * 7),
+    "colvo_tsdf_mesh_faces": (_i, [_vp, _vp, _vp] + [_i] * 4 + [_vp, _vp, _i, _vp, _vp]),
     "colvo_localize_workspace_bytes": (_sz, [_i, _i]),
     "colvo_localize_accumulate": (_i, [_vp] * 3 + [_i] * 4 + [_f, _i, _vp, _vp, _vp]),
     "colvo_localize_bounds": (_i, [_vp, _i, _i, _f, _vp, _vp]),

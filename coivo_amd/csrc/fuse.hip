@@ -35,10 +35,6 @@ struct Record {
 };
 static_assert(sizeof(Record) == 32, "Record is 32 B");
 
-__device__ __forceinline__ uint32_t colour_quantum(float c) {
-    return (uint32_t)fminf(fmaxf(rintf(c * 255.0f), 0.0f), 255.0f);       // fmaxf(NaN, 0) = 0
-}
-
 // grid (blocks_per_frame, N).  The two sample counts are summed per workgroup and added to one of COUNTER_LINES pairs, each in a
 // 64-byte line of its own (every wave adding to ONE address measured 7 ms for 42 M samples: 1.3 M adds queue up behind each other)
 __global__ __launch_bounds__(NT) void k_fuse_mark(const float* __restrict__ depth, const float* __restrict__ K,

@@ -137,7 +137,11 @@ namespace tune {
     X(render_load_first, 1, "a splat reads a pixel's key before its 64-bit atomic minimum and skips the atomic when the stored key is "  \
                             "already <= its own (keys only decrease: a stale read costs an atomic, never skips a needed one).  The "   \
                             "result does not depend on it.  543 031 points into 512 views of 256x320, whole call, alternating call by "  \
-                            "call: 0 -> 10881.4 us, 1 -> 6122.5 (tools/bench_render.py)")
+                            "call: 0 -> 10881.4 us, 1 -> 6122.5 (tools/bench_render.py)")                                               \
+    /* ---- TSDF fusion (tsdf.hip) ---- */                                                                                           \
+    X(tsdf_cull, 1, "k_tsdf_integrate tests the frames 64 at a time against the brick (depth slab and image rectangle, conservative) "  \
+                    "and walks only the survivors; 0: every brick walks every frame.  Integer sums: the result does not depend on it "  \
+                    "(tests/test_tsdf_gpu.py compares the bits; times: tools/bench_tsdf.py, DESIGN.md 3.6m)")
 
 struct Table {
 #define X(name, dflt, doc) double name = dflt;

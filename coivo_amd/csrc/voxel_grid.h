@@ -1,5 +1,5 @@
 // voxel_grid.h -- the voxel grid of the fusion and the walk over the samples of a set of depth maps, shared by
-// fuse.hip and normals.hip so that both place a sample in its voxel with the very same routine: `locate` below is PINNED -- float32,
+// fuse.hip, normals.hip and tsdf.hip so that all place a sample in its voxel with the very same routine: `locate` below is PINNED -- float32,
 // every operation individually rounded, in the order written -- against tests/fuse_ref.py.  A file that includes this header must
 // have contraction off (`#pragma clang fp contract(off)` in front of the include); the pragma below repeats it, and since a file-scope
 // pragma holds to the end of the translation unit, everything behind the include is compiled without contraction as well.
@@ -62,6 +62,11 @@ __device__ __forceinline__ bool locate(const Cam& c, const Grid& G, float u, flo
     vx.brick = (bz * G.nb[1] + by) * G.nb[0] + bx;
     vx.local = ((idx[2] & 7) * BRICK + (idx[1] & 7)) * BRICK + (idx[0] & 7);
     return inside;
+}
+
+// a colour in [0, 1] as one of 256 quanta, summed as an integer by fuse.hip and tsdf.hip
+__device__ __forceinline__ uint32_t colour_quantum(float c) {
+    return (uint32_t)fminf(fmaxf(rintf(c * 255.0f), 0.0f), 255.0f);       // fmaxf(NaN, 0) = 0
 }
 
 // ---- host side: geometry ---------------------------------------------------------------------------------------------------- //

@@ -214,6 +214,167 @@ def fuse_point_cloud(depths: torch.Tensor, K: torch.Tensor, cam2world: torch.Ten
     return FusedCloud(points, out_colors, counts, voxels, origin, dims, vs, n_input, n_outside, n_bricks, n_voxels)
 
 
+class TsdfVolume(NamedTuple):
+    pool: torch.Tensor              # [n_bricks*512, 2] int32: (sum q, n) per voxel, row slot * 512 + (lz * 8 + ly) * 8 + lx
+    color_sums: Optional[torch.Tensor]   # [n_bricks*512, 4] int32: sums of the colour quanta (r, g, b, 0); None without colours
+    brick_list: torch.Tensor        # [n_bricks] int32: the allocated bricks, ascending (bz * nby + by) * nbx + bx
+    table: torch.Tensor             # [bricks of the grid] int32: slot of each brick, -1 where not allocated
+    origin: Tuple[float, float, float]   # lower corner of the grid (float32 values)
+    dims: Tuple[int, int, int]      # voxels per axis
+    voxel_size: float               # as float32
+    trunc: float                    # truncation distance, a whole number of voxels (as float32)
+    has_colors: bool
+    n_input: int                    # walked samples with 0 < depth < max_depth
+    n_outside: int                  # ... of which outside the grid
+    n_bricks: int                   # allocated 8x8x8 bricks
+
+
+class Mesh(NamedTuple):
+    vertices: torch.Tensor          # [V,3] float32: one per active cell, in (brick, voxel in brick) order of the cell's minimum corner
+    faces: torch.Tensor             # [F,3] int32: triangles, wound so that the normal points to free space (the camera side)
+    colors: Optional[torch.Tensor]  # [V,3] float32 in [0,1] (None without colours)
+    normals: torch.Tensor           # [V,3] float32: unit gradient of the distance field, towards free space; 0 for a zero gradient
+    cells: torch.Tensor             # [V,3] int32: the cell (ix, iy, iz) of each vertex
+    n_open: int                     # cells with a sign change among their observed corners and one or more corners not observed
+
+
+class Meshing(NamedTuple):
+    """reconstruct_sequence's meshing policy: fuse_tsdf's trunc and extract_mesh's min_obs.  The defaults are choices, not tuned
+    values."""
+    trunc: Optional[float] = None   # None: four voxels
+    min_obs: int = 2
+
+
+def _tsdf_voxels(who: str, voxel_size, trunc):
+    """(voxel_size as float32, T): trunc must be a whole number T of voxels, 1 <= T <= 7; None is four voxels."""
+    vs = _f32(voxel_size)
+    if not (vs > 0.0 and math.isfinite(vs)):
+        raise ValueError(f"{who}: voxel_size must be finite and positive")
+    if trunc is None:
+        return vs, 4
+    if isinstance(trunc, bool) or not isinstance(trunc, (int, float)) or not math.isfinite(trunc) or not trunc > 0.0:
+        raise ValueError(f"{who}: trunc must be a whole number of voxels, 1 to 7 of them (or None: four), got {trunc!r}")
+    T = int(round(float(trunc) / vs))
+    if not 1 <= T <= 7 or abs(float(trunc) - T * vs) > 1e-5 * float(trunc):
+        raise ValueError(f"{who}: trunc must be a whole number of voxels, 1 to 7 of them (a band of T + 1 voxels never skips an "
+                         f"8-voxel brick), got {trunc!r} = {float(trunc) / vs:.6g} voxels of {vs}")
+    return vs, T
+
+
+def fuse_tsdf(depths: torch.Tensor, K: torch.Tensor, cam2world: torch.Tensor, *, voxel_size: float, trunc: Optional[float] = None,
+              colors: Optional[torch.Tensor] = None, stride: int = 1, max_depth: float = MAX_DEPTH, origin=None,
+              dims=None) -> TsdfVolume:
+    """Depth maps along a trajectory -> a truncated signed distance volume over fuse_point_cloud's grid (contract: include/colvo.h
+    colvo_tsdf_*; csrc/tsdf.hip).  Every `stride`-th pixel with 0 < depth < max_depth allocates the 8x8x8 bricks
+    within trunc + one voxel of its surface point along its ray; every voxel of an allocated brick then looks itself up in every
+    frame's full-resolution depth map and adds the quantised, truncated distance d - z (in units of trunc / 4096) and a count, and
+    with colors [N,3,H,W] the pixel's colour.  A voxel in front of the surface by more than trunc votes +1: frames that look through
+    a floater outvote it.  A voxel behind the surface by more than trunc is not observed by that frame.  `trunc` must be a whole
+    number of voxels, 1 to 7; None is four -- a choice, not a tuned value.  Integer sums: the volume is bit-identical between calls,
+    streams and frame orders and equals the NumPy replica tests/tsdf_ref.py.  origin / dims default to fusion_grid's.  Reads one
+    12-byte statistics block back after the plan to size the pool.  Not incremental: a call builds a volume from all its frames."""
+    who = "fuse_tsdf"
+    lib = _lib.load()
+    if not isinstance(depths, torch.Tensor) or depths.dim() != 4:
+        raise ValueError(f"{who}: depths must be [N,1,H,W]")
+    N, _, H, W = depths.shape
+    if isinstance(stride, bool) or not isinstance(stride, int) or stride < 1:
+        raise ValueError(f"{who}: stride must be an int >= 1, got {stride!r}")
+    if not _finite_pos32(max_depth):
+        raise ValueError(f"{who}: max_depth must be finite and positive (as float32), got {max_depth!r}")
+    vs, T = _tsdf_voxels(who, voxel_size, trunc)
+    depths = _chk(depths, "depths", (N, 1, H, W))
+    K = _chk(K, "K", (N, 3, 3))
+    cam2world = _chk(cam2world, "cam2world", (N, 4, 4))
+    if colors is not None:
+        colors = _chk(colors, "colors", (N, 3, H, W))
+    if (origin is None) != (dims is None):
+        raise ValueError(f"{who}: give origin and dims together, or neither")
+    if origin is None:
+        origin, dims = fusion_grid(K, cam2world, H, W, vs, max_depth)
+    origin = tuple(_f32(o) for o in origin)
+    dims = tuple(int(d) for d in dims)
+    if len(origin) != 3 or len(dims) != 3 or any(d <= 0 or d % 8 for d in dims):
+        raise ValueError(f"{who}: dims must be three positive multiples of 8, got {dims}")
+    scratch_bytes = int(lib.colvo_tsdf_plan_scratch_bytes(N, H, W, stride, *dims))
+    if scratch_bytes == 0:
+        raise ValueError(f"{who}: shape N={N} H={H} W={W} stride={stride} or grid {dims} beyond the kernels' limits")
+    dev = depths.device
+    total = (dims[0] // 8) * (dims[1] // 8) * (dims[2] // 8)
+    scratch = torch.empty(scratch_bytes, device=dev, dtype=torch.uint8)
+    table = torch.empty(total, device=dev, dtype=torch.int32)
+    brick_list = torch.empty(min(total, 1 << 22), device=dev, dtype=torch.int32)
+    stats = torch.empty(3, device=dev, dtype=torch.int32)
+    stream = _lib.stream_ptr()
+    _lib.check(lib.colvo_tsdf_plan(_lib.ptr(depths), _lib.ptr(K), _lib.ptr(cam2world), N, H, W, stride, float(max_depth), *origin, vs,
+                                   *dims, T, _lib.ptr(scratch), _lib.ptr(table), _lib.ptr(brick_list), _lib.ptr(stats), stream),
+               "colvo_tsdf_plan")
+    n_input, n_outside, n_bricks = (int(v) for v in stats.tolist())
+    if n_bricks >= 1 << 22:
+        raise RuntimeError(f"{who}: {n_bricks} allocated bricks, the limit is 2^22 - 1: use a larger voxel_size")
+    pool = torch.empty(n_bricks * 512, 2, device=dev, dtype=torch.int32)
+    sums = torch.empty(n_bricks * 512, 4, device=dev, dtype=torch.int32) if colors is not None else None
+    if n_bricks > 0:
+        _lib.check(lib.colvo_tsdf_integrate(_lib.ptr(depths), _lib.ptr(colors), _lib.ptr(K), _lib.ptr(cam2world), N, H, W,
+                                            float(max_depth), *origin, vs, *dims, T, _lib.ptr(brick_list), n_bricks, _lib.ptr(pool),
+                                            _lib.ptr(sums), 0, stream), "colvo_tsdf_integrate")
+    return TsdfVolume(pool, sums, brick_list[:n_bricks], table, origin, dims, vs, _f32(_f32(T) * vs), colors is not None, n_input,
+                      n_outside, n_bricks)
+
+
+def extract_mesh(volume: TsdfVolume, *, min_obs: int = 1) -> Mesh:
+    """The zero surface of a TsdfVolume as an indexed triangle mesh by surface nets (contract: include/colvo.h colvo_tsdf_mesh_*,
+    DESIGN.md §3.6m).  A voxel counts as observed with at least `min_obs` observations and as inside iff its integer sum is negative,
+    so the topology never depends on a rounding.  A cell of 2x2x2 voxels that are all observed and of mixed sign gets one vertex --
+    the mean of the sign changes along its edges --, a colour and a normal (the field's gradient, towards free space); a grid edge
+    with a sign change and four such cells around it gets one quad, written as two triangles wound towards free space.  Vertices are
+    shared by construction.  `n_open` counts the cells that would have had a vertex but for a corner that is not observed: what the
+    band's edge and min_obs cost.  Every output bit is a function of the volume alone and equals tests/tsdf_ref.py.  A mesh's
+    vertices are a cloud: evaluate.cloud_metrics(mesh.vertices, gt_points, ...) scores it.  Reads two small counts back (vertices,
+    then triangles) to size the outputs.  No hole filling, no simplification."""
+    who = "extract_mesh"
+    if not isinstance(volume, TsdfVolume):
+        raise ValueError(f"{who}: volume must be a TsdfVolume")
+    if isinstance(min_obs, bool) or not isinstance(min_obs, int) or min_obs < 1:
+        raise ValueError(f"{who}: min_obs must be an int >= 1, got {min_obs!r}")
+    lib = _lib.load()
+    dev = volume.table.device
+    n_bricks = int(volume.n_bricks)
+    origin = tuple(_f32(o) for o in volume.origin)
+    dims = tuple(int(d) for d in volume.dims)
+    vs = _f32(volume.voxel_size)
+    V = F = n_open = 0
+    stream = _lib.stream_ptr()
+    if n_bricks > 0:
+        if tuple(volume.pool.shape) != (n_bricks * 512, 2) or volume.pool.dtype != torch.int32 or not volume.pool.is_contiguous():
+            raise ValueError(f"{who}: volume.pool must be a contiguous [n_bricks*512, 2] int32 tensor")
+        scratch_bytes = int(lib.colvo_tsdf_mesh_scratch_bytes(n_bricks))
+        if scratch_bytes == 0:
+            raise ValueError(f"{who}: n_bricks {n_bricks} beyond the kernels' limits")
+        scratch = torch.empty(scratch_bytes, device=dev, dtype=torch.uint8)
+        stats2 = torch.empty(3, device=dev, dtype=torch.int32)
+        bricks = (_lib.ptr(volume.table), _lib.ptr(volume.brick_list), n_bricks)
+        _lib.check(lib.colvo_tsdf_mesh_count(_lib.ptr(volume.pool), *bricks, min_obs, *dims, _lib.ptr(scratch), _lib.ptr(stats2),
+                                             stream), "colvo_tsdf_mesh_count")
+        V, n_open = (int(v) for v in stats2[:2].tolist())
+    vertices = torch.empty(V, 3, device=dev, dtype=torch.float32)
+    normals = torch.empty(V, 3, device=dev, dtype=torch.float32)
+    colors = torch.empty(V, 3, device=dev, dtype=torch.float32) if volume.color_sums is not None else None
+    cells = torch.empty(V, 3, device=dev, dtype=torch.int32)
+    if V > 0:
+        vid = torch.empty(n_bricks * 512, device=dev, dtype=torch.int32)
+        _lib.check(lib.colvo_tsdf_mesh_vertices(_lib.ptr(volume.pool), _lib.ptr(volume.color_sums), *bricks, min_obs, *origin, vs,
+                                                *dims, _lib.ptr(scratch), V, _lib.ptr(vertices), _lib.ptr(colors), _lib.ptr(normals),
+                                                _lib.ptr(cells), _lib.ptr(vid), stats2[2:].data_ptr(), stream),
+                   "colvo_tsdf_mesh_vertices")
+        F = int(stats2[2].item())
+    faces = torch.empty(F, 3, device=dev, dtype=torch.int32)
+    if F > 0:
+        _lib.check(lib.colvo_tsdf_mesh_faces(_lib.ptr(volume.pool), *bricks, *dims, _lib.ptr(scratch), _lib.ptr(vid), F,
+                                             _lib.ptr(faces), stream), "colvo_tsdf_mesh_faces")
+    return Mesh(vertices, faces, colors, normals, cells, n_open)
+
+
 class CloudNormals(NamedTuple):
     normals: torch.Tensor           # [M,3] float32: unit normal of each row of the cloud in the world frame, facing the cameras; 0 without one
     counts: torch.Tensor            # [M]   int32: samples that gave the row a normal
@@ -702,13 +863,21 @@ def render_fused(fused: FusedCloud, K: torch.Tensor, cam2world: torch.Tensor, H:
                           max_depth=max_depth, want_normals=want_normals)
 
 
-def write_ply(path, points: torch.Tensor, colors: Optional[torch.Tensor] = None, normals: Optional[torch.Tensor] = None) -> None:
+def write_ply(path, points: torch.Tensor, colors: Optional[torch.Tensor] = None, normals: Optional[torch.Tensor] = None,
+              faces: Optional[torch.Tensor] = None) -> None:
     """Binary little-endian PLY: `float x y z` per vertex, with normals [M,3] `float nx ny nz` behind them (viewers shade by them)
-    and, with colours [M,3] in [0,1], `uchar red green blue` (rint(c * 255), clamped).  Without normals the bytes are what they were
-    before normals existed.  Host code; one device -> host copy."""
+    and, with colours [M,3] in [0,1], `uchar red green blue` (rint(c * 255), clamped).  With faces [F,3] (integer vertex indices, a
+    Mesh's `faces`) an `element face F` with `property list uchar int vertex_indices` follows the vertices.  Without normals and
+    without faces the bytes are what they were before either existed.  Host code; one device -> host copy (two with faces)."""
     import numpy as np
     if points.dim() != 2 or points.shape[1] != 3:
         raise ValueError("write_ply: points must be [M,3]")
+    if faces is not None:
+        if (not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.shape[1] != 3 or faces.is_floating_point()
+                or faces.dtype == torch.bool):
+            raise ValueError("write_ply: faces must be an integer tensor [F,3]")
+        if faces.numel() and (int(faces.min()) < 0 or int(faces.max()) >= points.shape[0]):
+            raise ValueError("write_ply: faces index vertices that do not exist")
     if colors is not None and tuple(colors.shape) != tuple(points.shape):
         raise ValueError("write_ply: colors must have the shape of points")
     if normals is not None and (not isinstance(normals, torch.Tensor) or tuple(normals.shape) != tuple(points.shape)):
@@ -729,6 +898,8 @@ def write_ply(path, points: torch.Tensor, colors: Optional[torch.Tensor] = None,
     if colors is not None:
         fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
         header += ["property uchar red", "property uchar green", "property uchar blue"]
+    if faces is not None:
+        header += [f"element face {faces.shape[0]}", "property list uchar int vertex_indices"]
     header.append("end_header")
     rows = np.empty(m, dtype=np.dtype(fields))
     n_float = 3 if normals is None else 6
@@ -741,6 +912,11 @@ def write_ply(path, points: torch.Tensor, colors: Optional[torch.Tensor] = None,
     with open(path, "wb") as f:
         f.write(("\n".join(header) + "\n").encode("ascii"))
         f.write(rows.tobytes())
+        if faces is not None:
+            tri = np.empty(faces.shape[0], dtype=np.dtype([("n", "u1"), ("v", "<i4", (3,))]))
+            tri["n"] = 3
+            tri["v"] = faces.detach().cpu().numpy()
+            f.write(tri.tobytes())
 
 
 class _ReconstructionFields(NamedTuple):
@@ -758,21 +934,24 @@ class Reconstruction(_ReconstructionFields):
     None; and `refinement`: with a Refinement policy the RefinementResult of the consecutive pairs -- `cam2world` is then the
     refined trajectory, `rel_poses` stays the raw network output -- else None; and `rendered`: with a Render policy the
     RenderedViews of `fused` in every frame's own camera along `cam2world`, else None; and `normals`: with Render(surfels=True) the
-    CloudNormals of `fused` (`rendered` is then the SurfelViews drawn with them), else None."""
+    CloudNormals of `fused` (`rendered` is then the SurfelViews drawn with them), else None; and `mesh`: with a Meshing policy the
+    Mesh extracted from the TSDF volume of the same depths and trajectory, else None."""
     polyps = None               # Optional[PolypLocalization]
     consistency = None          # Optional[ConsistencyResult]
     refinement = None           # Optional[RefinementResult]
     rendered = None             # Optional[RenderedViews], or SurfelViews with Render(surfels=True)
     normals = None              # Optional[CloudNormals]
+    mesh = None                 # Optional[Mesh]
 
     def __new__(cls, depths, rel_poses, cam2world, points, fused=None, polyps=None, consistency=None, refinement=None,
-                rendered=None, normals=None):
+                rendered=None, normals=None, mesh=None):
         self = super().__new__(cls, depths, rel_poses, cam2world, points, fused)
         self.polyps = polyps
         self.consistency = consistency
         self.refinement = refinement
         self.rendered = rendered
         self.normals = normals
+        self.mesh = mesh
         return self
 
     def _replace(self, **kw):
@@ -781,8 +960,9 @@ class Reconstruction(_ReconstructionFields):
         refinement = kw.pop("refinement", self.refinement)
         rendered = kw.pop("rendered", self.rendered)
         normals = kw.pop("normals", self.normals)
+        mesh = kw.pop("mesh", self.mesh)
         return type(self)(*super()._replace(**kw), polyps=polyps, consistency=consistency, refinement=refinement, rendered=rendered,
-                          normals=normals)
+                          normals=normals, mesh=mesh)
 
 
 @torch.no_grad()
@@ -805,7 +985,8 @@ def reconstruct_sequence(depth_net, pose_net, frames: torch.Tensor, K: torch.Ten
                          max_depth: float = MAX_DEPTH, chunk: int = 16, voxel_size: Optional[float] = None,
                          min_obs: int = 1, labels: Optional[torch.Tensor] = None,
                          num_labels: Optional[int] = None, consistency: Optional[Consistency] = None,
-                         refine: Optional[Refinement] = None, render: Optional[Render] = None) -> Reconstruction:
+                         refine: Optional[Refinement] = None, render: Optional[Render] = None,
+                         mesh: Optional[Meshing] = None) -> Reconstruction:
     """frames [N+1,3,H,W] of one sequence, K [3,3] or [N+1,3,3] -> depth of every frame, the pose of every consecutive
     pair (DCDP: PoseNet sees both depth maps), the integrated trajectory and the stitched cloud.  With a voxel_size also
     the fused cloud of the same samples, coloured by the frames (fuse_point_cloud; `fused`, else None).  With labels
@@ -819,7 +1000,10 @@ def reconstruct_sequence(depth_net, pose_net, frames: torch.Tensor, K: torch.Ten
     cloud is drawn back into every frame's own camera along the trajectory the call used (render_fused: same K, max_depth and
     image size; radius None is the voxel size) and the RenderedViews is `rendered` (else None).  With Render(surfels=True) the cloud's
     normals are first computed from the depths, stride, max_depth and trajectory it was fused with (cloud_normals; `normals`, else
-    None) and the cloud is drawn as oriented discs: `rendered` is then a SurfelViews."""
+    None) and the cloud is drawn as oriented discs: `rendered` is then a SurfelViews.  With a Meshing policy (needs voxel_size) the
+    depths the fusion used (filtered if a Consistency is given), coloured by the frames, are integrated at full resolution into a
+    TSDF volume along the trajectory the call used (fuse_tsdf: same K, voxel_size, stride and max_depth; policy.trunc) and the surface
+    is extracted from it (extract_mesh: policy.min_obs): the Mesh is `mesh` (else None)."""
     n = frames.shape[0]
     if n < 2:
         raise ValueError("reconstruct_sequence: need at least two frames")
@@ -838,6 +1022,13 @@ def reconstruct_sequence(depth_net, pose_net, frames: torch.Tensor, K: torch.Ten
         _check_render("reconstruct_sequence", voxel_size if render.radius is None else render.radius, render.max_splat, max_depth)
         if not isinstance(render.surfels, bool):
             raise ValueError(f"reconstruct_sequence: render.surfels must be a bool, got {render.surfels!r}")
+    if mesh is not None:
+        mesh = Meshing(*mesh)
+        if voxel_size is None:
+            raise ValueError("reconstruct_sequence: mesh needs voxel_size (the TSDF volume's voxels)")
+        _tsdf_voxels("reconstruct_sequence", voxel_size, mesh.trunc)
+        if isinstance(mesh.min_obs, bool) or not isinstance(mesh.min_obs, int) or mesh.min_obs < 1:
+            raise ValueError(f"reconstruct_sequence: mesh.min_obs must be an int >= 1, got {mesh.min_obs!r}")
     if K.dim() == 2:
         K = K.unsqueeze(0).expand(n, 3, 3)
     K = K.to(frames.device, torch.float32).contiguous()
@@ -867,4 +1058,9 @@ def reconstruct_sequence(depth_net, pose_net, frames: torch.Tensor, K: torch.Ten
             normals = cloud_normals(fused, depths, K, traj32, stride=stride, max_depth=max_depth)
         rendered = render_fused(fused, K, traj32, int(frames.shape[2]), int(frames.shape[3]), radius=render.radius,
                                 max_splat=render.max_splat, max_depth=max_depth, normals=normals)
-    return Reconstruction(raw, rel, traj, cloud, fused, polyps, checked, refined, rendered, normals)
+    surface = None
+    if mesh is not None:
+        volume = fuse_tsdf(depths, K, traj32, voxel_size=voxel_size, trunc=mesh.trunc, colors=frames.to(torch.float32).contiguous(),
+                           stride=stride, max_depth=max_depth)
+        surface = extract_mesh(volume, min_obs=mesh.min_obs)
+    return Reconstruction(raw, rel, traj, cloud, fused, polyps, checked, refined, rendered, normals, surface)

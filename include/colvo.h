@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define COLVO_ABI_VERSION 22
+#define COLVO_ABI_VERSION 23
 
 typedef void* colvo_stream_t; /* hipStream_t */
 
@@ -525,6 +525,69 @@ int colvo_cloud_normals(const float* depths, const float* K, const float* cam2wo
                         float ox, float oy, float oz, float voxel_size, int nx, int ny, int nz, const int32_t* voxels, int M,
                         float rel_edge, void* scratch, float* normals, int32_t* counts, float* coherence, int32_t* stats,
                         colvo_stream_t stream);
+
+/* TSDF fusion and surface-net meshing (csrc/tsdf.hip; replica tests/tsdf_ref.py, which the outputs equal bit for
+ * bit).  The grid, its 8x8x8 bricks and their ascending order are colvo_fuse_*'s.  T = trunc / voxel_size is a whole number of voxels,
+ * 1 <= T <= 7; trunc = (float)T * voxel_size and inv_trunc = 1.0f / trunc are computed in float32 on the host.  Float32 below means
+ * every operation individually rounded in the order written (no FMA contraction), divisions correctly rounded.
+ *   plan        every sample the fusion walks (stride, 0 < d < max_depth) marks, for k = -(T+1) .. T+1 with d_k = d + (float)k *
+ *               voxel_size > 0, the brick that the fusion's world-point routine gives for (u, v, d_k), if inside the grid.  The marks
+ *               are numbered in ascending brick order: table [bricks of the grid] int32 = slot or -1, brick_list [min(bricks, 2^22)]
+ *               int32 = brick of each slot.  stats (device int32[3]): kept samples, kept samples whose own point (k = 0) lies outside
+ *               the grid, allocated bricks.  scratch: colvo_tsdf_plan_scratch_bytes bytes.
+ *   integrate   full-resolution depths whatever the plan's stride.  Per voxel (ix, iy, iz) of an allocated brick and per frame, in
+ *               any order: c_a = o_a + ((float)i_a + 0.5f) * voxel_size; camera point q = c - t, P_x = (r_00 q_0 + r_10 q_1) + r_20 q_2
+ *               (the renderers' routine); Pz > 1e-3f; x = (fx * Px) / Pz + cx, u = (int)floorf(x + 0.5f), 0 <= u < W, y and v
+ *               likewise; d = depths[f,0,v,u] with 0 < d < max_depth; sdf = d - Pz; skipped if sdf < -trunc; q = (int)rintf(
+ *               (fminf(sdf, trunc) * inv_trunc) * 4096.0f).  pool [n_bricks * 512][2] int32 receives (sum q, n) per voxel, row
+ *               slot * 512 + (lz * 8 + ly) * 8 + lx, 8 bytes; with colors [N,3,H,W], color_sums [n_bricks * 512][4] int32 receives
+ *               the sums of clamp(rint(c * 255), 0, 255) (NaN -> 0) of the same pixel and a zero, 16 bytes (colors and color_sums
+ *               are NULL together).  With N <= 65535 no sum leaves int32 (|sum q| <= 65535 * 4096).  Both arrays are written whole:
+ *               they need not be cleared.  Frames that provably add nothing to a brick are skipped (tuning entry tsdf_cull); the
+ *               sums are integers, so no bit depends on that.  survivors: NULL, or int32[n_bricks] = frames each brick walked.
+ *   mesh        a voxel is observed iff its brick is allocated and n >= min_obs, inside iff sum q < 0.  Cell (i, j, k), considered
+ *               iff voxel (i, j, k) lies in an allocated brick, has the voxels (i..i+1, j..j+1, k..k+1) as corners c = x + 2 y + 4 z;
+ *               it is active iff all eight are observed and their signs are mixed, open iff the signs of the observed ones are mixed
+ *               and one or more is not observed (a voxel outside the grid is not observed).  An active cell has one vertex; vertices
+ *               are ordered by (slot, local index) of voxel (i, j, k).  With phi_c = (double)sum q / (double)n, over the 12 edges (a, b)
+ *               in the order: axis x, y, z; per axis the two other coordinates (0,0), (1,0), (0,1), (1,1), lower axis first; an edge
+ *               whose ends differ in sign adds its crossing a + (b - a) * (phi_a / (phi_a - phi_b)) (the axis coordinate is the
+ *               quotient, the others are a's 0.0 or 1.0) to a float64 sum; m = sum / (double)crossings;
+ *               vertices[v][a] = float(double(o_a) + ((double(i_a) + 0.5) + m_a) * double(voxel_size)); cells[v] = (i, j, k);
+ *               normals[v] = float(g_a / sqrt((g_x g_x + g_y g_y) + g_z g_z)), g_a = ((e_0 + e_1) + e_2) + e_3 with e_p = phi_b -
+ *               phi_a of the axis' four edges in the order above: it points to free space; (0, 0, 0) for a zero gradient;
+ *               colors[v][k] = float((sum over c = 0..7 of double(sum c_k) / (255.0 * double(n))) / 8.0).  All float64, every
+ *               operation rounded once, divisions and the square root correctly rounded: bit for bit the replica's.
+ *               vertex_ids [n_bricks * 512] int32 receives every considered cell's vertex, or -1.
+ *               The grid edge from voxel v (in an allocated brick) to v + e_axis has a quad iff the four cells around it -- A = v -
+ *               e_u - e_w, B = v - e_w, C = v, D = v - e_u, u = axis + 1, w = axis + 2 cyclic -- are active and its ends differ in
+ *               sign: triangles (A, B, C), (A, C, D) if v is the inside end, else (A, C, B), (A, D, C): the geometric normal points
+ *               from the inside end to the outside end.  faces [F][3] int32, ordered by (slot, local index of v, axis).
+ *     count     stats2 (device int32[2]): vertices V, open cells.  scratch: colvo_tsdf_mesh_scratch_bytes(n_bricks) bytes.
+ *     vertices  writes the V vertices (n_vertices = V: no row beyond it is written) and vertex_ids, counts the triangles:
+ *               n_faces (device int32[1]) = F.
+ *     faces     writes the F triangles (n_faces = F, even).
+ * Limits: those of colvo_fuse_* (N <= 65535, H*W < 2^30, fewer than 2^31 walked samples, fewer than 2^28 bricks in the grid, n_bricks
+ * < 2^22, voxel_size finite and positive), 1 <= T <= 7, min_obs >= 1, F < 2^31; pool, color_sums, table, brick_list and scratch
+ * 16-byte aligned.  Refused before any HIP call with a message that starts with the entry's name; the size functions return 0 for
+ * what the calls refuse. */
+size_t colvo_tsdf_plan_scratch_bytes(int N, int H, int W, int stride, int nx, int ny, int nz);
+int colvo_tsdf_plan(const float* depths, const float* K, const float* cam2world, int N, int H, int W, int stride, float max_depth,
+                    float ox, float oy, float oz, float voxel_size, int nx, int ny, int nz, int T, void* scratch, int32_t* table,
+                    int32_t* brick_list, int32_t* stats, colvo_stream_t stream);
+int colvo_tsdf_integrate(const float* depths, const float* colors, const float* K, const float* cam2world, int N, int H, int W,
+                         float max_depth, float ox, float oy, float oz, float voxel_size, int nx, int ny, int nz, int T,
+                         const int32_t* brick_list, int n_bricks, void* pool, void* color_sums, int32_t* survivors,
+                         colvo_stream_t stream);
+size_t colvo_tsdf_mesh_scratch_bytes(int n_bricks);
+int colvo_tsdf_mesh_count(const void* pool, const int32_t* table, const int32_t* brick_list, int n_bricks, int min_obs, int nx, int ny,
+                          int nz, void* scratch, int32_t* stats2, colvo_stream_t stream);
+int colvo_tsdf_mesh_vertices(const void* pool, const void* color_sums, const int32_t* table, const int32_t* brick_list, int n_bricks,
+                             int min_obs, float ox, float oy, float oz, float voxel_size, int nx, int ny, int nz, void* scratch,
+                             int n_vertices, float* vertices, float* colors, float* normals, int32_t* cells, int32_t* vertex_ids,
+                             int32_t* n_faces, colvo_stream_t stream);
+int colvo_tsdf_mesh_faces(const void* pool, const int32_t* table, const int32_t* brick_list, int n_bricks, int nx, int ny, int nz,
+                          const void* scratch, const int32_t* vertex_ids, int n_faces, int32_t* faces, colvo_stream_t stream);
 
 /* Polyp localisation: labelled pixels + depth maps + trajectory -> where each polyp lies, in the camera frame of
  * every frame that shows it and in the world frame, and how large it is.  labels [N,1,H,W] uint8: 0 background, 1..num_labels a
