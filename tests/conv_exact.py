@@ -164,6 +164,28 @@ class Layer:
         return dw.permute(0, 2, 3, 1).reshape(self.Cout, 9, self.Cin), db
 
 
+def layers(net, B, H, W):
+    """(name, Layer) of every conv of DepthNet (DepthNet._plan) or of PoseNet's stride-2 chain at batch B (frames / pairs)."""
+    import types
+    from coivo_amd import nn as hnn
+    if net == "depth":
+        plan = hnn.DepthNet._plan(types.SimpleNamespace(compute_dtype=torch.bfloat16, _plans={}), B, H, W)
+        return [(name, Layer.of_desc(d)) for name, d in plan.items()]
+    out, h, w, cin = [], H, W, 8
+    for i, c in enumerate(hnn.POSE_CH, start=1):
+        lay = Layer(B, h, w, cin, 0, False, False, c, 2)
+        out.append((f"conv{i}", lay))
+        h, w, cin = lay.Ho, lay.Wo, c
+    return out
+
+
+# The inference batch sizes of tests/test_conv_exact_small_batch_gpu.py (why each: its docstring); tests/test_abi_cpu.py holds the
+# exact-regime bounds for them.
+SMALL_BATCH_SHAPES = [("depth", 1, 256, 320), ("pose", 1, 256, 320), ("depth", 3, 256, 320), ("pose", 3, 256, 320),
+                      ("depth", 5, 256, 320), ("depth", 13, 256, 320), ("pose", 13, 256, 320),
+                      ("depth", 1, 512, 640), ("depth", 3, 512, 640), ("pose", 1, 512, 640)]
+
+
 def expect_exact(got, ref, quantum, what):
     """got (kernel dtype) == ref (float64, exact) rounded once to got's dtype, by value.  On failure: the number of mismatching
     elements, the largest difference in quanta and the first bad index (NHWC: b, y, x, c)."""

@@ -255,6 +255,29 @@ def oracle_step(seed, batch, dtype=torch.float32, masks=None, weights_seed=None,
                 grads=_named_grads(dn, pn), flips=stats["flips"], flip_worst=stats["worst"])
 
 
+def oracle_networks(seed, frames, dtype=torch.float32, device=None, bf16_weights=False, emulate=False):
+    """The oracle's two networks forward only, on the frames [N+1,3,H,W] of one sequence, whole (no chunks, no slices): DepthNet on
+    every frame, PoseNet on every consecutive pair with the depths this very run made (in float64: the float64 depths) -- what
+    inference.run_networks computes.  dtype: the oracle's arithmetic; device: where it runs (on a GPU with MIOpen off, as in
+    oracle_step); bf16_weights: the spec weights rounded to bf16 (bf16_rounded_state), the target of bf16 mode; emulate: the HIP
+    networks' bf16 storage points inserted (_bf16_hooks), the noise scale of bf16 mode.
+    -> (depths [N+1,1,H,W], rel_poses [N,6]) in `dtype` on the CPU."""
+    from oracle import colvo_spec as S
+    dn, pn = S.make_models(seed, dtype=dtype)
+    if bf16_weights:
+        dn.load_state_dict(bf16_rounded_state(dn))
+        pn.load_state_dict(bf16_rounded_state(pn))
+    if device is not None:
+        dn, pn = dn.to(device), pn.to(device)
+    if emulate:
+        _bf16_hooks(dn, pn, None, True, _Rows())
+    f = frames.to(device=device, dtype=dtype)
+    with torch.no_grad(), _plain_convs(device):
+        d = dn(f)
+        pose, _, _ = pn(f[:-1], f[1:], d[:-1], d[1:])
+    return d.cpu(), pose.cpu()
+
+
 def _timed(timings, key, fn):
     if timings is None:
         return fn()
@@ -318,17 +341,11 @@ def bf16_rounded_state(module):
     return {k: v.to(torch.bfloat16).to(v.dtype) for k, v in module.state_dict().items()}
 
 
-def oracle_step_bf16(seed, batch, masks=None, emulate=False, weights_seed=None, device=None, slice_pairs=None):
-    """The fp32 oracle's coupled step on bf16-ROUNDED weights; ReLU decisions forced to `masks` (hip_relu_masks) where given;
-    emulate: the bf16 storage points of the HIP networks inserted (see above); device, slice_pairs: as in oracle_step.
-    -> dict(loss, d_t, d_r, grads [(name, tensor)])."""
-    from oracle import colvo_spec as S
-    dn, pn = S.make_models(seed if weights_seed is None else weights_seed)
-    dn.load_state_dict(bf16_rounded_state(dn))
-    pn.load_state_dict(bf16_rounded_state(pn))
-    if device is not None:
-        dn, pn = dn.to(device), pn.to(device)
-    rows = _Rows()
+def _bf16_hooks(dn, pn, masks, emulate, rows):
+    """Forward hooks on the oracle networks for bf16 mode: with `emulate` every conv layer's output (not the fp32 heads') and the first
+    layer's input are rounded to bf16 -- the storage points of the HIP networks; with `masks` the ReLU decisions are forced to them
+    (rows: which rows of the masks the networks are looking at).  Shared by the step (oracle_step_bf16) and the forward-only run
+    (oracle_networks)."""
     for tag, net, first, fp32_layers in (("depth", dn, "enc1a", ("head",)), ("pose", pn, "conv1", ("pred",))):
         for name, mod in net.named_children():
             if name in fp32_layers:
@@ -348,6 +365,20 @@ def oracle_step_bf16(seed, batch, masks=None, emulate=False, weights_seed=None, 
             mod.register_forward_hook(hook)
             if emulate and name == first:
                 mod.register_forward_pre_hook(lambda mod, inp: (_RoundBf16.apply(inp[0]),))
+
+
+def oracle_step_bf16(seed, batch, masks=None, emulate=False, weights_seed=None, device=None, slice_pairs=None):
+    """The fp32 oracle's coupled step on bf16-ROUNDED weights; ReLU decisions forced to `masks` (hip_relu_masks) where given;
+    emulate: the bf16 storage points of the HIP networks inserted (see above); device, slice_pairs: as in oracle_step.
+    -> dict(loss, d_t, d_r, grads [(name, tensor)])."""
+    from oracle import colvo_spec as S
+    dn, pn = S.make_models(seed if weights_seed is None else weights_seed)
+    dn.load_state_dict(bf16_rounded_state(dn))
+    pn.load_state_dict(bf16_rounded_state(pn))
+    if device is not None:
+        dn, pn = dn.to(device), pn.to(device)
+    rows = _Rows()
+    _bf16_hooks(dn, pn, masks, emulate, rows)
     t = lambda v: v.to(device=device)
     with _plain_convs(device):
         loss, d_t, d_r, pose, a, b = _coupled_step(dn, pn, t(batch["tgt"]), t(batch["ref"]), t(batch["K"]), rows, slice_pairs, False)

@@ -363,3 +363,25 @@ def test_exact_data_stays_in_the_exact_regime_at_every_production_shape():
                     (X.make_base((4096,), g, "cpu"), X.QBASE, X.BASE_MAX)):
         assert torch.equal(t.to(torch.bfloat16).float(), t)
         assert torch.equal(t / q, (t / q).round()) and float((t / q).abs().max()) == m
+
+
+def test_exact_data_stays_in_the_exact_regime_at_the_inference_shapes():
+    """The same bounds for the descriptors of tests/test_conv_exact_small_batch_gpu.py (1 to 13 frames or pairs of 256x320, 1 and 3 of
+    512x640).  Fewer pixels than at the benchmark's shapes and a dy density capped at RHO_MAX: the bounds should hold, and here they
+    are computed, not assumed -- down to PoseNet's 2x3 last layer, where the weight gradient sums six pixels and dy must still
+    hold something."""
+    from tests import conv_exact as X
+    n = 0
+    for net, B, H, W in X.SMALL_BATCH_SHAPES:
+        for name, lay in X.layers(net, B, H, W):
+            what = f"{net} {name} B={B} {H}x{W}"
+            assert X.bound_fwd(lay.Cin) <= X.BOUND, what
+            assert X.bound_dgrad(lay.Cout, lay.up0 or lay.up1) <= X.BOUND, what
+            npix = lay.B * lay.Ho * lay.Wo
+            assert X.dy_density(npix) <= X.RHO_MAX, what
+            assert X.bound_wgrad(npix) <= X.BOUND, (what, X.bound_wgrad(npix))
+            assert X.dy_density(npix) * npix >= min(npix / 4, 1e5), what
+            n += 1
+    assert n == 6 * 20 + 4 * 7
+    last = dict(X.layers("pose", 1, 256, 320))["conv7"]
+    assert (last.Ho, last.Wo) == (2, 3)

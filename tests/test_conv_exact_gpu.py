@@ -34,21 +34,6 @@ PRODUCTION_FORMS = {"conv_rt", "conv_rt_bn32", "wgrad_full_grid", "wgrad_halved_
 _SEEN = {}          # shape -> {form: launches} of the sweep in this process
 
 
-def layers(net, B, H, W):
-    """(name, Layer) of every conv of DepthNet (DepthNet._plan) or of PoseNet's stride-2 chain at batch B (frames / pairs)."""
-    import types
-    from coivo_amd import nn as hnn
-    if net == "depth":
-        plan = hnn.DepthNet._plan(types.SimpleNamespace(compute_dtype=torch.bfloat16, _plans={}), B, H, W)
-        return [(name, X.Layer.of_desc(d)) for name, d in plan.items()]
-    out, h, w, cin = [], H, W, 8
-    for i, c in enumerate(hnn.POSE_CH, start=1):
-        lay = X.Layer(B, h, w, cin, 0, False, False, c, 2)
-        out.append((f"conv{i}", lay))
-        h, w, cin = lay.Ho, lay.Wo, c
-    return out
-
-
 def _free():
     gc.collect()
     torch.cuda.synchronize()
@@ -62,7 +47,7 @@ def sweep(net, B, H, W):
     d = dev()
     g = torch.Generator(device=d).manual_seed(B * 100003 + H * 7 + (net == "pose"))
     total = {dt: {} for dt in DTYPES}
-    for name, lay in layers(net, B, H, W):
+    for name, lay in X.layers(net, B, H, W):
         data = X.make_data(lay, g, d)
         for dt in DTYPES:
             forms = X.check_layer(lay, dt, g, d, data=data)
@@ -166,7 +151,7 @@ def test_a_dropped_tile_or_image_changes_the_exact_answer():
     production-shape weight gradient (enc3b at 64 frames of 256x320) -- torch.equal fails on either.  On this data test_conv_gpu.py's
     relative bar (2e-4 of the largest element + 2e-4 relative) fails too: dy has random signs, so dw is a random walk over ~3e5
     pixels and 128 of them move it by a few percent of max|dw|; the exact bar does not depend on that."""
-    lay = dict(layers("depth", 64, 256, 320))["enc3b"]
+    lay = dict(X.layers("depth", 64, 256, 320))["enc3b"]
     g = torch.Generator(device=dev()).manual_seed(5)
     data = X.make_data(lay, g, dev())
     X.check_wgrad_bound([data["x0"]], data["dy_wgrad"], "enc3b")
