@@ -138,7 +138,12 @@ namespace tune {
                             "already <= its own (keys only decrease: a stale read costs an atomic, never skips a needed one).  The "   \
                             "result does not depend on it.  543 031 points into 512 views of 256x320, whole call, alternating call by "  \
                             "call: 0 -> 10881.4 us, 1 -> 6122.5 (tools/bench_render.py)")                                               \
-    /* ---- TSDF fusion (tsdf.hip) ---- */                                                                                           \
+    /* ---- mesh rendering (raster.hip) ---- */                                                                                      \
+    X(raster_coop_min_pixels, 256, "a face whose bounding box holds at least this many pixel centres is not walked by its own lane: "  \
+                                   "the wave takes such faces one by one and all 64 lanes stride the box (0: every face; a value no "  \
+                                   "box reaches: none).  The result does not depend on it.  256 = four pixels per lane, a choice: "     \
+                                   "tools/bench_raster.py times both sides of it, DESIGN.md 3.6n has what was measured")               \
+    /* ---- TSDF fusion (tsdf.hip) ---- */                                                                                         \
     X(tsdf_cull, 1, "k_tsdf_integrate tests the frames 64 at a time against the brick (depth slab and image rectangle, conservative) "  \
                     "and walks only the survivors; 0: every brick walks every frame.  Integer sums: the result does not depend on it "  \
                     "(tests/test_tsdf_gpu.py compares the bits; times: tools/bench_tsdf.py, DESIGN.md 3.6m)")

@@ -700,20 +700,25 @@ class _RenderFields(NamedTuple):
 class Render(_RenderFields):
     """What reconstruct_sequence renders when asked: the fused cloud into every frame's own camera (render_fused).  The defaults
     are choices, not tuned values.  Behind the two fields -- it still unpacks into two -- `surfels`: True has the cloud's normals
-    computed (cloud_normals) and the cloud drawn as oriented discs (render_surfels) instead of squares."""
+    computed (cloud_normals) and the cloud drawn as oriented discs (render_surfels) instead of squares; and `mesh`: True has the
+    extracted surface mesh drawn instead of the cloud (render_mesh; needs a Meshing policy, excludes surfels; radius and max_splat
+    are not used)."""
     surfels = False
+    mesh = False
 
-    def __new__(cls, radius=None, max_splat=8, surfels=False):
+    def __new__(cls, radius=None, max_splat=8, surfels=False, mesh=False):
         self = super().__new__(cls, radius, max_splat)
         self.surfels = surfels
+        self.mesh = mesh
         return self
 
     def _replace(self, **kw):
         surfels = kw.pop("surfels", self.surfels)
-        return type(self)(*super()._replace(**kw), surfels=surfels)
+        mesh = kw.pop("mesh", self.mesh)
+        return type(self)(*super()._replace(**kw), surfels=surfels, mesh=mesh)
 
     def __repr__(self):
-        return f"Render(radius={self.radius!r}, max_splat={self.max_splat!r}, surfels={self.surfels!r})"
+        return f"Render(radius={self.radius!r}, max_splat={self.max_splat!r}, surfels={self.surfels!r}, mesh={self.mesh!r})"
 
 
 class RenderedViews(NamedTuple):
@@ -863,6 +868,88 @@ def render_fused(fused: FusedCloud, K: torch.Tensor, cam2world: torch.Tensor, H:
                           max_depth=max_depth, want_normals=want_normals)
 
 
+class MeshViews(NamedTuple):
+    depth: torch.Tensor              # [N,1,H,W] float32: camera-z where the pixel centre's ray meets the nearest face, +inf where empty
+    index: torch.Tensor              # [N,1,H,W] int32: that face's row, -1 where empty
+    colors: Optional[torch.Tensor]   # [N,3,H,W] float32: its vertex colours interpolated perspective-correctly, 0 where empty (None without)
+    normal: Optional[torch.Tensor]   # [N,3,H,W] float32: its unit face normal in the camera frame, towards the camera (None unless asked)
+    stats: torch.Tensor              # [N,8] int32: faces front, drawn, straddling, outside the guard band, back-facing, degenerate; fragments; covered pixels
+    face_pixels: Optional[torch.Tensor]   # [F] int32: the pixels of all views each face won (None unless asked)
+
+
+def render_mesh(mesh_or_vertices, faces: Optional[torch.Tensor] = None, K: Optional[torch.Tensor] = None,
+                cam2world: Optional[torch.Tensor] = None, H: Optional[int] = None, W: Optional[int] = None, *,
+                colors: Optional[torch.Tensor] = None, cull_back: bool = False, max_depth: float = MAX_DEPTH,
+                want_normals: bool = False, want_face_pixels: bool = False) -> MeshViews:
+    """A triangle mesh drawn into N camera views of H x W pixels (contract: include/colvo.h colvo_render_mesh, DESIGN.md §3.6n;
+    csrc/raster.hip).  Either a Mesh -- `render_mesh(mesh, K, cam2world, H, W)` or with keywords; its vertices, faces and colours are
+    taken, `colors=` overrides the latter -- or vertices [V,3] float32 and faces [F,3] int32 in the world frame with colors [V,3] or
+    None; K [3,3] or [N,3,3], cam2world [N,4,4], float32 on the device.  Every face whose three vertices are in front of a camera
+    (1e-3 < P_z < max_depth) is snapped to a 1/256-pixel grid and covers the pixel centres inside it -- top-left rule: a pixel centre
+    on an edge or a vertex shared by consistently wound faces belongs to exactly one of them --; a covered pixel gets the
+    perspective-correct depth of its ray on the face, the nearest face wins, equal depths go to the smallest row.  No radius, no
+    holes inside the surface.  cull_back drops the faces seen from behind (extract_mesh winds towards free space); off by default
+    because the wall is opaque from both sides -- a choice.  want_normals: also the winner's camera-frame face normal per pixel;
+    want_face_pixels: also how many pixels of all views each face won -- which part of the surface was seen, and how well.  The
+    cameras need not be frames of the sequence.  Integer edge functions, float64 depth in a written association, an integer
+    minimum and integer sums: identical bits on every call and stream, equal to the NumPy replica tests/raster_ref.py.
+
+    A pixel no face covers gets depth +inf and index -1, as render_cloud's.  There is no near-plane clipping: a face with a vertex
+    behind the camera or beyond max_depth is dropped whole and counted as straddling, a face with a vertex that projects more than
+    16384 pixels from the origin is dropped whole and counted as outside.  No anti-aliasing, blending or smooth shading.  No read-back and no host synchronisation."""
+    who = "render_mesh"
+    if isinstance(mesh_or_vertices, Mesh):
+        rest = [a for a in (faces, K, cam2world, H, W) if a is not None]
+        if len(rest) != 4:
+            raise ValueError(f"{who}: with a Mesh give K, cam2world, H and W (and no faces)")
+        K, cam2world, H, W = rest
+        vertices, faces = mesh_or_vertices.vertices, mesh_or_vertices.faces
+        colors = mesh_or_vertices.colors if colors is None else colors
+    else:
+        vertices = mesh_or_vertices
+    if not _finite_pos32(max_depth):
+        raise ValueError(f"{who}: max_depth must be finite and positive (as float32), got {max_depth!r}")
+    for name, val in (("cull_back", cull_back), ("want_normals", want_normals), ("want_face_pixels", want_face_pixels)):
+        if not isinstance(val, bool):
+            raise ValueError(f"{who}: {name} must be a bool, got {val!r}")
+    for name, val in (("H", H), ("W", W)):
+        if isinstance(val, bool) or not isinstance(val, int) or not 1 <= val <= 16384:
+            raise ValueError(f"{who}: {name} must be an int in 1..16384, got {val!r}")
+    if not isinstance(vertices, torch.Tensor) or vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise ValueError(f"{who}: vertices must be [V,3]")
+    if not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int32:
+        raise ValueError(f"{who}: faces must be [F,3] int32")
+    if not isinstance(cam2world, torch.Tensor) or cam2world.dim() != 3:
+        raise ValueError(f"{who}: cam2world must be [N,4,4]")
+    V, F, N = vertices.shape[0], faces.shape[0], cam2world.shape[0]
+    if not 1 <= N <= 65535 or N * H * W >= 1 << 31 or V >= 1 << 31 or F >= 1 << 31:
+        raise ValueError(f"{who}: V={V} F={F} N={N} H={H} W={W} beyond the kernels' limits (V, F < 2^31, 1 <= N <= 65535, "
+                         "H, W <= 16384, N*H*W < 2^31)")
+    vertices = _chk(vertices, "vertices", (V, 3))
+    if faces.device != vertices.device or not faces.is_contiguous():
+        raise ValueError(f"{who}: faces must be contiguous and on the device of vertices")
+    cam2world = _chk(cam2world, "cam2world", (N, 4, 4))
+    if isinstance(K, torch.Tensor) and K.dim() == 2:
+        K = K.unsqueeze(0).expand(N, 3, 3)
+    K = _chk(K, "K", (N, 3, 3))
+    if colors is not None:
+        colors = _chk(colors, "colors", (V, 3))
+    lib = _lib.load()
+    dev = vertices.device
+    scratch = torch.empty(int(lib.colvo_render_scratch_bytes(N, H, W)), device=dev, dtype=torch.uint8)
+    depth = torch.empty(N, 1, H, W, device=dev, dtype=torch.float32)
+    index = torch.empty(N, 1, H, W, device=dev, dtype=torch.int32)
+    out_colors = torch.empty(N, 3, H, W, device=dev, dtype=torch.float32) if colors is not None else None
+    out_normal = torch.empty(N, 3, H, W, device=dev, dtype=torch.float32) if want_normals else None
+    face_pixels = torch.empty(F, device=dev, dtype=torch.int32) if want_face_pixels else None
+    stats = torch.empty(N, 8, device=dev, dtype=torch.int32)
+    _lib.check(lib.colvo_render_mesh(_lib.ptr(vertices), _lib.ptr(faces), _lib.ptr(colors), V, F, _lib.ptr(K), _lib.ptr(cam2world), N, H,
+                                     W, float(max_depth), int(cull_back), _lib.ptr(scratch), _lib.ptr(depth), _lib.ptr(index),
+                                     _lib.ptr(out_colors), _lib.ptr(out_normal), _lib.ptr(face_pixels), _lib.ptr(stats),
+                                     _lib.stream_ptr()), "colvo_render_mesh")
+    return MeshViews(depth, index, out_colors, out_normal, stats, face_pixels)
+
+
 def write_ply(path, points: torch.Tensor, colors: Optional[torch.Tensor] = None, normals: Optional[torch.Tensor] = None,
               faces: Optional[torch.Tensor] = None) -> None:
     """Binary little-endian PLY: `float x y z` per vertex, with normals [M,3] `float nx ny nz` behind them (viewers shade by them)
@@ -935,11 +1022,12 @@ class Reconstruction(_ReconstructionFields):
     refined trajectory, `rel_poses` stays the raw network output -- else None; and `rendered`: with a Render policy the
     RenderedViews of `fused` in every frame's own camera along `cam2world`, else None; and `normals`: with Render(surfels=True) the
     CloudNormals of `fused` (`rendered` is then the SurfelViews drawn with them), else None; and `mesh`: with a Meshing policy the
-    Mesh extracted from the TSDF volume of the same depths and trajectory, else None."""
+    Mesh extracted from the TSDF volume of the same depths and trajectory, else None (with Render(mesh=True) `rendered` is the
+    MeshViews of that mesh)."""
     polyps = None               # Optional[PolypLocalization]
     consistency = None          # Optional[ConsistencyResult]
     refinement = None           # Optional[RefinementResult]
-    rendered = None             # Optional[RenderedViews], or SurfelViews with Render(surfels=True)
+    rendered = None             # Optional[RenderedViews], SurfelViews with Render(surfels=True), MeshViews with Render(mesh=True)
     normals = None              # Optional[CloudNormals]
     mesh = None                 # Optional[Mesh]
 
@@ -1003,7 +1091,9 @@ def reconstruct_sequence(depth_net, pose_net, frames: torch.Tensor, K: torch.Ten
     None) and the cloud is drawn as oriented discs: `rendered` is then a SurfelViews.  With a Meshing policy (needs voxel_size) the
     depths the fusion used (filtered if a Consistency is given), coloured by the frames, are integrated at full resolution into a
     TSDF volume along the trajectory the call used (fuse_tsdf: same K, voxel_size, stride and max_depth; policy.trunc) and the surface
-    is extracted from it (extract_mesh: policy.min_obs): the Mesh is `mesh` (else None)."""
+    is extracted from it (extract_mesh: policy.min_obs): the Mesh is `mesh` (else None).  With Render(mesh=True) (needs a Meshing policy;
+    not together with surfels=True) it is that mesh, not the cloud, that is drawn into every frame's own camera (render_mesh: same K,
+    max_depth and image size, culling off): `rendered` is then a MeshViews and `normals` stays None."""
     n = frames.shape[0]
     if n < 2:
         raise ValueError("reconstruct_sequence: need at least two frames")
@@ -1016,12 +1106,18 @@ def reconstruct_sequence(depth_net, pose_net, frames: torch.Tensor, K: torch.Ten
         refine = Refinement(*refine)
         _check_refinement("reconstruct_sequence", refine, max_depth)
     if render is not None:
-        render = Render(*render, surfels=getattr(render, "surfels", False))
+        render = Render(*render, surfels=getattr(render, "surfels", False), mesh=getattr(render, "mesh", False))
         if voxel_size is None:
             raise ValueError("reconstruct_sequence: render needs voxel_size (it draws the fused cloud)")
         _check_render("reconstruct_sequence", voxel_size if render.radius is None else render.radius, render.max_splat, max_depth)
         if not isinstance(render.surfels, bool):
             raise ValueError(f"reconstruct_sequence: render.surfels must be a bool, got {render.surfels!r}")
+        if not isinstance(render.mesh, bool):
+            raise ValueError(f"reconstruct_sequence: render.mesh must be a bool, got {render.mesh!r}")
+        if render.mesh and render.surfels:
+            raise ValueError("reconstruct_sequence: Render(mesh=True) draws the surface mesh, surfels=True the cloud: give one of them")
+        if render.mesh and mesh is None:
+            raise ValueError("reconstruct_sequence: Render(mesh=True) needs a Meshing policy (mesh=Meshing()): it draws the extracted mesh")
     if mesh is not None:
         mesh = Meshing(*mesh)
         if voxel_size is None:
@@ -1053,7 +1149,7 @@ def reconstruct_sequence(depth_net, pose_net, frames: torch.Tensor, K: torch.Ten
         from . import localize                       # (localize imports this module)
         polyps = localize.localize_polyps(depths, labels, K, traj32, num_labels=num_labels, stride=1, max_depth=max_depth)
     rendered = normals = None
-    if render is not None:
+    if render is not None and not render.mesh:
         if render.surfels:
             normals = cloud_normals(fused, depths, K, traj32, stride=stride, max_depth=max_depth)
         rendered = render_fused(fused, K, traj32, int(frames.shape[2]), int(frames.shape[3]), radius=render.radius,
@@ -1063,4 +1159,6 @@ def reconstruct_sequence(depth_net, pose_net, frames: torch.Tensor, K: torch.Ten
         volume = fuse_tsdf(depths, K, traj32, voxel_size=voxel_size, trunc=mesh.trunc, colors=frames.to(torch.float32).contiguous(),
                            stride=stride, max_depth=max_depth)
         surface = extract_mesh(volume, min_obs=mesh.min_obs)
+        if render is not None and render.mesh:
+            rendered = render_mesh(surface, K, traj32, int(frames.shape[2]), int(frames.shape[3]), max_depth=max_depth)
     return Reconstruction(raw, rel, traj, cloud, fused, polyps, checked, refined, rendered, normals, surface)

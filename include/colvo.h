@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define COLVO_ABI_VERSION 23
+#define COLVO_ABI_VERSION 24
 
 typedef void* colvo_stream_t; /* hipStream_t */
 
@@ -717,6 +717,47 @@ int colvo_render_cloud(const float* points, const float* colors, int M, const fl
 int colvo_render_surfels(const float* points, const float* normals, const float* colors, int M, const float* K, const float* cam2world,
                          int N, int H, int W, float radius, int max_splat, float max_depth, void* scratch, float* out_depth,
                          int32_t* out_index, float* out_colors, float* out_normal, int32_t* out_stats, colvo_stream_t stream);
+
+/* Triangle mesh into camera views: z-buffered rasterisation.  vertices [V,3] float32 in the world frame, faces [F,3]
+ * int32 (rows of vertices), colors [V,3] float32 or NULL, K [N,3,3], cam2world [N,4,4] float32 as for colvo_render_cloud, images of
+ * H x W pixels, cull_back 0 or 1.  Pixel u has its centre at x = u.  Float32 and float64 operations are individually rounded in the
+ * order written (no FMA contraction), plain divisions; edge functions are 64-bit integers.  Per frame n and face f:
+ *   camera      each of the three vertices as colvo_render_cloud's camera point P.  A face with an index outside [0, V) is dead in
+ *               every frame: never dereferenced, never counted.  A vertex is front iff P_z > 1e-3f and P_z < max_depth (NaN falls
+ *               out).  The face is front iff all three are; straddling iff some but not all are: dropped and counted.  There is NO
+ *               near-plane clipping: a face that crosses z = 1e-3 or max_depth is lost whole.
+ *   projection  of a front face: x = (fx * P_x) / P_z + cx, y = (fy * P_y) / P_z + cy.  In the guard band iff |x| <= 16384 and
+ *               |y| <= 16384 for all three vertices (NaN and infinities fail); a front face outside is dropped and counted.
+ *               X = (int)rintf(x * 256.0f), Y likewise: 1/256-pixel fixed point, |X|, |Y| <= 2^22.
+ *   area        A = (X1 - X0)(Y2 - Y0) - (X2 - X0)(Y1 - Y0) in int64.  A == 0: degenerate, dropped and counted.  A < 0: front-facing
+ *               (x right, y down: the winding extract_mesh produces).  A > 0: back-facing, always counted, dropped iff cull_back.
+ *               When A < 0 vertices 1 and 2 are exchanged and A = -A: the ORIENTED numbering, which everything below uses.
+ *   coverage    u_lo = max((min X + 255) >> 8, 0), u_hi = min(max X >> 8, W - 1), the same in v with Y, H (arithmetic shifts).  For the
+ *               directed edge a -> b opposite vertex k (1 -> 2, 2 -> 0, 0 -> 1), d = b - a and p = (256 u, 256 v):
+ *               E_k = d_x (p_y - a_y) - d_y (p_x - a_x), |E_k| < 2^48, E_0 + E_1 + E_2 = A.  The pixel is covered iff for every k
+ *               E_k > 0, or E_k == 0 and the edge is top-left: d_y < 0, or d_y == 0 and d_x > 0.  The pixel centres of a region
+ *               tessellated by consistently wound faces are each owned by exactly one face, on shared edges and vertices too.
+ *               The face is drawn iff it survived every test above and u_lo <= u_hi and v_lo <= v_hi.
+ *   depth       float64: iz_k = 1.0 / (double)P_z,k, w_k = (double)E_k * iz_k, s = (w_0 + w_1) + w_2, z = (float)((double)A / s):
+ *               the depth of the ray through the pixel centre on the snapped face.  min P_z,k <= z <= max P_z,k in float32.
+ *   key         (uint64(bits(z)) << 32) | uint32(f) into the pixel's minimum: the nearest face wins, equal depths go to the smallest f.
+ *   outputs     out_depth [N,1,H,W] float32: the winning z, +inf where empty;  out_index [N,1,H,W] int32: the winning face, -1 where
+ *               empty;  out_colors [N,3,H,W] float32 or NULL (colors must be given iff it is; NULL allowed when V = 0):
+ *               (float)(((w_0 * c_0 + w_1 * c_1) + w_2 * c_2) / s) of the winner's vertex colours as doubles, 0 where empty;
+ *               out_normal [N,3,H,W] float32 or NULL: the winner's unit face normal in the camera frame, float64, the face's own
+ *               numbering: a = P_1 - P_0, b = P_2 - P_0, m = a x b (m_x = a_y b_z - a_z b_y, ...), len = sqrt((m_x^2 + m_y^2) +
+ *               m_z^2), m / len, negated iff (m_x P_0x + m_y P_0y) + m_z P_0z > 0 of the unit vector, rounded to float32; 0 where
+ *               empty or len is 0 or not finite;  out_face_pixels [F] int32 or NULL: the pixels of all frames each face won (cleared
+ *               by the call; their sum is the sum of the covered pixels);  out_stats [N,8] int32 per frame: faces front, drawn,
+ *               straddling, outside the guard band, back-facing, degenerate, fragments ((face, pixel) offers), covered pixels.
+ *               Integer sums (they wrap beyond 2^31) and a minimum: identical bits on every call and stream.
+ * scratch: colvo_render_scratch_bytes(N, H, W) bytes, 16-byte aligned.  No read-back and no host synchronisation.
+ * Limits, refused before any HIP call with a message that starts `colvo_render_mesh:`: 0 <= V, F < 2^31 (F = 0 or V = 0 gives empty
+ * images), 1 <= N <= 65535, 1 <= H, W <= 16384, N*H*W < 2^31, max_depth finite and positive, cull_back in {0, 1}. */
+int colvo_render_mesh(const float* vertices, const int32_t* faces, const float* colors, int V, int F, const float* K,
+                      const float* cam2world, int N, int H, int W, float max_depth, int cull_back, void* scratch, float* out_depth,
+                      int32_t* out_index, float* out_colors, float* out_normal, int32_t* out_face_pixels, int32_t* out_stats,
+                      colvo_stream_t stream);
 
 /* Pose refinement by dense depth and intensity alignment: a few Gauss-Newton steps per edge on the per-pixel geometric
  * and photometric residuals of the two frames it connects, starting from the pose given.  depths [N,1,H,W], frames [N,3,H,W], K [N,3,3]
