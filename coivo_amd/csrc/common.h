@@ -137,6 +137,11 @@ inline void form_hits(uint32_t mask) {          // every FORM_f whose form_bit i
 int launch_dgrad_planes_s2_mfma(const void* g, const float* w, int Cin, int c_begin, int B, int Hi, int Wi, int Ho, int Wo, float* dst,
                                 int accumulate, hipStream_t stream);
 
+// csrc/pose_front.hip: COLVO_CMD_CONV_FWD with a chain length in i[0] -- PoseNet's conv1-conv3 in one launch -- and
+// COLVO_CMD_CONV_DGRAD_PLANES with g3 in p[3] -- their input-gradient chain down to the two depth planes in one launch
+int pose_front_fwd(const ColvoCmd& c, hipStream_t stream);
+int pose_front_bwd(const ColvoCmd& c, hipStream_t stream);
+
 __device__ __forceinline__ float uniform_f(float v) {
     return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)));
 }

@@ -1813,6 +1813,30 @@ inline ConvK dgrad_conv(const ColvoConvDesc* d, const void* dy, const void* w_bw
 }  // namespace
 }  // namespace colvo
 
+// pose_front.hip's planner: would colvo_conv_fwd run layer d as the plain one-tile kernel (k_conv3x3, 256 threads, one chunk in
+// flight)?  Plans only: no HIP call, no form counted.
+namespace colvo {
+bool conv_fwd_is_one_tile(const ColvoConvDesc* d) {
+    if (check_desc(d, "colvo_pose_front_plan")) return false;
+    ConvK k{};
+    fill_gather(d, nullptr, nullptr, k.g);
+    k.Ho = d->Ho; k.Wo = d->Wo;
+    k.Ctot = d->C0 + d->C1; k.N = d->Cout;
+    k.relu = d->relu;
+    ConvPlan p{};
+    if (conv_plan(d, PASS_FWD, 0, k, p)) return false;
+    return p.form == CONV_TILE && p.nth == NT && p.depth == 1;
+}
+// ... and would colvo_conv_dgrad run layer d's input gradient as k_dgrad_s2 with one chunk in flight?
+bool conv_dgrad_is_s2_tile(const ColvoConvDesc* d) {
+    if (check_desc(d, "colvo_pose_front_plan") || d->C1 != 0) return false;
+    ConvK k = dgrad_conv(d, nullptr, nullptr, 0, d->C0, nullptr, nullptr, 0);
+    ConvPlan p{};
+    if (conv_plan(d, PASS_DGRAD, d->up0, k, p)) return false;
+    return p.form == DGRAD_S2 && p.nch == 0;
+}
+}  // namespace colvo
+
 using namespace colvo;
 
 extern "C" int colvo_conv_fwd(const ColvoConvDesc* d, const void* x0, const void* x1, const void* w_fwd,

@@ -73,6 +73,11 @@ struct ConvPlan {
 bool conv_rt_plan(ConvK& k, int B, int dtype, ConvPlan& p);
 int conv_rt_launch(const ConvK& k, const ConvPlan& p, int dtype, hipStream_t s);
 
+// conv.hip, for pose_front.hip's planner: whether colvo_conv_fwd would run layer d as the plain one-tile kernel, and colvo_conv_dgrad
+// its input gradient as k_dgrad_s2 with one chunk in flight.  Plans only: no HIP call, no form counted.
+bool conv_fwd_is_one_tile(const ColvoConvDesc* d);
+bool conv_dgrad_is_s2_tile(const ColvoConvDesc* d);
+
 // Where a weight-gradient kernel puts its sums: part of the kernel argument of all three kernels (k_wgrad3x3, k_wgrad_up2, k_wgrad_rt),
 // filled once per launch by wgrad.hip's wgrad_resolve.  Device pointers and flags only.
 //   slabs != null  every pixel-range split STORES its sums into a slab of its own; k_wgrad_reduce or colvo_wgrad_reduce_group adds the

@@ -87,6 +87,7 @@ extern "C" int colvo_set_aux_side_streams(int n) {
 static int run_one(const ColvoCmd& c, int k, colvo_stream_t s) {
     switch (c.op) {
         case COLVO_CMD_CONV_FWD:
+            if (c.i[0]) return pose_front_fwd(c, (hipStream_t)s);      // a chain of layers in one launch (csrc/pose_front.hip)
             return colvo_conv_fwd(&c.desc, c.p[0], c.p[1], c.p[2], (const float*)c.p[3], (void*)c.p[4], s);
         case COLVO_CMD_CONV_DGRAD:
             return colvo_conv_dgrad(&c.desc, c.i[0], c.p[0], c.p[1], c.p[2], (void*)c.p[3], c.i[1], s);
@@ -133,6 +134,7 @@ static int run_one(const ColvoCmd& c, int k, colvo_stream_t s) {
                                        (const float*)c.p[4], (const float*)c.p[8], (const float*)c.p[9], c.i[1], c.i[2], c.i[3],
                                        c.f[0], c.f[1], (void*)c.p[5], (float*)c.p[6], (float*)c.p[7], s);
         case COLVO_CMD_CONV_DGRAD_PLANES:
+            if (c.p[3]) return pose_front_bwd(c, (hipStream_t)s);      // the input-gradient chain in front of it in the same launch
             return colvo_conv_dgrad_planes(&c.desc, c.p[0], (const float*)c.p[1], c.i[0], c.i[1], (float*)c.p[2], c.i[2], s);
         case COLVO_CMD_CONV_BWD_FUSED:
             if (c.p[9]) return colvo_conv_bwd_fused_det(&c.desc, c.p[0], c.p[1], c.p[2], c.i[0], (void*)c.p[3], (float*)c.p[4], (float*)c.p[5],

@@ -104,6 +104,14 @@ namespace tune {
     X(head_wgrad_wgs, 1024, "grid of k_head_wgrad_mfma (one partial row per workgroup)") \
     X(planes_mfma, 1, "input gradient of PoseNet's first layer w.r.t. the two depth channels by MFMA (k_dgrad_planes_s2_mfma)") \
     X(planes_groups, 2, "... 16-block groups a wave walks (its weight set-up is amortised over them)") \
+    X(pose_front, 1, "PoseNet's three front layers (8 -> 16 -> 32 -> 64, stride 2, bf16) as ONE forward launch "        \
+                     "(k_pose_front_fwd, csrc/pose_front.hip: a workgroup carries a 4 x 8 or 4 x 10 tile of conv3 through all three "  \
+                     "levels, weights resident in LDS) where each layer would otherwise be a one-tile launch at the floor; same bits.  " \
+                     "8 pairs of 256x320, step in ms, three alternating rounds: parent 1.3955-1.4025, forward chain alone 1.3836-1.3920, "         \
+                     "both chains 1.3682-1.3824; level at 64 pairs, where it is not selected (profiles/pose_front_ab.md)")                                                                                              \
+    X(pose_front_bwd, 1, "... and their input-gradient chain g3 -> g2 -> g1 -> the two depth planes as ONE launch (k_pose_front_bwd) in "  \
+                         "place of two k_dgrad_s2 launches and k_dgrad_planes_s2_mfma; only with pose_front on.  On top of the forward chain: "     \
+                         "1.3836-1.3920 -> 1.3682-1.3824 ms (profiles/pose_front_ab.md)")    \
     X(fwd16, 1, "the 16 -> 16 full-resolution layer and the depth head behind it in one pass (k_fwd16_head, csrc/fwd16.hip)")          \
     X(fwd16_wgs, 1024, "... its grid (at least; one workgroup per 8 tiles beyond that)")                                              \
     X(fwd16_tiles_per_wg, 32, "... tiles per workgroup beyond fwd16_wgs (grid in whole rounds of 1024)")                                       \

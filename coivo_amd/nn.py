@@ -1055,13 +1055,25 @@ class PoseNet(_ArenaModule):
             for i, c in enumerate(POSE_CH, start=1):
                 P[i] = ops.conv_desc(dt, B, h, w, cin, c, stride=2)
                 h, w, cin = P[i].Ho, P[i].Wo, c
+        # the planner's answer follows the tuning table (`pose_front`): asked per call, and part of the recorded pass's key
+        P["front"] = front = ops.pose_front_plan(P[1]) is not None
         out = torch.empty(8 * B, device=tgt.device, dtype=torch.float32)     # planar: [pose Bx6 | a B | b B]
-        inst = self._acquire((B, H, W, dt, has_depth))
+        inst = self._acquire((B, H, W, dt, front, has_depth))
 
         def body():
             x = filled if filled is not None else ops.pack_nchw(srcs, 8, dt)
             A = {"in": x}
-            for i in range(1, 8):
+            first = 1
+            if front:
+                # conv1-conv3 as one launch (csrc/pose_front.hip): all three maps are written, the bits are the three launches'
+                lays = []
+                for i in range(1, 4):
+                    L, d = getattr(self, f"conv{i}"), P[i]
+                    A[i] = torch.empty(d.B, d.Ho, d.Wo, d.Cout, device=x.device, dtype=x.dtype)
+                    lays.append((L.w_fwd, L.bias.data, A[i]))
+                ops.conv_fwd_chain(P[1], x, lays)
+                x, first = A[3], 4
+            for i in range(first, 8):
                 x = _conv(x, getattr(self, f"conv{i}"), P[i])
                 A[i] = x
             ops.pose_head_fwd(x, self.pred.w_master, self.pred.bias.data, out)
@@ -1086,6 +1098,8 @@ class PoseNet(_ArenaModule):
         # both depth gradients from one launch: [2][B,1,H,W], each half a contiguous tensor of its own
         d_tr = torch.empty(2, B, 1, H, W, device=dev, dtype=torch.float32) if has_depth else None
         d_t, d_r = (d_tr[0], d_tr[1]) if has_depth else (None, None)
+        # the input-gradient chain ends in the depth planes: only a call with depth maps has it (asked per call, as in the forward pass)
+        chain = bool(has_depth) and _lib.dev_env("COLVO_NO_DGRAD_PLANES") is None and ops.pose_front_plan(P[1], 1) is not None
 
         def body():
             self._bwd_begin()
@@ -1098,6 +1112,14 @@ class PoseNet(_ArenaModule):
                 L = getattr(self, f"conv{i}")
                 src = (filled if filled is not None else A["in"]) if i == 1 else A[i - 1]
                 self._conv_wgrad(L, P[i], src, None, g)
+                if i == 3 and chain:
+                    # g3 -> g2 -> g1 -> d_tr in one launch (csrc/pose_front.hip; the bits of the three launches below).  conv3's
+                    # weight gradient was forked before it, conv2's and conv1's follow it, in today's order
+                    g2, g1 = torch.empty_like(A[2]), torch.empty_like(A[1])
+                    ops.conv_dgrad_chain(P[1], g, L.w_bwd, self.conv2.w_bwd, A[2], A[1], g2, g1, self.conv1.w_master, 6, 2, d_tr)
+                    self._conv_wgrad(self.conv2, P[2], A[1], None, g2)
+                    self._conv_wgrad(self.conv1, P[1], filled if filled is not None else A["in"], None, g1)
+                    break
                 if i > 1:
                     dx = torch.empty_like(src)
                     ops.conv_dgrad(P[i], 0, g, L.w_bwd, src, dx, False)
@@ -1117,7 +1139,7 @@ class PoseNet(_ArenaModule):
             ext["d_tr"] = d_tr
         if filled is not None:
             ext["in"] = filled
-        which = "bwd:" + ",".join(sorted(grads))       # a missing (None) gradient changes the recorded commands
+        which = "bwd:" + ",".join(sorted(grads)) + (",chain" if chain else "")     # a missing (None) gradient changes the recorded commands
         self._run_pass(inst, which, ext, body)
         return d_t, d_r
 

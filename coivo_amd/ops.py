@@ -58,6 +58,33 @@ def conv_fwd(d: ConvDesc, x0, x1, w_fwd, bias, y) -> None:
     _issue(_lib.CMD_CONV_FWD, d, (x0, x1, w_fwd, bias, y))
 
 
+def pose_front_plan(d1: ConvDesc, direction: int = 0) -> Optional[Tuple[int, int, int, int]]:
+    """(workgroups, tile rows, tile columns, LDS bytes) of the chain launch that replaces PoseNet's three front layers behind the
+    first layer's descriptor d1, or None where the chain is not selected (include/colvo.h colvo_pose_front_plan; no GPU needed)."""
+    out = (C.c_int32 * 4)()
+    if not _lib.load().colvo_pose_front_plan(C.byref(d1), int(direction), out):
+        return None
+    return tuple(int(v) for v in out)
+
+
+def conv_fwd_chain(d1: ConvDesc, x, layers) -> None:
+    """PoseNet's three front layers in one launch: layers = [(w_fwd, bias, y)] * 3, d1 the first layer's descriptor (the chain form of
+    CMD_CONV_FWD; refused where pose_front_plan(d1) is None)."""
+    if len(layers) != 3:
+        raise ValueError("conv_fwd_chain: three layers")
+    flat = [t for lay in layers for t in lay]
+    _need_cuda(x, *flat)
+    _issue(_lib.CMD_CONV_FWD, d1, [x, None] + flat, [3] + [lay[2].shape[-1] for lay in layers])
+
+
+def conv_dgrad_chain(d1: ConvDesc, g3, w_bwd3, w_bwd2, act2, act1, g2, g1, w_master1, c_begin: int, c_count: int, dst) -> None:
+    """The input gradients behind conv3's output gradient g3 in one launch: g2 (masked by act2 > 0), g1 (masked by act1 > 0) and the
+    fp32 planes dst [c_count, B, 1, Hi, Wi] of conv1's input gradient (the chain form of CMD_CONV_DGRAD_PLANES; refused where
+    pose_front_plan(d1, 1) is None)."""
+    _need_cuda(g3, w_bwd3, w_bwd2, act2, act1, g2, g1, w_master1, dst)
+    _issue(_lib.CMD_CONV_DGRAD_PLANES, d1, (g1, w_master1, dst, g3, w_bwd3, w_bwd2, act2, act1, g2, g1), (c_begin, c_count, 0))
+
+
 def conv_dgrad(d: ConvDesc, src: int, dy, w_bwd, relu_mask, dx, accumulate: bool) -> None:
     _need_cuda(dy, w_bwd, relu_mask, dx)
     _issue(_lib.CMD_CONV_DGRAD, d, (dy, w_bwd, relu_mask, dx), (src, int(accumulate)))

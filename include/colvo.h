@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define COLVO_ABI_VERSION 24
+#define COLVO_ABI_VERSION 25
 
 typedef void* colvo_stream_t; /* hipStream_t */
 
@@ -180,6 +180,18 @@ typedef struct ColvoConvDesc {
  * in `dtype`; bias fp32 [Cout]. */
 int colvo_conv_fwd(const ColvoConvDesc* d, const void* x0, const void* x1, const void* w_fwd,
                    const float* bias, void* y, colvo_stream_t stream);
+
+/* PoseNet's three front layers (8 -> 16 -> 32 -> 64 channels, 3x3, stride 2, bias + ReLU, bf16) as ONE launch: the chain form of
+ * COLVO_CMD_CONV_FWD (below; csrc/pose_front.hip).  Plan query, no side effect: reads d1 -- the FIRST layer's descriptor -- and the
+ * tuning table, calls no HIP and counts no form.  direction 0: the forward chain (writes all three activation maps; the bits of
+ * three colvo_conv_fwd calls).  direction 1: the input-gradient chain, the chain form of COLVO_CMD_CONV_DGRAD_PLANES: from conv3's
+ * output gradient g3 it writes g2 = dgrad(conv3) masked by act2 > 0, g1 = dgrad(conv2) masked by act1 > 0 and conv1's input
+ * gradient w.r.t. two channels as fp32 planes (the bits of two colvo_conv_dgrad calls and colvo_conv_dgrad_planes; tuning entry
+ * `pose_front_bwd` on top of `pose_front`).  Returns 0 when the chain is not selected (tuning entry off, f32, H or W not a multiple
+ * of 8, other channel counts, or a batch at which one of the three layers would not take the one-tile form of colvo_conv_fwd --
+ * resp. one of the replaced input-gradient launches not k_dgrad_s2 / k_dgrad_planes_s2_mfma: the chain's bits are those forms'
+ * bits); otherwise 1, and out (may be NULL) receives {workgroups, conv3 tile rows, conv3 tile columns, LDS bytes}. */
+int colvo_pose_front_plan(const ColvoConvDesc* d1, int direction, int32_t* out);
 
 /* Input gradient of source `src` (0 or 1).  dy[B,Ho,Wo,Cout] must already be the gradient w.r.t. the
  * pre-activation (see relu_mask below).  w_bwd: weights packed [C0+C1][ksize*ksize][Cout].
@@ -975,7 +987,8 @@ int colvo_read_npy_u8_frames(const char* const* paths, int n, int h, int w, uint
  * command issued by colvo_run_command.                                                         *
  * ------------------------------------------------------------------------------------------- */
 enum {
-    COLVO_CMD_CONV_FWD = 1,      /* p: x0 x1 w_fwd bias y */
+    COLVO_CMD_CONV_FWD = 1,      /* p: x0 x1 w_fwd bias y; chain form (i[0] = 3, colvo_pose_front_plan): p: x - w1 b1 y1 w2 b2 y2 w3 b3 y3;
+                                    i: 3 and the three output channel counts (16 32 64); desc: the first layer's */
     COLVO_CMD_CONV_DGRAD,        /* i: src accumulate; p: dy w_bwd relu_mask dx */
     COLVO_CMD_CONV_WGRAD,        /* p: x0 x1 dy dw db scratch; i: scratch_bytes slabs_only arena_is_zero (scratch != NULL:
                                     colvo_conv_wgrad_det, or with slabs_only colvo_conv_wgrad_slabs; scratch == NULL and arena_is_zero:
@@ -992,7 +1005,8 @@ enum {
     COLVO_CMD_DEPTH_HEAD_BWD_PARTS, /* i: dtype B H W C; f: min max; p: x w depth g_first g_second g_raw scale_a scale_b scratch dx g_raw_second */
     COLVO_CMD_CONV_DGRAD_BOTH,    /* p: dy w_bwd relu_mask0 relu_mask1 dx0 dx1 */
     COLVO_CMD_WGRAD_REDUCE_GROUP, /* p: sets (HOST pointer to ColvoWgradSlabs[n], alive as long as the list); i: n */
-    COLVO_CMD_CONV_DGRAD_PLANES,  /* p: dy w_master dst; i: c_begin c_count accumulate */
+    COLVO_CMD_CONV_DGRAD_PLANES,  /* p: dy w_master dst; i: c_begin c_count accumulate; chain form (p[3] != NULL, colvo_pose_front_plan
+                                   * direction 1): p: g1 w_master dst g3 w_bwd3 w_bwd2 act2 act1 g2 g1 (g2, g1: written); desc: conv1's */
     COLVO_CMD_CONV_BWD_FUSED,     /* p: dy w_bwd x dx dw db head_dpre head_w head_partials scratch; i: relu_mask scratch_bytes
                                    * (p[9] scratch != NULL: colvo_conv_bwd_fused_det; with p[4] dw == NULL the rows stay in the scratch) */
     COLVO_CMD_HEAD_WGRAD_REDUCE,  /* p: partials dw db; i: rows */
