@@ -158,17 +158,14 @@ __global__ __launch_bounds__(NT) void k_raster_resolve(const unsigned long long*
                                                        float* __restrict__ out_depth, int32_t* __restrict__ out_index,
                                                        float* __restrict__ out_colors, float* __restrict__ out_normal,
                                                        int32_t* __restrict__ face_pixels, int32_t* __restrict__ counters) {
-    __shared__ int sm_stats[NT / 64][1];
-    const int n = blockIdx.y;
-    const size_t HW = (size_t)g.H * g.W;
-    const size_t p = (size_t)blockIdx.x * NT + threadIdx.x;
-    const bool in = p < HW;
-    const unsigned long long key = in ? keys[(size_t)n * HW + p] : EMPTY;
-    const bool hit = key != EMPTY;
-    if (in) {
-        const int f = (int)(unsigned)key;
-        out_depth[(size_t)n * HW + p] = hit ? __uint_as_float((unsigned)(key >> 32)) : __builtin_inff();
-        out_index[(size_t)n * HW + p] = hit ? f : -1;
+    const ResolvePixel r = resolve_open(keys, g);
+    const int n = r.n;
+    const size_t HW = r.HW, p = r.p;
+    bool hit = false;
+    if (r.in) {
+        unsigned row;
+        hit = resolve_pixel(r, nullptr, out_depth, out_index, nullptr, row);                   // (the colours are interpolated below)
+        const int f = (int)row;
         float col[3] = {0.0f, 0.0f, 0.0f}, nrm[3] = {0.0f, 0.0f, 0.0f};
         int idx[3];
         if ((int)hit & (int)(out_colors != nullptr || out_normal != nullptr) && load_face(faces, f, g.M, mesh.V, idx)) {
@@ -218,18 +215,12 @@ __global__ __launch_bounds__(NT) void k_raster_resolve(const unsigned long long*
         }
         if (face_pixels && (int)hit & (int)(f >= 0) & (int)(f < g.M)) atomicAdd(face_pixels + f, 1);
     }
-    const int cnt[1] = {(int)__popcll(__ballot(hit))};
-    striped_counter_add(cnt, sm_stats, counters + ((size_t)n * MAX_LINES + blockIdx.x % (unsigned)MAX_LINES) * LINE_INTS + LINE_COVERED);
+    resolve_close(hit, n, LINE_COVERED, counters);
 }
 
-// grid N, one wave: out_stats[n][k] = sum over the frame's counter lines
+// grid N, one wave: the draw's seven counts, then covered
 __global__ __launch_bounds__(64) void k_raster_stats(const int32_t* __restrict__ counters, int32_t* __restrict__ out_stats) {
-    const int n = blockIdx.x, k = threadIdx.x;
-    if (k >= N_STATS) return;
-    int t = 0;
-#pragma unroll
-    for (int l = 0; l < MAX_LINES; ++l) t += counters[((size_t)n * MAX_LINES + l) * LINE_INTS + k];
-    out_stats[(size_t)n * N_STATS + k] = t;
+    stats_row<N_STATS, LINE_COVERED, 7>(counters, out_stats);
 }
 
 }  // namespace
@@ -244,35 +235,25 @@ extern "C" int colvo_render_mesh(const float* vertices, const int32_t* faces, co
     COLVO_CHECK_ARG(V >= 0 && F >= 0, "colvo_render_mesh: bad mesh V=%d F=%d (0 <= V, F < 2^31)", V, F);
     COLVO_CHECK_ARG(render_shape(N, H, W) && H <= 16384 && W <= 16384,
                     "colvo_render_mesh: bad shape N=%d H=%d W=%d (1 <= N <= 65535, 1 <= H, W <= 16384, N*H*W < 2^31)", N, H, W);
-    COLVO_CHECK_ARG(max_depth > 0.0f && max_depth < __builtin_inff(), "colvo_render_mesh: bad max_depth %g (finite and positive)",
-                    (double)max_depth);
     COLVO_CHECK_ARG(cull_back == 0 || cull_back == 1, "colvo_render_mesh: bad cull_back %d (0 or 1)", cull_back);
-    COLVO_CHECK_ARG((vertices || V == 0) && (faces || F == 0) && K && cam2world && scratch && out_depth && out_index && out_stats,
-                    "colvo_render_mesh: null pointer argument");
-    COLVO_CHECK_ARG(out_colors ? (colors || V == 0) : !colors,
-                    "colvo_render_mesh: null pointer argument: colors and out_colors go together");
-    COLVO_CHECK_ARG(aligned16(scratch), "colvo_render_mesh: scratch must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     Geom g;
-    g.M = F; g.N = N; g.H = H; g.W = W; g.max_splat = 0; g.radius = 0.0f; g.max_depth = max_depth;
+    Scratch w;
+    if (int e = begin_render("colvo_render_mesh", (vertices || V == 0) && (faces || F == 0), colors || V == 0, colors, K, cam2world, F, N, H,
+                             W, 0.0f, 0, max_depth, scratch, out_depth, out_index, out_colors, out_stats, s, g, w))
+        return e;
     const double coop = TUNE_F(raster_coop_min_pixels);
     Mesh mesh;
     mesh.V = V;
     mesh.cull_back = cull_back;
     mesh.coop_min = coop >= 2147483647.0 ? 2147483647 : coop >= 0.0 ? (int)coop : 0;             // (a NaN counts as 0)
-    const Scratch w = layout(scratch, N, H, W);
-    launch_clear(w, N, H, W, s);
-    COLVO_CHECK_LAUNCH("k_render_clear");
     if (out_face_pixels && F > 0) {
         colvo::launch(k_raster_zero, dim3(blocks_of(F, NT)), dim3(NT), 0, s, out_face_pixels, F);
         COLVO_CHECK_LAUNCH("k_raster_zero");
     }
     if (F > 0 && V > 0) {
-        const dim3 grid(blocks_of(F, NT), blocks_of(N, FRAME_GROUP));
-        if (TUNE(render_load_first))
-            colvo::launch(k_raster_draw<true>, grid, dim3(NT), 0, s, vertices, faces, K, cam2world, g, mesh, w.keys, w.counters);
-        else
-            colvo::launch(k_raster_draw<false>, grid, dim3(NT), 0, s, vertices, faces, K, cam2world, g, mesh, w.keys, w.counters);
+        launch_draw(k_raster_draw<true>, k_raster_draw<false>, dim3(blocks_of(F, NT), blocks_of(N, FRAME_GROUP)), s, vertices, faces, K,
+                    cam2world, g, mesh, w.keys, w.counters);
         COLVO_CHECK_LAUNCH("k_raster_draw");
     }
     colvo::launch(k_raster_resolve, dim3(blocks_of((long long)H * W, NT), N), dim3(NT), 0, s, (const unsigned long long*)w.keys, vertices,

@@ -11,6 +11,7 @@
 //                     barrier per frame is enough.
 //   k_render_resolve  one thread per pixel: key -> depth, index, gathered colour; covered pixels counted by ballot.
 //   k_render_stats    one wave per frame: the counter lines summed into out_stats[N][4].
+// The frame of the last two and the entry point's checks are render_common.h's, shared with surfels.hip and raster.hip.
 //
 // Every float32 operation is individually rounded -- contraction is off for this whole file --, the minimum is an integer minimum and
 // every sum is an integer: a call's bits do not depend on scheduling or on the stream.
@@ -27,6 +28,7 @@ namespace {
 using namespace render_common;
 
 constexpr int N_STATS = 4;                 // front, drawn, clipped, covered
+constexpr int LINE_COVERED = 3;            // a counter line: front, drawn, clipped (the splat's), covered (the resolve's)
 
 // grid (ceil(M / NT), ceil(N / FRAME_GROUP))
 template <bool LOAD_FIRST>
@@ -71,27 +73,16 @@ __global__ __launch_bounds__(NT) void k_render_splat(const float* __restrict__ p
 __global__ __launch_bounds__(NT) void k_render_resolve(const unsigned long long* __restrict__ keys, const float* __restrict__ colors, Geom g,
                                                        float* __restrict__ out_depth, int32_t* __restrict__ out_index,
                                                        float* __restrict__ out_colors, int32_t* __restrict__ counters) {
-    __shared__ int sm_stats[NT / 64][1];
-    const int n = blockIdx.y;
-    const size_t HW = (size_t)g.H * g.W;
-    const size_t p = (size_t)blockIdx.x * NT + threadIdx.x;
-    const bool in = p < HW;
-    const unsigned long long key = in ? keys[(size_t)n * HW + p] : EMPTY;
+    const ResolvePixel r = resolve_open(keys, g);
     bool hit = false;
     unsigned idx;
-    if (in) hit = resolve_pixel(key, colors, HW, (size_t)n * HW + p, (size_t)n * 3 * HW + p, out_depth, out_index, out_colors, idx);
-    const int cnt[1] = {(int)__popcll(__ballot(hit))};
-    striped_counter_add(cnt, sm_stats, counters + ((size_t)n * MAX_LINES + blockIdx.x % (unsigned)MAX_LINES) * LINE_INTS + 3);
+    if (r.in) hit = resolve_pixel(r, colors, out_depth, out_index, out_colors, idx);
+    resolve_close(hit, r.n, LINE_COVERED, counters);
 }
 
-// grid N, one wave: out_stats[n][k] = sum over the frame's counter lines
+// grid N, one wave
 __global__ __launch_bounds__(64) void k_render_stats(const int32_t* __restrict__ counters, int32_t* __restrict__ out_stats) {
-    const int n = blockIdx.x, k = threadIdx.x;
-    if (k >= N_STATS) return;
-    int t = 0;
-#pragma unroll
-    for (int l = 0; l < MAX_LINES; ++l) t += counters[((size_t)n * MAX_LINES + l) * LINE_INTS + k];
-    out_stats[(size_t)n * N_STATS + k] = t;
+    stats_row<N_STATS, LINE_COVERED, 3>(counters, out_stats);
 }
 
 }  // namespace
@@ -108,29 +99,15 @@ extern "C" int colvo_render_cloud(const float* points, const float* colors, int 
                                   int W, float radius, int max_splat, float max_depth, void* scratch, float* out_depth,
                                   int32_t* out_index, float* out_colors, int32_t* out_stats, colvo_stream_t stream) {
     COLVO_CHECK_ARG(M >= 0, "colvo_render_cloud: bad point count M=%d (0 <= M < 2^31)", M);
-    COLVO_CHECK_ARG((points || M == 0) && K && cam2world && scratch && out_depth && out_index && out_stats,
-                    "colvo_render_cloud: null pointer argument");
-    COLVO_CHECK_ARG(out_colors ? (colors || M == 0) : !colors,
-                    "colvo_render_cloud: null pointer argument: colors and out_colors go together");
-    COLVO_CHECK_ARG(render_shape(N, H, W), "colvo_render_cloud: bad shape N=%d H=%d W=%d (1 <= N <= 65535, H*W < 2^30, N*H*W < 2^31)", N, H,
-                    W);
-    COLVO_CHECK_ARG(max_splat >= 0 && max_splat <= MAX_SPLAT, "colvo_render_cloud: bad max_splat %d (0 .. %d)", max_splat, MAX_SPLAT);
-    COLVO_CHECK_ARG(radius >= 0.0f && radius < __builtin_inff(), "colvo_render_cloud: bad radius %g (finite and >= 0)", (double)radius);
-    COLVO_CHECK_ARG(max_depth > 0.0f && max_depth < __builtin_inff(), "colvo_render_cloud: bad max_depth %g (finite and positive)",
-                    (double)max_depth);
-    COLVO_CHECK_ARG(aligned16(scratch), "colvo_render_cloud: scratch must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     Geom g;
-    g.M = M; g.N = N; g.H = H; g.W = W; g.max_splat = max_splat; g.radius = radius; g.max_depth = max_depth;
-    const Scratch w = layout(scratch, N, H, W);
-    launch_clear(w, N, H, W, s);
-    COLVO_CHECK_LAUNCH("k_render_clear");
+    Scratch w;
+    if (int e = begin_render("colvo_render_cloud", points || M == 0, colors || M == 0, colors, K, cam2world, M, N, H, W, radius, max_splat,
+                             max_depth, scratch, out_depth, out_index, out_colors, out_stats, s, g, w))
+        return e;
     if (M > 0) {
-        const dim3 grid(blocks_of(M, NT), blocks_of(N, FRAME_GROUP));
-        if (TUNE(render_load_first))
-            colvo::launch(k_render_splat<true>, grid, dim3(NT), 0, s, points, K, cam2world, g, w.keys, w.counters);
-        else
-            colvo::launch(k_render_splat<false>, grid, dim3(NT), 0, s, points, K, cam2world, g, w.keys, w.counters);
+        launch_draw(k_render_splat<true>, k_render_splat<false>, dim3(blocks_of(M, NT), blocks_of(N, FRAME_GROUP)), s, points, K, cam2world,
+                    g, w.keys, w.counters);
         COLVO_CHECK_LAUNCH("k_render_splat");
     }
     colvo::launch(k_render_resolve, dim3(blocks_of((long long)H * W, NT), N), dim3(NT), 0, s, (const unsigned long long*)w.keys, colors, g,

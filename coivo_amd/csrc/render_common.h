@@ -1,9 +1,11 @@
-// render_common.h -- what the two renderers share: render.hip draws screen-aligned squares, surfels.hip draws
-// oriented discs.  Steps 1 to 5 of colvo_render_cloud's contract (camera point, front, centre, half-widths, footprint) are ONE routine
-// here, so a point without a normal is drawn by surfels.hip with the bits render.hip gives it; so are the key buffer's layout and
-// clear and the decoding of a winning key.  A file that includes this header must have contraction off in front of the include.
+// render_common.h -- what the renderers share: render.hip draws screen-aligned squares, surfels.hip
+// draws oriented discs, raster.hip triangles.  Steps 1 to 5 of colvo_render_cloud's contract (camera point, front, centre, half-widths,
+// footprint) are ONE routine here, so a point without a normal is drawn by surfels.hip with the bits render.hip gives it; so are the
+// key buffer's layout and clear, the decoding of a winning key, the frame of a resolve kernel, the stats kernel's body, and what the
+// entry points check and launch alike.  A file that includes this header must have contraction off in front of the include.
 #pragma once
 #include "scene.h"
+#include "tuning.h"
 
 #pragma clang fp contract(off)
 
@@ -96,13 +98,32 @@ __device__ __forceinline__ void offer_key(unsigned long long* p, unsigned long l
     atomicMin(p, key);
 }
 
-// one pixel of k_render_resolve / k_surfel_resolve: key -> depth, index, gathered colour.  Returns whether a point landed; idx < M then.
-__device__ __forceinline__ bool resolve_pixel(unsigned long long key, const float* __restrict__ colors, size_t HW, size_t frame_pixel,
-                                              size_t colour_pixel, float* __restrict__ out_depth, int32_t* __restrict__ out_index,
-                                              float* __restrict__ out_colors, unsigned& idx) {
-    const bool hit = key != EMPTY;
-    idx = (unsigned)key;
-    out_depth[frame_pixel] = hit ? __uint_as_float((unsigned)(key >> 32)) : __builtin_inff();
+// the opening of a resolve kernel, grid (ceil(H * W / NT), N): the frame, the pixel, whether it is inside the image, its key
+struct ResolvePixel {
+    int n;
+    size_t HW, p;
+    bool in;
+    unsigned long long key;
+};
+
+__device__ __forceinline__ ResolvePixel resolve_open(const unsigned long long* __restrict__ keys, const Geom& g) {
+    ResolvePixel r;
+    r.n = blockIdx.y;
+    r.HW = (size_t)g.H * g.W;
+    r.p = (size_t)blockIdx.x * NT + threadIdx.x;
+    r.in = r.p < r.HW;
+    r.key = r.in ? keys[(size_t)r.n * r.HW + r.p] : EMPTY;
+    return r;
+}
+
+// one pixel inside the image: key -> depth, index and, with out_colors, the gathered colour of row idx of `colors` (a renderer that
+// makes its colours otherwise passes none).  Returns whether something landed; idx is its row then.
+__device__ __forceinline__ bool resolve_pixel(const ResolvePixel& r, const float* __restrict__ colors, float* __restrict__ out_depth,
+                                              int32_t* __restrict__ out_index, float* __restrict__ out_colors, unsigned& idx) {
+    const bool hit = r.key != EMPTY;
+    const size_t frame_pixel = (size_t)r.n * r.HW + r.p;
+    idx = (unsigned)r.key;
+    out_depth[frame_pixel] = hit ? __uint_as_float((unsigned)(r.key >> 32)) : __builtin_inff();
     out_index[frame_pixel] = hit ? (int)idx : -1;
     if (out_colors) {
         float c[3] = {0.0f, 0.0f, 0.0f};
@@ -110,11 +131,33 @@ __device__ __forceinline__ bool resolve_pixel(unsigned long long key, const floa
 #pragma unroll
             for (int k = 0; k < 3; ++k) c[k] = colors[(size_t)idx * 3 + k];
         }
-        float* o = out_colors + colour_pixel;
+        float* o = out_colors + (size_t)r.n * 3 * r.HW + r.p;
 #pragma unroll
-        for (int k = 0; k < 3; ++k) o[k * HW] = c[k];
+        for (int k = 0; k < 3; ++k) o[k * r.HW] = c[k];
     }
     return hit;
+}
+
+// ... and its close: the covered pixels counted by ballot into slot line_covered of the frame's counter lines.  Every thread of the
+// workgroup comes here.
+__device__ __forceinline__ void resolve_close(bool hit, int n, int line_covered, int32_t* __restrict__ counters) {
+    __shared__ int sm_stats[NT / 64][1];
+    const int cnt[1] = {(int)__popcll(__ballot(hit))};
+    striped_counter_add(cnt, sm_stats, counters + ((size_t)n * MAX_LINES + blockIdx.x % (unsigned)MAX_LINES) * LINE_INTS + line_covered);
+}
+
+// a stats kernel, grid N, one wave: out_stats[n][k] = sum over the frame's counter lines.  The draw kernel's counts keep their order;
+// the covered pixels, slot LINE_COVERED of a counter line, go to column OUT_COVERED of the N_STATS columns.  A renderer's kernel is
+// this one line under the renderer's own name (listings and profiles tell the renderers apart by it).
+template <int N_STATS, int LINE_COVERED, int OUT_COVERED>
+__device__ __forceinline__ void stats_row(const int32_t* __restrict__ counters, int32_t* __restrict__ out_stats) {
+    const int n = blockIdx.x, k = threadIdx.x;
+    if (k >= N_STATS) return;
+    const int slot = k < OUT_COVERED ? k : k == OUT_COVERED ? LINE_COVERED : k - 1;
+    int t = 0;
+#pragma unroll
+    for (int l = 0; l < MAX_LINES; ++l) t += counters[((size_t)n * MAX_LINES + l) * LINE_INTS + slot];
+    out_stats[(size_t)n * N_STATS + k] = t;
 }
 
 inline bool render_shape(int N, int H, int W) {
@@ -136,12 +179,33 @@ inline Scratch layout(void* base, int N, int H, int W) {
     return s;
 }
 
-// k_render_clear for a call's scratch; the launch's error is the caller's to check
-inline void launch_clear(const Scratch& w, int N, int H, int W, hipStream_t s) {
+// What the three entry points refuse and set up alike, under the entry point's own name `who`: the required pointers (`drawn`: what
+// is drawn is there, or there is none of it), colours with their output, the shape, the policy, the scratch; then the Geom (rows:
+// Geom::M), the scratch's layout and k_render_clear.  -> 0, or the error to return.
+inline int begin_render(const char* who, bool drawn, bool colours_there, const void* colors, const void* K, const void* cam2world, int rows,
+                        int N, int H, int W, float radius, int max_splat, float max_depth, void* scratch, const void* out_depth,
+                        const void* out_index, const void* out_colors, const void* out_stats, hipStream_t s, Geom& g, Scratch& w) {
+    COLVO_CHECK_ARG(drawn && K && cam2world && scratch && out_depth && out_index && out_stats, "%s: null pointer argument", who);
+    COLVO_CHECK_ARG(out_colors ? colours_there : !colors, "%s: null pointer argument: colors and out_colors go together", who);
+    COLVO_CHECK_ARG(render_shape(N, H, W), "%s: bad shape N=%d H=%d W=%d (1 <= N <= 65535, H*W < 2^30, N*H*W < 2^31)", who, N, H, W);
+    COLVO_CHECK_ARG(max_splat >= 0 && max_splat <= MAX_SPLAT, "%s: bad max_splat %d (0 .. %d)", who, max_splat, MAX_SPLAT);
+    COLVO_CHECK_ARG(radius >= 0.0f && radius < __builtin_inff(), "%s: bad radius %g (finite and >= 0)", who, (double)radius);
+    COLVO_CHECK_ARG(max_depth > 0.0f && max_depth < __builtin_inff(), "%s: bad max_depth %g (finite and positive)", who, (double)max_depth);
+    COLVO_CHECK_ARG(aligned16(scratch), "%s: scratch must be 16-byte aligned", who);
+    g.M = rows; g.N = N; g.H = H; g.W = W; g.max_splat = max_splat; g.radius = radius; g.max_depth = max_depth;
+    w = layout(scratch, N, H, W);
     const long long total = (long long)N * H * W;
     const int n_counters = N * MAX_LINES * LINE_INTS;
     const long long clear_threads = (total >> 1) + 1 > n_counters ? (total >> 1) + 1 : n_counters;
     colvo::launch(k_render_clear, dim3(blocks_of(clear_threads, NT)), dim3(NT), 0, s, w.keys, total, w.counters, n_counters);
+    COLVO_CHECK_LAUNCH("k_render_clear");
+    return 0;
+}
+
+// a draw kernel in the form tuning.h render_load_first selects: the relaxed load in front of the atomic minimum, or not
+template <typename... P, typename... A>
+inline void launch_draw(void (*load_first)(P...), void (*plain)(P...), dim3 grid, hipStream_t s, A&&... a) {
+    colvo::launch(TUNE(render_load_first) ? load_first : plain, grid, dim3(NT), 0, s, static_cast<A&&>(a)...);
 }
 
 }  // namespace render_common

@@ -112,41 +112,29 @@ __global__ __launch_bounds__(NT) void k_surfel_resolve(const unsigned long long*
                                                        const float* __restrict__ M, Geom g, float* __restrict__ out_depth,
                                                        int32_t* __restrict__ out_index, float* __restrict__ out_colors,
                                                        float* __restrict__ out_normal, int32_t* __restrict__ counters) {
-    __shared__ int sm_stats[NT / 64][1];
-    const int n = blockIdx.y;
-    const size_t HW = (size_t)g.H * g.W;
-    const size_t p = (size_t)blockIdx.x * NT + threadIdx.x;
-    const bool in = p < HW;
-    const unsigned long long key = in ? keys[(size_t)n * HW + p] : EMPTY;
+    const ResolvePixel r = resolve_open(keys, g);
     bool hit = false;
     unsigned idx;
-    if (in) {
-        hit = resolve_pixel(key, colors, HW, (size_t)n * HW + p, (size_t)n * 3 * HW + p, out_depth, out_index, out_colors, idx);
+    if (r.in) {
+        hit = resolve_pixel(r, colors, out_depth, out_index, out_colors, idx);
         if (out_normal) {
             float m[3] = {0.0f, 0.0f, 0.0f};
             if (hit) {
                 const float* q = normals + (size_t)idx * 3;
                 const float N0 = q[0], N1 = q[1], N2 = q[2];
-                if (has_normal(N0, N1, N2)) cam_normal(load_cam(K, M, n), N0, N1, N2, m);
+                if (has_normal(N0, N1, N2)) cam_normal(load_cam(K, M, r.n), N0, N1, N2, m);
             }
-            float* o = out_normal + (size_t)n * 3 * HW + p;
+            float* o = out_normal + (size_t)r.n * 3 * r.HW + r.p;
 #pragma unroll
-            for (int k = 0; k < 3; ++k) o[k * HW] = m[k];
+            for (int k = 0; k < 3; ++k) o[k * r.HW] = m[k];
         }
     }
-    const int cnt[1] = {(int)__popcll(__ballot(hit))};
-    striped_counter_add(cnt, sm_stats, counters + ((size_t)n * MAX_LINES + blockIdx.x % (unsigned)MAX_LINES) * LINE_INTS + LINE_COVERED);
+    resolve_close(hit, r.n, LINE_COVERED, counters);
 }
 
-// grid N, one wave: out_stats[n][k] = sum over the frame's counter lines
+// grid N, one wave: front, drawn, clipped, covered, culled, flat
 __global__ __launch_bounds__(64) void k_surfel_stats(const int32_t* __restrict__ counters, int32_t* __restrict__ out_stats) {
-    const int n = blockIdx.x, k = threadIdx.x;
-    if (k >= N_STATS) return;
-    const int slot = k < 3 ? k : k == 3 ? LINE_COVERED : k - 1;  // front, drawn, clipped, covered, culled, flat
-    int t = 0;
-#pragma unroll
-    for (int l = 0; l < MAX_LINES; ++l) t += counters[((size_t)n * MAX_LINES + l) * LINE_INTS + slot];
-    out_stats[(size_t)n * N_STATS + k] = t;
+    stats_row<N_STATS, LINE_COVERED, 3>(counters, out_stats);
 }
 
 }  // namespace
@@ -159,29 +147,15 @@ extern "C" int colvo_render_surfels(const float* points, const float* normals, c
                                     void* scratch, float* out_depth, int32_t* out_index, float* out_colors, float* out_normal,
                                     int32_t* out_stats, colvo_stream_t stream) {
     COLVO_CHECK_ARG(M >= 0, "colvo_render_surfels: bad point count M=%d (0 <= M < 2^31)", M);
-    COLVO_CHECK_ARG(((points && normals) || M == 0) && K && cam2world && scratch && out_depth && out_index && out_stats,
-                    "colvo_render_surfels: null pointer argument");
-    COLVO_CHECK_ARG(out_colors ? (colors || M == 0) : !colors,
-                    "colvo_render_surfels: null pointer argument: colors and out_colors go together");
-    COLVO_CHECK_ARG(render_shape(N, H, W), "colvo_render_surfels: bad shape N=%d H=%d W=%d (1 <= N <= 65535, H*W < 2^30, N*H*W < 2^31)", N,
-                    H, W);
-    COLVO_CHECK_ARG(max_splat >= 0 && max_splat <= MAX_SPLAT, "colvo_render_surfels: bad max_splat %d (0 .. %d)", max_splat, MAX_SPLAT);
-    COLVO_CHECK_ARG(radius >= 0.0f && radius < __builtin_inff(), "colvo_render_surfels: bad radius %g (finite and >= 0)", (double)radius);
-    COLVO_CHECK_ARG(max_depth > 0.0f && max_depth < __builtin_inff(), "colvo_render_surfels: bad max_depth %g (finite and positive)",
-                    (double)max_depth);
-    COLVO_CHECK_ARG(aligned16(scratch), "colvo_render_surfels: scratch must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     Geom g;
-    g.M = M; g.N = N; g.H = H; g.W = W; g.max_splat = max_splat; g.radius = radius; g.max_depth = max_depth;
-    const Scratch w = layout(scratch, N, H, W);
-    launch_clear(w, N, H, W, s);
-    COLVO_CHECK_LAUNCH("k_render_clear");
+    Scratch w;
+    if (int e = begin_render("colvo_render_surfels", (points && normals) || M == 0, colors || M == 0, colors, K, cam2world, M, N, H, W,
+                             radius, max_splat, max_depth, scratch, out_depth, out_index, out_colors, out_stats, s, g, w))
+        return e;
     if (M > 0) {
-        const dim3 grid(blocks_of(M, NT), blocks_of(N, FRAME_GROUP));
-        if (TUNE(render_load_first))
-            colvo::launch(k_surfel_splat<true>, grid, dim3(NT), 0, s, points, normals, K, cam2world, g, w.keys, w.counters);
-        else
-            colvo::launch(k_surfel_splat<false>, grid, dim3(NT), 0, s, points, normals, K, cam2world, g, w.keys, w.counters);
+        launch_draw(k_surfel_splat<true>, k_surfel_splat<false>, dim3(blocks_of(M, NT), blocks_of(N, FRAME_GROUP)), s, points, normals, K,
+                    cam2world, g, w.keys, w.counters);
         COLVO_CHECK_LAUNCH("k_surfel_splat");
     }
     colvo::launch(k_surfel_resolve, dim3(blocks_of((long long)H * W, NT), N), dim3(NT), 0, s, (const unsigned long long*)w.keys, colors,

@@ -66,13 +66,13 @@ from __future__ import annotations
 
 import math
 import ctypes
-import struct
 from typing import NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
 from . import _lib
 from . import inference
+from ._args import f32 as _f32
 
 MIN_DEPTH = 0.1      # spec: MIN_DEPTH
 MAX_DEPTH = 10.0     # spec: MAX_DEPTH
@@ -290,10 +290,6 @@ class CloudMetrics(_CloudMetricsFields):
     def _replace(self, **kw):
         registration = kw.pop("registration", self.registration)
         return type(self)(*super()._replace(**kw), registration=registration)
-
-
-def _f32(x) -> float:
-    return struct.unpack("f", struct.pack("f", float(x)))[0]
 
 
 def _chk_cloud(t, name: str) -> torch.Tensor:

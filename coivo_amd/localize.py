@@ -30,7 +30,7 @@ import torch
 
 from . import _lib
 from . import evaluate
-from .inference import MAX_DEPTH, _chk, _f32
+from ._args import MAX_DEPTH, depth_views, f32
 
 
 class PolypLocalization(NamedTuple):
@@ -89,9 +89,6 @@ def localize_polyps(depths: torch.Tensor, labels: torch.Tensor, K: torch.Tensor,
     integer sums: max_depth * ray_max * 4096 must stay below 2^31 and its square times the walked pixels of a frame below 2^62.
     Reads K back for that check and two counts at the end."""
     lib = _lib.load()
-    if not isinstance(depths, torch.Tensor) or depths.dim() != 4:
-        raise ValueError("localize_polyps: depths must be [N,1,H,W]")
-    N, _, H, W = depths.shape
     if not isinstance(num_labels, int) or not 1 <= num_labels <= 255:
         raise ValueError(f"localize_polyps: num_labels must be an integer in 1..255, got {num_labels!r}")
     if stride < 1 or min_samples < 1:
@@ -100,16 +97,14 @@ def localize_polyps(depths: torch.Tensor, labels: torch.Tensor, K: torch.Tensor,
         raise ValueError("localize_polyps: max_depth must be finite and positive")
     if clip_sigma is not None and not (clip_sigma >= 0.0 and math.isfinite(clip_sigma)):
         raise ValueError("localize_polyps: clip_sigma must be finite and not negative")
-    depths = _chk(depths, "depths", (N, 1, H, W))
-    K = _chk(K, "K", (N, 3, 3))
-    cam2world = _chk(cam2world, "cam2world", (N, 4, 4))
+    depths, K, cam2world, N, H, W = depth_views("localize_polyps", depths, K, cam2world)
     if not isinstance(labels, torch.Tensor) or not labels.is_cuda or labels.dtype != torch.uint8 or \
             tuple(labels.shape) != (N, 1, H, W) or labels.device != depths.device:
         raise ValueError(f"labels: expected a uint8 CUDA tensor of shape {(N, 1, H, W)} on {depths.device}, got "
                          f"{getattr(labels, 'dtype', None)} {tuple(getattr(labels, 'shape', ()))} on {getattr(labels, 'device', None)}")
     labels = labels.contiguous()
     L = num_labels
-    check_sum_bounds(K, H, W, int(stride), _f32(max_depth))
+    check_sum_bounds(K, H, W, int(stride), f32(max_depth))
     nbytes = int(lib.colvo_localize_workspace_bytes(N, L))
     if nbytes == 0:
         raise ValueError(f"localize_polyps: unsupported N={N} (N <= 65535)")

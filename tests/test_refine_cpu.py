@@ -314,9 +314,10 @@ def test_python_wrappers_refuse_bad_arguments(lib):
     with pytest.raises(ValueError, match="iterations"):
         I.refine_trajectory(d, f, k, torch.from_numpy(M), iterations=0)
     # the edge list and T are checked before anything is uploaded (the checks of the device tensors come first: fake them)
-    fake = lambda t, name, shape: t
+    fake = lambda who, name, t, shape: t
     import unittest.mock as mock
-    with mock.patch.object(I, "_chk", fake):
+    from coivo_amd import _args, refine
+    with mock.patch.object(_args, "device_f32", fake), mock.patch.object(refine, "device_f32", fake):
         for edges in ([(0, 0)], [(0, 3)], [(-1, 1)], [], [(0, 1, 2)], [0, 1], torch.tensor([[0, 1]]).float(), None):
             with pytest.raises(ValueError, match="edge|edges_ij|E="):
                 I._refine_inputs("refine_edges", d, f, k, edges, T[:1])
