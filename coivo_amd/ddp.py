@@ -439,7 +439,7 @@ class GradBuckets:
         for st in self.states:
             join = getattr(st.module, "join_side", None)
             if join is not None:
-                join()                          # weight gradients whose join the network deferred (nn._ArenaModule)
+                join()                          # weight gradients whose join the network deferred (sidechain.SideChain)
         for st in self.states:
             while st.next < len(st.bounds):     # layers that reported out of order / never reported
                 self._launch(st, st.bounds[st.next], st.bounds[st.next - 1])

@@ -192,7 +192,7 @@ def conv_wgrad(d: ConvDesc, x0, x1, dy, dw, db, scratch: Optional[torch.Tensor] 
     layers then store instead of adding (include/colvo.h colvo_conv_wgrad_clean)."""
     _need_cuda(x0, x1, dy, dw, db, scratch)
     nb = 0 if scratch is None else scratch.numel() * scratch.element_size()
-    # (i[2] = "the arena is still zero": recorded, it is patched per replay by Program.set_flags, nn._ArenaModule._run_pass)
+    # (i[2] = "the arena is still zero": recorded, it is patched per replay by Program.set_flags, passes.RecordedPasses._run_pass)
     _issue(_lib.CMD_CONV_WGRAD, d, (x0, x1, dy, dw, db, scratch), (nb, 0, int(arena_is_zero)),
            flag_slot=2 if scratch is None else None)
 

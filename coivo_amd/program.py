@@ -59,6 +59,8 @@ class Program:
         self.uses_side = False
         self.flag_slots: List[Tuple[int, int]] = []   # (command, integer slot) of per-replay flags (set_flags)
         self._flag_value = 0
+        self.flush: Optional[List[bool]] = None       # per mark: its hook call launched something (learned by run_with_marks)
+        self.deferred_join = False           # recorded with its side-chain join left to the end of the whole backward pass
 
     # ---- recording ------------------------------------------------------------------------------------------- #
     def __enter__(self):
@@ -150,6 +152,42 @@ class Program:
         base = C.addressof(self._arr) + begin * C.sizeof(_lib.Cmd)
         _lib.check(lib.colvo_run_commands(base, n - begin, _lib.stream_ptr(),
                                           0 if side is None else side.cuda_stream), "colvo_run_commands")
+
+    def run_with_marks(self, side: Optional[torch.cuda.Stream], call) -> None:
+        """Replay with the hook call(*payload) of every mark enqueued behind that mark's commands.
+        Data parallel: the hook of a finished layer may launch a collective, which must be enqueued right after that
+        layer's kernels.  The first replay splits the program after EVERY layer and notes which hook calls launched
+        something (a hook that returns None is assumed to); later replays split only there and run the hooks of the
+        layers in between together, still in order.  A launch at an unexpected place re-arms the learning pass."""
+        done = 0
+        flush = self.flush
+        if flush is None or len(flush) != len(self.marks):
+            learned = []
+            for idx, mark in self.marks:
+                self.run(side, done, idx)
+                done = idx
+                r = call(*mark)
+                learned.append(r is None or bool(r))
+            self.flush = learned
+        else:
+            pending, ok = [], True
+            for i, (idx, mark) in enumerate(self.marks):
+                pending.append(mark)
+                if flush[i]:
+                    self.run(side, done, idx)
+                    done = idx
+                    for j, m in enumerate(pending):
+                        r = call(*m)
+                        ok = ok and ((r is None or bool(r)) == (j == len(pending) - 1))
+                    pending = []
+            if pending:
+                self.run(side, done, self.marks[-1][0])
+                done = self.marks[-1][0]
+                for m in pending:
+                    ok = ok and not call(*m)
+            if not ok:
+                self.flush = None
+        self.run(side, done, None)
 
     def __len__(self) -> int:
         return len(self._arr) if self._arr is not None else len(self.cmds)
