@@ -130,11 +130,29 @@ class Mesh(NamedTuple):
     n_open: int                     # cells with a sign change among their observed corners and one or more corners not observed
 
 
-class Meshing(NamedTuple):
-    """reconstruct_sequence's meshing policy: fuse_tsdf's trunc and extract_mesh's min_obs.  The defaults are choices, not tuned
-    values."""
+class _MeshingFields(NamedTuple):
     trunc: Optional[float] = None   # None: four voxels
     min_obs: int = 2
+
+
+class Meshing(_MeshingFields):
+    """reconstruct_sequence's meshing policy: fuse_tsdf's trunc and extract_mesh's min_obs.  The defaults are choices, not tuned
+    values.  Behind the two fields -- it still unpacks into two and equals the pair -- a third, `min_faces` (positional or by
+    keyword; 0, a choice: the mesh is left as extracted): with min_faces > 0 the components with fewer faces, and every vertex no
+    face uses, are removed (coivo_amd.topology.clean_mesh)."""
+    min_faces = 0
+
+    def __new__(cls, trunc=None, min_obs=2, min_faces=0):
+        self = super().__new__(cls, trunc, min_obs)
+        self.min_faces = min_faces
+        return self
+
+    def _replace(self, **kw):
+        min_faces = kw.pop("min_faces", self.min_faces)
+        return type(self)(*super()._replace(**kw), min_faces=min_faces)
+
+    def __repr__(self):
+        return f"Meshing(trunc={self.trunc!r}, min_obs={self.min_obs!r}, min_faces={self.min_faces!r})"
 
 
 def tsdf_voxels(who: str, voxel_size, trunc):

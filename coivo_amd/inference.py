@@ -8,7 +8,8 @@ maps of each frame using the colonoscopic trajectory").  filter_depths is the cr
 stitch_point_cloud (oracle/SPEC.md §6c).  The per-pixel work runs in csrc/reconstruct.hip; the trajectory integration is N
 products of 4x4 matrices and is done on the host in float64 (it is control flow, not a kernel).  The fusion runs in
 csrc/fuse.hip.  render_cloud / render_fused draw a cloud back into camera views (csrc/render.hip).
-  The entry points of fusion, consistency, refine, render and ply are re-exported here.
+  mesh_topology / clean_mesh say what the extracted surface is -- components, boundary loops, areas -- and remove its debris (DESIGN.md
+§3.6o, csrc/topology.hip).  The entry points of fusion, consistency, refine, render, topology and ply are re-exported here.
 """
 from __future__ import annotations
 
@@ -27,6 +28,7 @@ from .refine import (REFINE_BAD_EDGE, REFINE_NOT_PD, REFINE_OK, REFINE_REVERTED,
                      _refine_inputs, check_refinement, refine_accumulate, refine_edges, refine_trajectory, rigid_inverse)
 from .render import (MeshViews, Render, RenderedViews, SurfelViews, check_render, render_cloud, render_fused, render_mesh,
                      render_surfels)
+from .topology import CleanedMesh, MeshTopology, clean_mesh, mesh_topology
 
 
 def pose_to_matrix4(pose: torch.Tensor) -> torch.Tensor:
@@ -102,16 +104,17 @@ class Reconstruction(_ReconstructionFields):
     RenderedViews of `fused` in every frame's own camera along `cam2world`, else None; and `normals`: with Render(surfels=True) the
     CloudNormals of `fused` (`rendered` is then the SurfelViews drawn with them), else None; and `mesh`: with a Meshing policy the
     Mesh extracted from the TSDF volume of the same depths and trajectory, else None (with Render(mesh=True) `rendered` is the
-    MeshViews of that mesh)."""
+    MeshViews of that mesh); and `topology`: with a Meshing policy the MeshTopology of `mesh` (unit = the voxel size), else None."""
     polyps = None               # Optional[PolypLocalization]
     consistency = None          # Optional[ConsistencyResult]
     refinement = None           # Optional[RefinementResult]
     rendered = None             # Optional[RenderedViews], SurfelViews with Render(surfels=True), MeshViews with Render(mesh=True)
     normals = None              # Optional[CloudNormals]
     mesh = None                 # Optional[Mesh]
+    topology = None             # Optional[MeshTopology]
 
     def __new__(cls, depths, rel_poses, cam2world, points, fused=None, polyps=None, consistency=None, refinement=None,
-                rendered=None, normals=None, mesh=None):
+                rendered=None, normals=None, mesh=None, topology=None):
         self = super().__new__(cls, depths, rel_poses, cam2world, points, fused)
         self.polyps = polyps
         self.consistency = consistency
@@ -119,6 +122,7 @@ class Reconstruction(_ReconstructionFields):
         self.rendered = rendered
         self.normals = normals
         self.mesh = mesh
+        self.topology = topology
         return self
 
     def _replace(self, **kw):
@@ -128,8 +132,9 @@ class Reconstruction(_ReconstructionFields):
         rendered = kw.pop("rendered", self.rendered)
         normals = kw.pop("normals", self.normals)
         mesh = kw.pop("mesh", self.mesh)
+        topology = kw.pop("topology", self.topology)
         return type(self)(*super()._replace(**kw), polyps=polyps, consistency=consistency, refinement=refinement, rendered=rendered,
-                          normals=normals, mesh=mesh)
+                          normals=normals, mesh=mesh, topology=topology)
 
 
 @torch.no_grad()
@@ -172,7 +177,10 @@ def reconstruct_sequence(depth_net, pose_net, frames: torch.Tensor, K: torch.Ten
     TSDF volume along the trajectory the call used (fuse_tsdf: same K, voxel_size, stride and max_depth; policy.trunc) and the surface
     is extracted from it (extract_mesh: policy.min_obs): the Mesh is `mesh` (else None).  With Render(mesh=True) (needs a Meshing policy;
     not together with surfels=True) it is that mesh, not the cloud, that is drawn into every frame's own camera (render_mesh: same K,
-    max_depth and image size, culling off): `rendered` is then a MeshViews and `normals` stays None."""
+    max_depth and image size, culling off): `rendered` is then a MeshViews and `normals` stays None.  With a Meshing policy the
+    topology of the mesh is computed as well (mesh_topology, unit = voxel_size; `topology`, else None); with policy.min_faces > 0 the
+    components with fewer faces -- and every vertex no face uses -- are first removed (clean_mesh) and the topology is that of the
+    cleaned mesh, which is then `mesh` and what Render(mesh=True) draws; with min_faces = 0 `mesh` is extract_mesh's, bit for bit."""
     who = "reconstruct_sequence"
     n = frames.shape[0]
     if n < 2:
@@ -198,11 +206,12 @@ def reconstruct_sequence(depth_net, pose_net, frames: torch.Tensor, K: torch.Ten
         if render.mesh and mesh is None:
             raise ValueError(f"{who}: Render(mesh=True) needs a Meshing policy (mesh=Meshing()): it draws the extracted mesh")
     if mesh is not None:
-        mesh = Meshing(*mesh)
+        mesh = Meshing(*mesh, min_faces=mesh.min_faces) if isinstance(mesh, Meshing) else Meshing(*mesh)      # (a plain tuple may hold two or three)
         if voxel_size is None:
             raise ValueError(f"{who}: mesh needs voxel_size (the TSDF volume's voxels)")
         tsdf_voxels(who, voxel_size, mesh.trunc)
         int_range(who, "mesh.min_obs", mesh.min_obs, 1)
+        int_range(who, "mesh.min_faces", mesh.min_faces, 0)
     K = per_view_K(K, n).to(frames.device, torch.float32).contiguous()
     depths, rel = run_networks(depth_net, pose_net, frames, chunk=chunk)
     traj = integrate_trajectory(rel)
@@ -229,11 +238,15 @@ def reconstruct_sequence(depth_net, pose_net, frames: torch.Tensor, K: torch.Ten
             normals = cloud_normals(fused, depths, K, traj32, stride=stride, max_depth=max_depth)
         rendered = render_fused(fused, K, traj32, int(frames.shape[2]), int(frames.shape[3]), radius=render.radius,
                                 max_splat=render.max_splat, max_depth=max_depth, normals=normals)
-    surface = None
+    surface = topology = None
     if mesh is not None:
         volume = fuse_tsdf(depths, K, traj32, voxel_size=voxel_size, trunc=mesh.trunc, colors=frames.to(torch.float32).contiguous(),
                            stride=stride, max_depth=max_depth)
         surface = extract_mesh(volume, min_obs=mesh.min_obs)
+        topology = mesh_topology(surface, unit=voxel_size)
+        if mesh.min_faces > 0:
+            surface = clean_mesh(surface, topology, min_faces=mesh.min_faces).mesh
+            topology = mesh_topology(surface, unit=voxel_size)
         if render is not None and render.mesh:
             rendered = render_mesh(surface, K, traj32, int(frames.shape[2]), int(frames.shape[3]), max_depth=max_depth)
-    return Reconstruction(raw, rel, traj, cloud, fused, polyps, checked, refined, rendered, normals, surface)
+    return Reconstruction(raw, rel, traj, cloud, fused, polyps, checked, refined, rendered, normals, surface, topology)

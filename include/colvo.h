@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define COLVO_ABI_VERSION 25
+#define COLVO_ABI_VERSION 26
 
 typedef void* colvo_stream_t; /* hipStream_t */
 
@@ -770,6 +770,65 @@ int colvo_render_mesh(const float* vertices, const int32_t* faces, const float* 
                       const float* cam2world, int N, int H, int W, float max_depth, int cull_back, void* scratch, float* out_depth,
                       int32_t* out_index, float* out_colors, float* out_normal, int32_t* out_face_pixels, int32_t* out_stats,
                       colvo_stream_t stream);
+
+/* Mesh topology: components, edges, boundary loops, areas and lengths, and cleaning (csrc/topology.hip; replica
+ * tests/topology_ref.py, which every output equals bit for bit).  vertices [V,3] float32, faces [F,3] int32 (rows of vertices).
+ * Definitions.  A face is DEAD iff an index lies outside [0, V) or two of its indices are equal: it joins nothing, has no edges and
+ *   no area.  The other faces are live.  A COMPONENT is a class of vertices joined by live faces; a vertex that no live face uses is a
+ *   component of its own with no faces.  Components are numbered 0 .. C-1 by ascending smallest vertex.  An EDGE is an unordered pair
+ *   of vertices that is a side of a live face; its multiplicity m is the number of live-face sides on it (a face given twice counts
+ *   twice); it is BOUNDARY iff m = 1 and NON-MANIFOLD iff m > 2.  A LOOP is a connected component of the graph of the boundary edges
+ *   (two rings that touch in a vertex are one loop); loops are numbered 0 .. L-1 by ascending smallest vertex.
+ * Measures, float64, every operation individually rounded in the order written (no FMA contraction), division and square root
+ *   correctly rounded, coordinates widened from float32.  With `unit` a finite positive float32: area quantum qa = ((double)unit *
+ *   (double)unit) * 2^-16, length quantum ql = (double)unit * 2^-16.  Face (i, j, k): a = p_j - p_i, b = p_k - p_i componentwise;
+ *   n_x = a_y b_z - a_z b_y, n_y = a_z b_x - a_x b_z, n_z = a_x b_y - a_y b_x; s = (n_x n_x + n_y n_y) + n_z n_z; area = 0.5 *
+ *   sqrt(s); quanta = llrint(area / qa), ties to even.  Boundary edge (lo < hi): d = p_hi - p_lo; length = sqrt((d_x d_x + d_y d_y) +
+ *   d_z d_z); quanta = llrint(length / ql).  A face or boundary edge whose quotient is NaN or >= 2^62 is UNMEASURED: it adds 0 quanta
+ *   and is counted.  The sums are int64 adds (they wrap beyond 2^63).
+ * Three calls on one stream, with one scratch of colvo_mesh_topology_scratch_bytes(V, F) bytes (16-byte aligned) that carries state
+ * from each to the next, and one stats block (device int32[8], cleared by the first call): [0] C, [1] dead faces, [2] L, [3]
+ * unmeasured faces, [4] unmeasured boundary edges, [5] not zero iff a thread exhausted a loop bound (the outputs are then not valid:
+ * the caller must raise), [6] sides of live faces, [7] 0.
+ *   components  vertex_component [V] int32; face_component [F] int32, -1 for a dead face; stats[0], stats[1].  The caller reads C.
+ *   edges       components [C][8] int64: smallest vertex, vertices, faces, edges, boundary edges, non-manifold edges, loops (written
+ *               by `loops`; 0 here), area in quanta.  vertex_loop [V] int32: the loop of a vertex on a boundary edge, else -1.
+ *               stats[2], [3], [6].  The caller reads L; with L = 0 it is done.
+ *   loops       (L >= 1) loops [L][4] int64: smallest vertex, component, edges, length in quanta; adds the loop counts to
+ *               components[.][6]; stats[4].
+ * Every in-kernel loop has a bound known on entry (a parent chain strictly descends: V links; a union ends or lowers one of its two
+ * vertices every round: 2 V + 2 rounds); no thread waits for another thread's store.  One thread per side scans the sides that share
+ * its smaller endpoint: quadratic in the edges at one lower endpoint (12 at most on extract_mesh's meshes) -- the limit for general
+ * meshes with a vertex of very high degree.
+ * Limits, refused before any HIP call with a message that starts with the entry's name: 1 <= V < 2^31, 0 <= F < 2^29 (faces may be
+ * NULL when F = 0; the caller handles V = 0 without a call), unit finite and positive, 1 <= C, L <= V.  The size function returns 0 for
+ * what the calls refuse. */
+size_t colvo_mesh_topology_scratch_bytes(int V, int F);
+int colvo_mesh_topology_components(const int32_t* faces, int V, int F, void* scratch, int32_t* vertex_component,
+                                   int32_t* face_component, int32_t* stats, colvo_stream_t stream);
+int colvo_mesh_topology_edges(const float* vertices, const int32_t* faces, int V, int F, float unit, int C, void* scratch,
+                              const int32_t* vertex_component, const int32_t* face_component, int64_t* components,
+                              int32_t* vertex_loop, int32_t* stats, colvo_stream_t stream);
+int colvo_mesh_topology_loops(const float* vertices, int V, int F, float unit, int C, int L, const void* scratch,
+                              const int32_t* vertex_component, const int32_t* vertex_loop, int64_t* components, int64_t* loops,
+                              int32_t* stats, colvo_stream_t stream);
+
+/* The mesh without the components a caller drops.  kept [C] uint8: not zero = keep.  Order is preserved.
+ *   plan    vertex_map [V] int32: the new row of every vertex of a kept component, -1 for the others; vertex_index [V] int32: the
+ *           first V2 entries are the old rows of the new vertices, ascending; face_index [F] int32: the first F2 entries are the old
+ *           rows of the live faces of kept components, ascending (a dead face has component -1 and is dropped); counts (device
+ *           int32[2]): V2, F2.  A component number outside [0, C) is dropped.  scratch: colvo_mesh_clean_scratch_bytes(V, F) bytes.
+ *   write   out_vertices, out_colors, out_normals [V2][3] float32 and out_cells [V2][3] int32: the old rows' bits (colors, normals and
+ *           cells may each be NULL with their output); out_faces [F2][3] int32: the old faces' indices through vertex_map.
+ * Limits as above; 0 <= V2 <= V, 0 <= F2 <= F, one of them positive.  Refusals start with the entry's name. */
+size_t colvo_mesh_clean_scratch_bytes(int V, int F);
+int colvo_mesh_clean_plan(const int32_t* vertex_component, const int32_t* face_component, const uint8_t* kept, int V, int F, int C,
+                          void* scratch, int32_t* vertex_map, int32_t* vertex_index, int32_t* face_index, int32_t* counts,
+                          colvo_stream_t stream);
+int colvo_mesh_clean_write(const float* vertices, const float* colors, const float* normals, const int32_t* cells,
+                           const int32_t* faces, int V, int F, const int32_t* vertex_map, const int32_t* vertex_index,
+                           const int32_t* face_index, int V2, int F2, float* out_vertices, float* out_colors, float* out_normals,
+                           int32_t* out_cells, int32_t* out_faces, colvo_stream_t stream);
 
 /* Pose refinement by dense depth and intensity alignment: a few Gauss-Newton steps per edge on the per-pixel geometric
  * and photometric residuals of the two frames it connects, starting from the pose given.  depths [N,1,H,W], frames [N,3,H,W], K [N,3,3]
