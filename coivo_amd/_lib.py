@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("COLVO_LIB_PATH") or os.path.join(_HERE, "lib", "libcolvo.so")
 
 F32, BF16 = 0, 1
-ABI_VERSION = 26
+ABI_VERSION = 27
 
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 
@@ -169,6 +169,10 @@ SIGNATURES = {
     "colvo_cloud_index_build": (_i, [_vp, _i, _f, _vp, _vp]),
     "colvo_cloud_query": (_i, [_vp, _i, _i, _f, _vp, _i] + [_vp] * 6),
     "colvo_cloud_transform": (_i, [_vp, _i, _vp, _vp, _vp]),
+    "colvo_surface_scratch_bytes": (_sz, [_i, _i]),
+    "colvo_surface_index_plan": (_i, [_vp, _vp, _i, _i, _f, _vp, _vp, _vp]),
+    "colvo_surface_index_fill": (_i, [_vp, _vp, _i, _i, _vp, C.c_int64, _i, _vp, _vp]),
+    "colvo_surface_query": (_i, [_vp, _i, _vp, _vp, _i, _i, _f, _vp, _i, _vp, _vp, C.c_int64, _i] + [_vp] * 7),
     "colvo_register_scratch_bytes": (_sz, [_i]),
     "colvo_register_accumulate": (_i, [_vp, _i, _vp, _vp, _i, _f, _vp, _vp, _vp, _i] + [_vp] * 4),
     "colvo_register_clouds": (_i, [_vp, _i, _vp, _vp, _i, _f, _vp, _vp, _vp, _i, _i, _i, C.c_double, _i] + [_vp] * 6),

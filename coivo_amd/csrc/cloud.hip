@@ -92,32 +92,10 @@ __global__ __launch_bounds__(NT) void k_cloud_bounds(const float* __restrict__ P
     }
 }
 
-// one thread: the box -> origin, edge, dims
+// one thread: the box -> origin, edge, dims (cloud_grid::make_grid)
 __global__ void k_cloud_grid(Header* __restrict__ h, float max_dist) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    if (h->n_valid == 0u) return;                                // the header was cleared: cells = 0
-    float lo[3], hi[3], ext = 0.0f;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        lo[a] = float_key_inv(~h->key[a]);
-        hi[a] = float_key_inv(h->key[3 + a]);
-        ext = fmaxf(ext, hi[a] - lo[a]);
-    }
-    const float edge = fmaxf(max_dist * EDGE_MARGIN, __fdiv_rn(ext, AXIS_DIV));
-    const float inv = __fdiv_rn(1.0f, edge);
-    const bool single = !(finite_f(ext) && finite_f(edge) && finite_f(inv) && inv > 0.0f);
-    int cells = 1;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        h->o[a] = lo[a];
-        int n = 1;
-        if (!single) n = (int)fminf(fmaxf(floorf((hi[a] - lo[a]) * inv), 0.0f), (float)(AXIS_LIMIT - 1)) + 1;
-        h->n[a] = n;
-        cells *= n;
-    }
-    h->inv = single ? 0.0f : inv;
-    h->single = single ? 1u : 0u;
-    h->cells = cells;
+    make_grid(h, max_dist);
 }
 
 // one thread per reference point: count[cell] += 1; the value before the add is the point's rank in its cell (-1: invalid point)

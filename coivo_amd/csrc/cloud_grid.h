@@ -60,6 +60,34 @@ __device__ __forceinline__ Grid load_grid(const Header* __restrict__ h) {
     return G;
 }
 
+// One thread: the box of the header's keys -> origin, cell edge and dims, for the cloud's index and the surface's (csrc/surface.hip)
+// alike.  edge = max(max_dist * EDGE_MARGIN, extent / AXIS_DIV), float32, every operation rounded once.
+__device__ __forceinline__ void make_grid(Header* __restrict__ h, float max_dist) {
+    if (h->n_valid == 0u) return;                                // the header was cleared: cells = 0
+    float lo[3], hi[3], ext = 0.0f;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        lo[a] = float_key_inv(~h->key[a]);
+        hi[a] = float_key_inv(h->key[3 + a]);
+        ext = fmaxf(ext, hi[a] - lo[a]);
+    }
+    const float edge = fmaxf(max_dist * EDGE_MARGIN, __fdiv_rn(ext, AXIS_DIV));
+    const float inv = __fdiv_rn(1.0f, edge);
+    const bool single = !(finite_f(ext) && finite_f(edge) && finite_f(inv) && inv > 0.0f);
+    int cells = 1;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        h->o[a] = lo[a];
+        int n = 1;
+        if (!single) n = (int)fminf(fmaxf(floorf((hi[a] - lo[a]) * inv), 0.0f), (float)(AXIS_LIMIT - 1)) + 1;
+        h->n[a] = n;
+        cells *= n;
+    }
+    h->inv = single ? 0.0f : inv;
+    h->single = single ? 1u : 0u;
+    h->cells = cells;
+}
+
 // The pinned cell coordinate of one axis: ((x - o) * inv), floored by the callers.
 __device__ __forceinline__ float grid_coord(const Grid& G, int a, float x) { return (x - G.o[a]) * G.inv; }
 

@@ -154,7 +154,16 @@ namespace tune {
     /* ---- TSDF fusion (tsdf.hip) ---- */                                                                                         \
     X(tsdf_cull, 1, "k_tsdf_integrate tests the frames 64 at a time against the brick (depth slab and image rectangle, conservative) "  \
                     "and walks only the survivors; 0: every brick walks every frame.  Integer sums: the result does not depend on it "  \
-                    "(tests/test_tsdf_gpu.py compares the bits; times: tools/bench_tsdf.py, DESIGN.md 3.6m)")
+                    "(tests/test_tsdf_gpu.py compares the bits; times: tools/bench_tsdf.py, DESIGN.md 3.6m)")                           \
+    /* ---- point-to-surface distances (surface.hip) ---- */                                                                        \
+    X(surface_span_limit, 4, "a face whose box of grid cells spans more than this many cells on an axis (1..128) goes onto the oversize "  \
+                             "list every query examines whole; any other is entered into at most limit^3 = 64 cells, which bounds the fill "  \
+                             "loop and the pair count (64 F).  The result does not depend on it.  A choice, not tuned: with a cell edge of at "  \
+                             "least max_dist, a face of extract_mesh (under one voxel across) spans one or two cells; DESIGN.md 3.6p")                  \
+    X(surface_copy_records, 0, "a record of the surface index is the face's nine coordinates and its index (48 bytes, three 16-byte loads "  \
+                               "in cell order) instead of its index alone (4 bytes, and a gather through faces and vertices per candidate).  "   \
+                               "The plan reads it and reports the record size; the result does not depend on it.  tools/bench_surface.py "      \
+                               "times both forms; DESIGN.md 3.6p has what was measured")
 
 struct Table {
 #define X(name, dflt, doc) double name = dflt;

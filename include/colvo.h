@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define COLVO_ABI_VERSION 26
+#define COLVO_ABI_VERSION 27
 
 typedef void* colvo_stream_t; /* hipStream_t */
 
@@ -943,6 +943,69 @@ int colvo_cloud_index_build(const float* ref, int M, float max_dist, void* works
 int colvo_cloud_query(const float* query, int N, int M, float max_dist, const float* thresholds, int n_thresholds, void* workspace,
                       float* dist, float* dist2, int32_t* nearest, uint64_t* stats, colvo_stream_t stream);
 int colvo_cloud_transform(const float* points, int N, const float* Rts, float* out, colvo_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------- *
+ * Point-to-surface distances: exact truncated nearest point OF THE TRIANGLES of a mesh         *
+ * (NumPy replica tests/surface_ref.py, brute force, no grid).                  *
+ * ------------------------------------------------------------------------------------------- */
+/* query Q [N,3] float32, vertices [V,3] float32, faces [F,3] int32 (rows of vertices), contiguous; max_dist > 0 as the cloud calls take
+ * it; up to 8 thresholds as colvo_cloud_query takes them.
+ *   validity  A face is DEAD exactly as for colvo_mesh_topology_*: an index outside [0, V) or a repeated index.  A live face with a
+ *             coordinate that is not finite is SKIPPED.  Dead and skipped faces take no part and are counted.  A query with a
+ *             coordinate that is not finite is invalid: it takes no part, is not counted as valid, and gets the sentinels below.
+ *   arithmetic  float64 on coordinates widened from float32, every operation individually rounded in the order written (no FMA
+ *             contraction), division and square root correctly rounded.  For query p and face (a, b, c), componentwise:
+ *               ab = b - a, ac = c - a, bc = c - b, ca = a - c, pa = p - a, pb = p - b, pc = p - c;
+ *               n_x = ab_y ac_z - ab_z ac_y, n_y = ab_z ac_x - ab_x ac_z, n_z = ab_x ac_y - ab_y ac_x;
+ *               s = (n_x n_x + n_y n_y) + n_z n_z;   h = (n_x pa_x + n_y pa_y) + n_z pa_z;
+ *               T(e, w) = (n_x c_x + n_y c_y) + n_z c_z with c_x = e_y w_z - e_z w_y, c_y = e_z w_x - e_x w_z, c_z = e_x w_y - e_y w_x.
+ *             Up to four candidates (d2, point), tried in this order; only a strictly smaller d2 replaces the running one:
+ *               plane   used iff s > 0 (and finite) and T(ab, pa) >= 0, T(bc, pb) >= 0, T(ca, pc) >= 0:
+ *                       k = h / s, d2 = (h h) / s, point_j = p_j - n_j k.
+ *               ab, bc, ca   segment (u, e, w) = (a, ab, pa), (b, bc, pb), (c, ca, pc): ee = (e_x e_x + e_y e_y) + e_z e_z,
+ *                       we = (w_x e_x + w_y e_y) + w_z e_z, t = min(max(we / ee, 0), 1) if ee > 0 else 0, point_j = u_j + t e_j,
+ *                       d_j = p_j - point_j, d2 = (d_x d_x + d_y d_y) + d_z d_z.
+ *             Every candidate is a point of the triangle; a degenerate live face (collinear: s = 0 exactly, since equal products
+ *             round alike; coincident vertices) degrades to its segments or a point and never yields a NaN.
+ *   reach     md2 = double(max_dist)^2, exact.  A face is within reach iff its d2 < md2 (strict).  The winner is the least
+ *             (d2, face index) in lexicographic order over the faces within reach.
+ *   outputs   dist2 [N] float64: the winner's d2.  dist [N] float32: sqrt(dist2) in float64, rounded once to float32.  face [N] int32.
+ *             closest [N][3] float32: the winning candidate's point, rounded once.  side [N] int8: the sign of h on the winning face
+ *             (+1: the side the normal ab x ac points to -- free space, for extract_mesh's winding), 0 where h = 0 or s is not > 0.
+ *             Nothing within reach, or an invalid query: md2, float32(max_dist), -1, the query itself (zeros for an invalid query), 0.
+ *   stats     device uint64[19], exact integers.  [0..11] have colvo_cloud_query's meaning and order (the thresholds compare dist2
+ *             with double(float32(tau_k))^2; the quanta are taken from the float32 dist with the same s; [11] counts the records and
+ *             oversize faces examined).  [12] valid queries with side > 0, [13] with side < 0, [14] reached queries whose winning
+ *             candidate is the plane one, [15] dead faces, [16] skipped faces, [17] (cell, face) pairs in the index, [18] faces on the
+ *             oversize list.
+ * Every output bit follows from the inputs alone, as for the cloud calls.
+ * Index.  The grid of colvo_cloud_index_build over the bounding box of the vertices of the live, not skipped faces: cell edge
+ * max(max_dist * (1 + 2^-10), largest extent / 126).  A face is entered into every cell of the box [c(min_a) .. c(max_a)] of its own
+ * axis-aligned bounds (c: the clamped floor of the pinned float32 cell coordinate); DESIGN.md §3.6p has the argument that the 27 cells
+ * around a query's cell then hold every face within reach.  A face whose box spans more than the tuning entry surface_span_limit (4)
+ * cells on an axis goes onto an oversize list that every valid query examines whole.  Neither the list nor a face met in several
+ * cells can change a bit: the minimum is over (d2, face).
+ *   plan    bounds, grid, per-face counts, the ordered scan; counts (device int64[8]): pairs, oversize faces, dead, skipped,
+ *           record_bytes, three zeros.  record_bytes is 4 (a record is a face index; the query gathers through faces and vertices)
+ *           or 48 (the face's nine coordinates, its index and two words of padding, read as three 16-byte words), by the tuning
+ *           entry surface_copy_records when the plan is made.  The caller reads counts back -- the one read-back -- and allocates
+ *           records: pairs * record_bytes bytes, 16-byte aligned.
+ *   fill    the faces sorted by cell into records.  pairs, record_bytes: the plan's.
+ *   query   with the same vertices, faces, max_dist, scratch, records, pairs and record_bytes.  It clears and writes the counter lines of the
+ *           scratch: one query at a time per scratch; any number of queries may follow one plan / fill.
+ * scratch: colvo_surface_scratch_bytes(V, F) bytes, 16-byte aligned, carries the index's header, cell starts and oversize list from
+ * each call to the next.
+ * Limits, refused before any HIP call with a message that starts with the entry's name: 0 <= V, 0 <= F < 2^29, 0 <= N < 2^30,
+ * 0 <= pairs < 2^30, record_bytes 4 or 48; max_dist and thresholds as the cloud calls refuse them.  Empty sides are legal and launch nothing that indexes
+ * (their pointers may be NULL).  The size function returns 0 for what the calls refuse. */
+size_t colvo_surface_scratch_bytes(int V, int F);
+int colvo_surface_index_plan(const float* vertices, const int32_t* faces, int V, int F, float max_dist, void* scratch, int64_t* counts,
+                             colvo_stream_t stream);
+int colvo_surface_index_fill(const float* vertices, const int32_t* faces, int V, int F, void* scratch, int64_t pairs, int record_bytes,
+                             void* records, colvo_stream_t stream);
+int colvo_surface_query(const float* query, int N, const float* vertices, const int32_t* faces, int V, int F, float max_dist,
+                        const float* thresholds, int n_thresholds, void* scratch, const void* records, int64_t pairs, int record_bytes,
+                        double* dist2, float* dist, int32_t* face, float* closest, int8_t* side, uint64_t* stats, colvo_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------- *
  * Registration of two point clouds: point-to-plane (or point-to-point) ICP over the index of    *
