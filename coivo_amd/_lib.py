@@ -82,6 +82,7 @@ SIGNATURES = {
     "colvo_full_objective_terms": (_i, [_vp, _i, _i, _i, _i, C.POINTER(_vp)]),
     "colvo_conv_fwd": (_i, [C.POINTER(ConvDesc)] + [_vp] * 6),
     "colvo_pose_front_plan": (_i, [C.POINTER(ConvDesc), _i, C.POINTER(C.c_int32)]),
+    "colvo_pose_tail_plan": (_i, [C.POINTER(ConvDesc), _i, C.POINTER(C.c_int32)]),
     "colvo_conv_dgrad": (_i, [C.POINTER(ConvDesc), _i, _vp, _vp, _vp, _vp, _i, _vp]),
     "colvo_conv_dgrad_both": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "colvo_conv_dgrad_planes": (_i, [C.POINTER(ConvDesc), _vp, _vp, _i, _i, _vp, _i, _vp]),

@@ -29,7 +29,8 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-
 # (profiles/r2_mfma_hazard.md).  wgrad.hip keeps AGPR accumulators (faster pixel loop) and ties them with "+a".
 FILE_FLAGS = {"conv.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "bwd16.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
               "fwd16.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "conv_rt.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
-              "wgrad_rt.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "pose_front.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
+              "wgrad_rt.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "pose_front.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
+              "pose_tail.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
 
 
 def _deps():

@@ -142,6 +142,11 @@ int launch_dgrad_planes_s2_mfma(const void* g, const float* w, int Cin, int c_be
 int pose_front_fwd(const ColvoCmd& c, hipStream_t stream);
 int pose_front_bwd(const ColvoCmd& c, hipStream_t stream);
 
+// csrc/pose_tail.hip: COLVO_CMD_CONV_FWD with i[0] = -1 and COLVO_CMD_CONV_DGRAD with i[2] = 1 -- one of PoseNet's conv5-conv7 as a
+// whole-K resident launch (colvo_pose_tail_plan)
+int pose_tail_fwd(const ColvoCmd& c, hipStream_t stream);
+int pose_tail_dgrad(const ColvoCmd& c, hipStream_t stream);
+
 __device__ __forceinline__ float uniform_f(float v) {
     return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)));
 }

@@ -1835,6 +1835,27 @@ bool conv_dgrad_is_s2_tile(const ColvoConvDesc* d) {
     if (conv_plan(d, PASS_DGRAD, d->up0, k, p)) return false;
     return p.form == DGRAD_S2 && p.nch == 0;
 }
+// pose_tail.hip's planner: k_conv3x3 in any of its one-tile forms (one chunk in flight, the two-chunk ring, 512 threads) walks the
+// 32-channel chunks in ascending order, tap by tap: one sum order
+bool conv_fwd_is_tile_chunks32(const ColvoConvDesc* d) {
+    if (check_desc(d, "colvo_pose_tail_plan")) return false;
+    ConvK k{};
+    fill_gather(d, nullptr, nullptr, k.g);
+    k.Ho = d->Ho; k.Wo = d->Wo;
+    k.Ctot = d->C0 + d->C1; k.N = d->Cout;
+    k.relu = d->relu;
+    ConvPlan p{};
+    if (conv_plan(d, PASS_FWD, 0, k, p)) return false;
+    return p.form == CONV_TILE && p.ng == 4;
+}
+int conv_dgrad_kind(const ColvoConvDesc* d) {
+    if (check_desc(d, "colvo_pose_tail_plan") || d->C1 != 0) return DGRAD_KIND_OTHER;
+    ConvK k = dgrad_conv(d, nullptr, nullptr, 0, d->C0, nullptr, nullptr, 0);
+    ConvPlan p{};
+    if (conv_plan(d, PASS_DGRAD, d->up0, k, p)) return DGRAD_KIND_OTHER;
+    if (p.form == DGRAD_S2) return DGRAD_KIND_S2;
+    return p.form == CONV_TILE && p.ng == 4 && k.g.mode[0] == MODE_DILATE && !k.pool2 ? DGRAD_KIND_DILATED_TILE : DGRAD_KIND_OTHER;
+}
 }  // namespace colvo
 
 using namespace colvo;

@@ -77,6 +77,11 @@ int conv_rt_launch(const ConvK& k, const ConvPlan& p, int dtype, hipStream_t s);
 // its input gradient as k_dgrad_s2 with one chunk in flight.  Plans only: no HIP call, no form counted.
 bool conv_fwd_is_one_tile(const ColvoConvDesc* d);
 bool conv_dgrad_is_s2_tile(const ColvoConvDesc* d);
+// ... and for pose_tail.hip's: whether colvo_conv_fwd would run layer d as k_conv3x3 over 32-channel chunks (any of its one-tile forms:
+// they add a column's products in one order), and which kernel colvo_conv_dgrad would run for its input gradient
+bool conv_fwd_is_tile_chunks32(const ColvoConvDesc* d);
+enum { DGRAD_KIND_OTHER = 0, DGRAD_KIND_S2, DGRAD_KIND_DILATED_TILE };       // k_dgrad_s2; k_conv3x3 over the zero-dilated dy, 32-channel chunks
+int conv_dgrad_kind(const ColvoConvDesc* d);
 
 // Where a weight-gradient kernel puts its sums: part of the kernel argument of all three kernels (k_wgrad3x3, k_wgrad_up2, k_wgrad_rt),
 // filled once per launch by wgrad.hip's wgrad_resolve.  Device pointers and flags only.

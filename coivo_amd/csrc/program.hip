@@ -87,9 +87,11 @@ extern "C" int colvo_set_aux_side_streams(int n) {
 static int run_one(const ColvoCmd& c, int k, colvo_stream_t s) {
     switch (c.op) {
         case COLVO_CMD_CONV_FWD:
+            if (c.i[0] == -1) return pose_tail_fwd(c, (hipStream_t)s);  // the whole-K resident form, by request (csrc/pose_tail.hip)
             if (c.i[0]) return pose_front_fwd(c, (hipStream_t)s);      // a chain of layers in one launch (csrc/pose_front.hip)
             return colvo_conv_fwd(&c.desc, c.p[0], c.p[1], c.p[2], (const float*)c.p[3], (void*)c.p[4], s);
         case COLVO_CMD_CONV_DGRAD:
+            if (c.i[2]) return pose_tail_dgrad(c, (hipStream_t)s);     // the whole-K resident form, by request (csrc/pose_tail.hip)
             return colvo_conv_dgrad(&c.desc, c.i[0], c.p[0], c.p[1], c.p[2], (void*)c.p[3], c.i[1], s);
         case COLVO_CMD_CONV_DGRAD_BOTH:
             return colvo_conv_dgrad_both(&c.desc, c.p[0], c.p[1], c.p[2], c.p[3], (void*)c.p[4], (void*)c.p[5], s);

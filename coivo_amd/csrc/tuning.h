@@ -112,6 +112,24 @@ namespace tune {
     X(pose_front_bwd, 1, "... and their input-gradient chain g3 -> g2 -> g1 -> the two depth planes as ONE launch (k_pose_front_bwd) in "  \
                          "place of two k_dgrad_s2 launches and k_dgrad_planes_s2_mfma; only with pose_front on.  On top of the forward chain: "     \
                          "1.3836-1.3920 -> 1.3682-1.3824 ms (profiles/pose_front_ab.md)")    \
+    X(pose_tail, 1, "PoseNet's conv5-conv7 forward as whole-K resident launches (k_conv_wholek, csrc/pose_tail.hip: a workgroup owns 16 "   \
+                    "output channels x the pixels of whole images, requests its whole [16][9][Cin] weight slab and its input maps before the "   \
+                    "first wait and runs complete K chains out of LDS) in place of the 4- / 8-chunk k_conv3x3 launches; same bits.  "           \
+                    "Reached only by explicit request in CMD_CONV_FWD where colvo_pose_tail_plan selects the layer.  8 pairs of 256x320, "      \
+                    "us a launch in the step: conv5 9.1 -> 6.1, conv6 10.6 -> 6.1, conv7 10.4 -> 5.6; step in ms, three alternating rounds: "     \
+                    "parent 1.3064-1.3143, forward only 1.2989-1.3072 (overlaps the parent by one round; -0.7 % by the medians), both "           \
+                    "directions 1.2820-1.2897; level at 64 pairs, where it is not selected (profiles/pose_tail_ab.md)")                           \
+    X(pose_tail_bwd, 1, "... and the input gradients of conv7 (zero-dilated k_conv3x3 order), conv6 and conv5 (k_dgrad_s2 order) in the same "    \
+                        "form, by explicit request in CMD_CONV_DGRAD; only with pose_tail on.  conv7 10.8 -> 6.5, conv6 12.7 -> 6.7, conv5 "      \
+                        "12.5 -> 7.4 us; on top of the forward form 1.2989-1.3072 -> 1.2820-1.2897 ms, separated (profiles/pose_tail_ab.md)")     \
+    X(pose_tail_max_pairs, 24, "... batch ceiling of both: selected up to this many images per launch.  Step in ms at --config 1 with "           \
+                               "--batch-per-gpu B, form off -> on, two alternating rounds: 12 pairs 1.7632 / 1.7507 -> 1.7289 / 1.7349, "        \
+                               "16 pairs 2.0896 / 2.0914 -> 2.0662 / 2.0687, 24 pairs 2.8134 / 2.8156 -> 2.7660 / 2.7773 (separated in "         \
+                               "every round); 32 pairs 3.4339 / 3.4595 -> 3.4827 / 3.4582 and 64 pairs 6.4265 / 6.4446 -> 6.4426 / 6.4275 "      \
+                               "are not resolved, so configs[3] and [4] stay on k_conv3x3 / k_dgrad_s2 (profiles/pose_tail_ab.md)")               \
+    X(pose_tail_images, 0, "... images per workgroup (0: the fewest at which the grid is at most 256 workgroups, as many as fit beyond; "          \
+                           "tests force fragments that span images with it).  Alone at 8 pairs 1 image is the fastest or level on every "         \
+                           "launch: conv6's input gradient 5.6 / 5.6 / 5.5 / 6.8 us at 1 / 2 / 4 / 8 images, conv7's 5.5 / 5.7 / 5.8 / 7.2")       \
     X(fwd16, 1, "the 16 -> 16 full-resolution layer and the depth head behind it in one pass (k_fwd16_head, csrc/fwd16.hip)")          \
     X(fwd16_wgs, 1024, "... its grid (at least; one workgroup per 8 tiles beyond that)")                                              \
     X(fwd16_tiles_per_wg, 32, "... tiles per workgroup beyond fwd16_wgs (grid in whole rounds of 1024)")                                       \

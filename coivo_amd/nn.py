@@ -115,9 +115,9 @@ class _ArenaModule(Arena, RecordedPasses, SideChain, nn.Module):
         return t
 
 
-def _conv(x0, L: ConvParams, desc, x1=None):
+def _conv(x0, L: ConvParams, desc, x1=None, whole_k: bool = False):
     y = torch.empty(desc.B, desc.Ho, desc.Wo, desc.Cout, device=x0.device, dtype=x0.dtype)
-    ops.conv_fwd(desc, x0, x1, L.w_fwd, L.bias.data, y)
+    ops.conv_fwd(desc, x0, x1, L.w_fwd, L.bias.data, y, whole_k)
     return y
 
 
@@ -528,8 +528,10 @@ class PoseNet(_ArenaModule):
         P = self._plan(B, H, W)
         # the planner's answer follows the tuning table (`pose_front`): asked per call, and part of the recorded pass's key
         P["front"] = front = ops.pose_front_plan(P[1]) is not None
+        # ... and conv5-conv7 one by one (`pose_tail`, csrc/pose_tail.hip): the whole-K resident form where the planner selects it
+        P["tail"] = tail = tuple(ops.pose_tail_plan(P[i]) is not None for i in (5, 6, 7))
         out = torch.empty(8 * B, device=tgt.device, dtype=torch.float32)     # planar: [pose Bx6 | a B | b B]
-        inst = self._acquire((B, H, W, dt, front, has_depth))
+        inst = self._acquire((B, H, W, dt, front, tail, has_depth))
 
         def body():
             x = filled if filled is not None else ops.pack_nchw(srcs, 8, dt)
@@ -545,7 +547,7 @@ class PoseNet(_ArenaModule):
                 ops.conv_fwd_chain(P[1], x, lays)
                 x, first = A[3], 4
             for i in range(first, len(POSE_LAYERS)):
-                A[i] = x = _conv(x, getattr(self, POSE_LAYERS[i - 1][0]), P[i])
+                A[i] = x = _conv(x, getattr(self, POSE_LAYERS[i - 1][0]), P[i], whole_k=5 <= i <= 7 and tail[i - 5])
             ops.pose_head_fwd(x, self.pred.w_master, self.pred.bias.data, out)
             return A
 
@@ -570,6 +572,7 @@ class PoseNet(_ArenaModule):
         d_t, d_r = (d_tr[0], d_tr[1]) if has_depth else (None, None)
         # the input-gradient chain ends in the depth planes: only a call with depth maps has it (asked per call, as in the forward pass)
         chain = bool(has_depth) and _lib.dev_env("COLVO_NO_DGRAD_PLANES") is None and ops.pose_front_plan(P[1], 1) is not None
+        tail = tuple(ops.pose_tail_plan(P[i], 1) is not None for i in (5, 6, 7))      # (asked per call as well)
 
         def body():
             self._bwd_begin()
@@ -592,7 +595,7 @@ class PoseNet(_ArenaModule):
                     break
                 if i > 1:
                     dx = torch.empty_like(src)
-                    ops.conv_dgrad(P[i], 0, g, L.w_bwd, src, dx, False)
+                    ops.conv_dgrad(P[i], 0, g, L.w_bwd, src, dx, False, whole_k=5 <= i <= 7 and tail[i - 5])
                     g = dx
                 elif has_depth and _lib.dev_env("COLVO_NO_DGRAD_PLANES") is None:
                     # only the two depth channels of the 8-channel input gradient are wanted, as fp32 planes: one small kernel
@@ -609,7 +612,8 @@ class PoseNet(_ArenaModule):
             ext["d_tr"] = d_tr
         if filled is not None:
             ext["in"] = filled
-        which = "bwd:" + ",".join(sorted(grads)) + (",chain" if chain else "")     # a missing (None) gradient changes the recorded commands
+        # a missing (None) gradient changes the recorded commands, and so do the planners' answers
+        which = "bwd:" + ",".join(sorted(grads)) + ",tail" + "".join(str(int(t)) for t in tail) + (",chain" if chain else "")
         self._run_pass(inst, which, ext, body)
         return d_t, d_r
 

@@ -53,9 +53,19 @@ def conv_desc(dtype: torch.dtype, B: int, Hi: int, Wi: int, C0: int, Cout: int, 
     return d
 
 
-def conv_fwd(d: ConvDesc, x0, x1, w_fwd, bias, y) -> None:
+def conv_fwd(d: ConvDesc, x0, x1, w_fwd, bias, y, whole_k: bool = False) -> None:
+    """whole_k: the whole-K resident form (i[0] = -1 of CMD_CONV_FWD; refused where pose_tail_plan(d) is None)."""
     _need_cuda(x0, x1, w_fwd, bias, y)
-    _issue(_lib.CMD_CONV_FWD, d, (x0, x1, w_fwd, bias, y))
+    _issue(_lib.CMD_CONV_FWD, d, (x0, x1, w_fwd, bias, y), (-1,) if whole_k else ())
+
+
+def pose_tail_plan(d: ConvDesc, direction: int = 0) -> Optional[Tuple[int, int, int, int]]:
+    """(workgroups, images per workgroup, LDS bytes, kernel kind) of the whole-K resident launch of layer d -- forward (direction 0)
+    or input gradient (1) -- or None where it is not selected (include/colvo.h colvo_pose_tail_plan; no GPU needed)."""
+    out = (C.c_int32 * 4)()
+    if not _lib.load().colvo_pose_tail_plan(C.byref(d), int(direction), out):
+        return None
+    return tuple(int(v) for v in out)
 
 
 def pose_front_plan(d1: ConvDesc, direction: int = 0) -> Optional[Tuple[int, int, int, int]]:
@@ -85,9 +95,10 @@ def conv_dgrad_chain(d1: ConvDesc, g3, w_bwd3, w_bwd2, act2, act1, g2, g1, w_mas
     _issue(_lib.CMD_CONV_DGRAD_PLANES, d1, (g1, w_master1, dst, g3, w_bwd3, w_bwd2, act2, act1, g2, g1), (c_begin, c_count, 0))
 
 
-def conv_dgrad(d: ConvDesc, src: int, dy, w_bwd, relu_mask, dx, accumulate: bool) -> None:
+def conv_dgrad(d: ConvDesc, src: int, dy, w_bwd, relu_mask, dx, accumulate: bool, whole_k: bool = False) -> None:
+    """whole_k: the whole-K resident form (i[2] = 1 of CMD_CONV_DGRAD; refused where pose_tail_plan(d, 1) is None)."""
     _need_cuda(dy, w_bwd, relu_mask, dx)
-    _issue(_lib.CMD_CONV_DGRAD, d, (dy, w_bwd, relu_mask, dx), (src, int(accumulate)))
+    _issue(_lib.CMD_CONV_DGRAD, d, (dy, w_bwd, relu_mask, dx), (src, int(accumulate)) + ((1,) if whole_k else ()))
 
 
 def conv_dgrad_both(d: ConvDesc, dy, w_bwd, relu_mask0, relu_mask1, dx0, dx1) -> None:

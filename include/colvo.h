@@ -193,6 +193,20 @@ int colvo_conv_fwd(const ColvoConvDesc* d, const void* x0, const void* x1, const
  * bits); otherwise 1, and out (may be NULL) receives {workgroups, conv3 tile rows, conv3 tile columns, LDS bytes}. */
 int colvo_pose_front_plan(const ColvoConvDesc* d1, int direction, int32_t* out);
 
+/* PoseNet's deep layers conv5-conv7 (3x3, stride 2, bf16, 128 or 256 input channels of the launch's K) as WHOLE-K RESIDENT launches
+ * at small batches (csrc/pose_tail.hip): a workgroup owns 16 output channels x the pixels of whole images, requests its whole weight
+ * slab and source maps up front and runs complete K chains out of LDS, instead of walking 4-8 channel chunks one round trip at a
+ * time.  Plan query, no side effect: reads d -- the LAYER's descriptor -- and the tuning table, calls no HIP and counts no form.
+ * direction 0: the forward pass (the bits of colvo_conv_fwd); direction 1: the input gradient w.r.t. source 0 (the bits of
+ * colvo_conv_dgrad without accumulate; tuning entry `pose_tail_bwd` on top of `pose_tail`).  Returns 0 when the layer is not selected:
+ * tuning entry off, f32, not stride 2, a second or up-sampled source, K not 128 or 256, output channels not a multiple of 16, more
+ * than `pose_tail_max_pairs` images, operands beyond 160 KB of LDS, or a shape at which the plain call would not run the form the
+ * bits are tied to (k_conv3x3 over 32-channel chunks forward; k_dgrad_s2, or k_conv3x3 over the zero-dilated dy, backward).
+ * Otherwise 1, and out (may be NULL) receives {workgroups, images per workgroup, LDS bytes, kernel kind (0: conv order, 1: k_dgrad_s2
+ * order)}.  The form is reached only by explicit request: COLVO_CMD_CONV_FWD with i[0] = -1, COLVO_CMD_CONV_DGRAD with i[2] = 1
+ * (below); a request at a shape this query does not select is an error, never a fall-back, and the plain entry points never take it. */
+int colvo_pose_tail_plan(const ColvoConvDesc* d, int direction, int32_t* out);
+
 /* Input gradient of source `src` (0 or 1).  dy[B,Ho,Wo,Cout] must already be the gradient w.r.t. the
  * pre-activation (see relu_mask below).  w_bwd: weights packed [C0+C1][ksize*ksize][Cout].
  * dx has the STORED shape of the source (half resolution when up-sampled).
@@ -1110,8 +1124,10 @@ int colvo_read_npy_u8_frames(const char* const* paths, int n, int h, int w, uint
  * ------------------------------------------------------------------------------------------- */
 enum {
     COLVO_CMD_CONV_FWD = 1,      /* p: x0 x1 w_fwd bias y; chain form (i[0] = 3, colvo_pose_front_plan): p: x - w1 b1 y1 w2 b2 y2 w3 b3 y3;
-                                    i: 3 and the three output channel counts (16 32 64); desc: the first layer's */
-    COLVO_CMD_CONV_DGRAD,        /* i: src accumulate; p: dy w_bwd relu_mask dx */
+                                    i: 3 and the three output channel counts (16 32 64); desc: the first layer's;
+                                    whole-K form (i[0] = -1, colvo_pose_tail_plan): p as in the plain form with x1 NULL */
+    COLVO_CMD_CONV_DGRAD,        /* i: src accumulate; p: dy w_bwd relu_mask dx; whole-K form (i[2] = 1, colvo_pose_tail_plan
+                                    direction 1): i: 0 0 1, p as in the plain form */
     COLVO_CMD_CONV_WGRAD,        /* p: x0 x1 dy dw db scratch; i: scratch_bytes slabs_only arena_is_zero (scratch != NULL:
                                     colvo_conv_wgrad_det, or with slabs_only colvo_conv_wgrad_slabs; scratch == NULL and arena_is_zero:
                                     colvo_conv_wgrad_clean -- the host patches that integer before each replay) */
