@@ -8,6 +8,7 @@
 
 #include <atomic>
 #include <mutex>
+#include <utility>
 
 #include "../../include/colvo.h"
 
@@ -78,6 +79,16 @@ inline int allow_dynamic_lds(size_t lds, int limit, const char* who) {
     const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, limit);
     if (e != hipSuccess) { set_error("%s: dynamic LDS opt-in failed: %s", who, hipGetErrorString(e)); return (int)e; }
     done.store(true, std::memory_order_release);
+    return 0;
+}
+
+// The launch of a resident kernel (one workgroup per CU, up to the whole 160 KB of LDS): opt-in, launch, check.  who: the caller's
+// name for the opt-in's error; name: the kernel's for the launch's.
+template <auto Kernel, typename... A>
+inline int launch_resident(unsigned grid, int nt, int lds, hipStream_t s, const char* who, const char* name, A&&... args) {
+    if (int e = allow_dynamic_lds<Kernel>((size_t)lds, 160 * 1024, who)) return e;
+    colvo::launch(Kernel, dim3(grid), dim3((unsigned)nt), (unsigned)lds, s, std::forward<A>(args)...);
+    COLVO_CHECK_LAUNCH(name);
     return 0;
 }
 

@@ -34,7 +34,7 @@
 //   - both operands have the reduction index (pixel) as the slow LDS dimension: bf16 fragments are
 //     read with ds_read_b64_tr_b16 (hardware transpose), f32 fragments with plain ds_read_b32.
 #define COLVO_ACC_CONSTRAINT "+v"     // built with -mllvm -amdgpu-mfma-vgpr-form (coivo_amd/build.py)
-#include "conv_common.h"
+#include "conv_lane.h"
 #include "conv_stage.h"
 
 namespace colvo {
@@ -120,13 +120,8 @@ __device__ __forceinline__ void conv_epilogue(const ConvK& a, const float* sOut,
         } else {
             if (a.mask) {
                 const u32x4 m = ld16(a.mask + off);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    // bf16 > 0  <=>  sign clear and magnitude non-zero
-                    const uint32_t lo = m[k] & 0xFFFFu, hi = m[k] >> 16;
-                    if (!(lo != 0 && lo < 0x8000u)) v[2 * k] = 0.0f;
-                    if (!(hi != 0 && hi < 0x8000u)) v[2 * k + 1] = 0.0f;
-                }
+                relu_mask_keep(m[0], m[1], v);
+                relu_mask_keep(m[2], m[3], v + 4);
             }
             if (a.accumulate) {
                 const u32x4 o = ld16(a.out + off);
@@ -224,12 +219,7 @@ struct Epi {
 #pragma unroll
             for (int mf = 0; mf < 2; ++mf) {
                 float v[4];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) v[r] = acc[mf][nf][r] + __uint_as_float(bs[r]);
-                if (a.relu) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.0f);
-                }
+                lane_bias_relu(acc[mf][nf], bs, a.relu, v);
                 if constexpr (ES == 4) {
                     if (a.mask) {
 #pragma unroll
@@ -244,15 +234,7 @@ struct Epi {
                     for (int r = 0; r < 4; ++r) o[r] = __float_as_uint(v[r]);
                     __builtin_amdgcn_raw_buffer_store_b128(o, rout, off[mf][nf], soff, 0);
                 } else {
-                    if (a.mask) {
-#pragma unroll
-                        for (int k = 0; k < 2; ++k) {
-                            // bf16 > 0  <=>  sign clear and magnitude non-zero
-                            const uint32_t lo = pm[mf][nf][k] & 0xFFFFu, hi = pm[mf][nf][k] >> 16;
-                            if (!(lo != 0 && lo < 0x8000u)) v[2 * k] = 0.0f;
-                            if (!(hi != 0 && hi < 0x8000u)) v[2 * k + 1] = 0.0f;
-                        }
-                    }
+                    if (a.mask) relu_mask_keep(pm[mf][nf][0], pm[mf][nf][1], v);
                     if (a.accumulate) {
 #pragma unroll
                         for (int k = 0; k < 2; ++k) {
@@ -260,10 +242,7 @@ struct Epi {
                             v[2 * k + 1] += bf2f((uint16_t)(pa[mf][nf][k] >> 16));
                         }
                     }
-                    u32x2 o;
-#pragma unroll
-                    for (int k = 0; k < 2; ++k) o[k] = pack2bf(v[2 * k], v[2 * k + 1]);
-                    __builtin_amdgcn_raw_buffer_store_b64(o, rout, off[mf][nf], soff, 0);
+                    __builtin_amdgcn_raw_buffer_store_b64(lane_pack_bf16(v), rout, off[mf][nf], soff, 0);
                 }
             }
         }
@@ -618,7 +597,8 @@ __global__ __launch_bounds__(NTH, NTH == 512 ? 4 : ((BN <= 32 && DEPTH == 1 && !
 // chunks a k-group IS a tap, so each k-group's MFMAs go to the accumulator set of the tap's parity class (4 sets), reading
 // the patch at the tap's (+1 row if ky == 0, +1 column if kx == 0) offset.  Same MFMA count as one ordinary 3x3 tile, but
 // 512 input-gradient pixels instead of 128: a quarter of the MFMAs, a quarter of the workgroups, no dead patch bytes.
-// The weight operand is the flipped layout w_bwd [Cin][8 - tap][Cout] the dilated form uses (slot m holds tap 8 - m).
+// The weight operand is the flipped layout w_bwd [Cin][8 - tap][Cout] the dilated form uses; which tap, class and offset a slot
+// means is conv_lane.h's s2_tap, shared with the resident kernels that promise this kernel's sums.
 template <typename T, int BN, int DEPTH, int NCH = 0>
 __global__ __launch_bounds__(NT, (DEPTH == 1 && TT<T>::ES == 2) ? 3 : 2) void k_dgrad_s2(const ConvK a) {
     constexpr int G = TT<T>::G, ES = TT<T>::ES;
@@ -689,8 +669,8 @@ __global__ __launch_bounds__(NT, (DEPTH == 1 && TT<T>::ES == 2) ? 3 : 2) void k_
         }
         u32x4 av[2][2], bv[2][NF];
         auto read_frags = [&](int m, u32x4 (&ar)[2], u32x4 (&br)[NF]) {
-            const int t = 8 - m, ky = t / 3, kx = t - 3 * ky;       // slot m of the flipped slab holds tap 8 - m
-            const int aoff = ((ky == 0 ? a.pwp : 0) + (kx == 0 ? 1 : 0)) * PIXP + kg * 16;
+            const S2Tap tp = s2_tap(m);
+            const int aoff = ((tp.dy ? a.pwp : 0) + tp.dx) * PIXP + kg * 16;
 #pragma unroll
             for (int mf = 0; mf < 2; ++mf) ar[mf] = ld16(sP + pbase[mf] + aoff);
 #pragma unroll
@@ -701,8 +681,7 @@ __global__ __launch_bounds__(NT, (DEPTH == 1 && TT<T>::ES == 2) ? 3 : 2) void k_
         for (int m = 0; m < STEPS; ++m) {
             const int cur = m & 1;
             if (m + 1 < STEPS) read_frags(m + 1, av[cur ^ 1], bv[cur ^ 1]);
-            const int t = 8 - m, ky = t / 3, kx = t - 3 * ky;
-            const int cls = (ky != 1 ? 2 : 0) | (kx != 1 ? 1 : 0);   // parity class (iy & 1, ix & 1) this tap feeds
+            const int cls = s2_tap(m).cls;                 // parity class (iy & 1, ix & 1) this tap feeds
             if constexpr (ES == 2) {
 #pragma unroll
                 for (int mf = 0; mf < 2; ++mf)
@@ -1385,8 +1364,7 @@ __global__ __launch_bounds__(NT) void k_conv3x3_res(const ConvK a, int ntiles, u
 // host side                                                                                      //
 // --------------------------------------------------------------------------------------------- //
 // Every call plans first (conv_plan: form, instantiation, tile, grid, LDS and form counters; no HIP call, no counter moved) and
-// then runs the plan (launch_plan).
-enum { PASS_FWD, PASS_DGRAD, PASS_DGRAD_BOTH };
+// then runs the plan (launch_plan).  PASS_* and the forms: conv_common.h.
 
 // The LDS and 1-D grid of a one-tile kernel (k_conv3x3, k_conv_up2, k_dgrad_up2, k_dgrad_s2) over the tile k carries
 int plan_tiles(ConvK& k, int B, ConvPlan& p, size_t lds, size_t lds_max, const char* what, const char* name) {
@@ -1813,48 +1791,23 @@ inline ConvK dgrad_conv(const ColvoConvDesc* d, const void* dy, const void* w_bw
 }  // namespace
 }  // namespace colvo
 
-// pose_front.hip's planner: would colvo_conv_fwd run layer d as the plain one-tile kernel (k_conv3x3, 256 threads, one chunk in
-// flight)?  Plans only: no HIP call, no form counted.
+// The planners of the resident kernels: the plan the plain call would run for d (conv_common.h)
 namespace colvo {
-bool conv_fwd_is_one_tile(const ColvoConvDesc* d) {
-    if (check_desc(d, "colvo_pose_front_plan")) return false;
+PlainForm conv_plain_form(const ColvoConvDesc* d, int pass, const char* who) {
+    const PlainForm none{-1, 0, 0, 0, 0, false};
+    if ((pass != PASS_FWD && pass != PASS_DGRAD) || check_desc(d, who) || (pass == PASS_DGRAD && d->C1 != 0)) return none;
     ConvK k{};
-    fill_gather(d, nullptr, nullptr, k.g);
-    k.Ho = d->Ho; k.Wo = d->Wo;
-    k.Ctot = d->C0 + d->C1; k.N = d->Cout;
-    k.relu = d->relu;
+    if (pass == PASS_FWD) {
+        fill_gather(d, nullptr, nullptr, k.g);
+        k.Ho = d->Ho; k.Wo = d->Wo;
+        k.Ctot = d->C0 + d->C1; k.N = d->Cout;
+        k.relu = d->relu;
+    } else {
+        k = dgrad_conv(d, nullptr, nullptr, 0, d->C0, nullptr, nullptr, 0);
+    }
     ConvPlan p{};
-    if (conv_plan(d, PASS_FWD, 0, k, p)) return false;
-    return p.form == CONV_TILE && p.nth == NT && p.depth == 1;
-}
-// ... and would colvo_conv_dgrad run layer d's input gradient as k_dgrad_s2 with one chunk in flight?
-bool conv_dgrad_is_s2_tile(const ColvoConvDesc* d) {
-    if (check_desc(d, "colvo_pose_front_plan") || d->C1 != 0) return false;
-    ConvK k = dgrad_conv(d, nullptr, nullptr, 0, d->C0, nullptr, nullptr, 0);
-    ConvPlan p{};
-    if (conv_plan(d, PASS_DGRAD, d->up0, k, p)) return false;
-    return p.form == DGRAD_S2 && p.nch == 0;
-}
-// pose_tail.hip's planner: k_conv3x3 in any of its one-tile forms (one chunk in flight, the two-chunk ring, 512 threads) walks the
-// 32-channel chunks in ascending order, tap by tap: one sum order
-bool conv_fwd_is_tile_chunks32(const ColvoConvDesc* d) {
-    if (check_desc(d, "colvo_pose_tail_plan")) return false;
-    ConvK k{};
-    fill_gather(d, nullptr, nullptr, k.g);
-    k.Ho = d->Ho; k.Wo = d->Wo;
-    k.Ctot = d->C0 + d->C1; k.N = d->Cout;
-    k.relu = d->relu;
-    ConvPlan p{};
-    if (conv_plan(d, PASS_FWD, 0, k, p)) return false;
-    return p.form == CONV_TILE && p.ng == 4;
-}
-int conv_dgrad_kind(const ColvoConvDesc* d) {
-    if (check_desc(d, "colvo_pose_tail_plan") || d->C1 != 0) return DGRAD_KIND_OTHER;
-    ConvK k = dgrad_conv(d, nullptr, nullptr, 0, d->C0, nullptr, nullptr, 0);
-    ConvPlan p{};
-    if (conv_plan(d, PASS_DGRAD, d->up0, k, p)) return DGRAD_KIND_OTHER;
-    if (p.form == DGRAD_S2) return DGRAD_KIND_S2;
-    return p.form == CONV_TILE && p.ng == 4 && k.g.mode[0] == MODE_DILATE && !k.pool2 ? DGRAD_KIND_DILATED_TILE : DGRAD_KIND_OTHER;
+    if (conv_plan(d, pass, pass == PASS_DGRAD ? d->up0 : 0, k, p)) return none;
+    return PlainForm{p.form, p.ng, p.nth, p.depth, p.nch, k.g.mode[0] == MODE_DILATE && !k.pool2};
 }
 }  // namespace colvo
 

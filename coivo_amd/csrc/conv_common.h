@@ -54,6 +54,7 @@ struct ConvK {
 
 // A forward / input-gradient launch, decided by conv_plan (conv.hip) before any HIP call: the form, its kernel instantiation, LDS,
 // grid, extra kernel arguments and the form counters the launch records.
+enum { PASS_FWD, PASS_DGRAD, PASS_DGRAD_BOTH };
 enum { CONV_UP2, CONV_RT, CONV_Q, CONV_RES, CONV_RES_S2, CONV_TILE, DGRAD_S2, DGRAD_UP2 };
 struct ConvPlan {
     int form;
@@ -73,15 +74,12 @@ struct ConvPlan {
 bool conv_rt_plan(ConvK& k, int B, int dtype, ConvPlan& p);
 int conv_rt_launch(const ConvK& k, const ConvPlan& p, int dtype, hipStream_t s);
 
-// conv.hip, for pose_front.hip's planner: whether colvo_conv_fwd would run layer d as the plain one-tile kernel, and colvo_conv_dgrad
-// its input gradient as k_dgrad_s2 with one chunk in flight.  Plans only: no HIP call, no form counted.
-bool conv_fwd_is_one_tile(const ColvoConvDesc* d);
-bool conv_dgrad_is_s2_tile(const ColvoConvDesc* d);
-// ... and for pose_tail.hip's: whether colvo_conv_fwd would run layer d as k_conv3x3 over 32-channel chunks (any of its one-tile forms:
-// they add a column's products in one order), and which kernel colvo_conv_dgrad would run for its input gradient
-bool conv_fwd_is_tile_chunks32(const ColvoConvDesc* d);
-enum { DGRAD_KIND_OTHER = 0, DGRAD_KIND_S2, DGRAD_KIND_DILATED_TILE };       // k_dgrad_s2; k_conv3x3 over the zero-dilated dy, 32-channel chunks
-int conv_dgrad_kind(const ColvoConvDesc* d);
+// conv.hip, for the planners of the resident kernels (pose_front.hip, pose_tail.hip): which kernel, in which sum order, the plain call
+// would run for descriptor d -- colvo_conv_fwd (PASS_FWD) or colvo_conv_dgrad for source 0 (PASS_DGRAD; a concat layer is refused).
+// form: ConvPlan's, < 0 where the descriptor is refused or not planned; ng, nth, depth, nch: ConvPlan's; dilated: the launch is
+// k_conv3x3 reading the zero-dilated dy directly (no 2x2 pooling behind it).  Plans only: no HIP call, no form counted.
+struct PlainForm { int form; int ng, nth, depth, nch; bool dilated; };
+PlainForm conv_plain_form(const ColvoConvDesc* d, int pass, const char* who);
 
 // Where a weight-gradient kernel puts its sums: part of the kernel argument of all three kernels (k_wgrad3x3, k_wgrad_up2, k_wgrad_rt),
 // filled once per launch by wgrad.hip's wgrad_resolve.  Device pointers and flags only.

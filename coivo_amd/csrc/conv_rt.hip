@@ -24,7 +24,7 @@
 // Selected by conv_rt_plan for direct (not up-sampled / dilated) sources in whole 32-channel chunks when the 16 x 16 tiling
 // wastes little of the image and the grid has at least rt_min_wgs workgroups (tuning.h).
 #define COLVO_ACC_CONSTRAINT "+v"     // built with -mllvm -amdgpu-mfma-vgpr-form (coivo_amd/build.py)
-#include "conv_common.h"
+#include "conv_lane.h"
 #include "conv_stage.h"
 
 namespace colvo {
@@ -265,12 +265,7 @@ __global__ __launch_bounds__(NT, (NF == 2 && TT<T>::ES == 2) ? 3 : 2) void k_con
 #pragma unroll
                 for (int nf = 0; nf < NF; ++nf) {
                     float v[4];
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) v[q] = acc[r][nf][q] + __uint_as_float(biasv[nf][q]);
-                    if (a.relu) {
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) v[q] = fmaxf(v[q], 0.0f);
-                    }
+                    lane_bias_relu(acc[r][nf], biasv[nf], a.relu, v);
                     if constexpr (ES == 4) {
                         if (mask) {
 #pragma unroll
@@ -285,15 +280,7 @@ __global__ __launch_bounds__(NT, (NF == 2 && TT<T>::ES == 2) ? 3 : 2) void k_con
                         for (int q = 0; q < 4; ++q) o[q] = __float_as_uint(v[q]);
                         __builtin_amdgcn_raw_buffer_store_b128(o, rout, obase + noff[nf], 0, 0);
                     } else {
-                        if (mask) {
-#pragma unroll
-                            for (int q = 0; q < 2; ++q) {
-                                // bf16 > 0  <=>  sign clear and magnitude non-zero
-                                const uint32_t lo = pm[nf][q] & 0xFFFFu, hi = pm[nf][q] >> 16;
-                                if (!(lo != 0 && lo < 0x8000u)) v[2 * q] = 0.0f;
-                                if (!(hi != 0 && hi < 0x8000u)) v[2 * q + 1] = 0.0f;
-                            }
-                        }
+                        if (mask) relu_mask_keep(pm[nf][0], pm[nf][1], v);
                         if (a.accumulate) {
 #pragma unroll
                             for (int q = 0; q < 2; ++q) {
@@ -301,10 +288,7 @@ __global__ __launch_bounds__(NT, (NF == 2 && TT<T>::ES == 2) ? 3 : 2) void k_con
                                 v[2 * q + 1] += bf2f((uint16_t)(pa[nf][q] >> 16));
                             }
                         }
-                        u32x2 o;
-#pragma unroll
-                        for (int q = 0; q < 2; ++q) o[q] = pack2bf(v[2 * q], v[2 * q + 1]);
-                        __builtin_amdgcn_raw_buffer_store_b64(o, rout, obase + noff[nf], 0, 0);
+                        __builtin_amdgcn_raw_buffer_store_b64(lane_pack_bf16(v), rout, obase + noff[nf], 0, 0);
                     }
                 }
             }

@@ -9,14 +9,15 @@
 // Bits: every output element is the sum the one-tile kernel k_conv3x3 (conv.hip) forms for it -- one channel chunk per layer, the
 // same v_mfma_f32_16x16x32_bf16 per k-group of four 16-byte granules (granule = tap * NG + channel granule, padded k-groups read
 // tap 8's pixels against zero weights), k-groups in ascending order from a zero accumulator, the in-place terminator of
-// mfma_result_guard, then bias, ReLU and one v_cvt_pk_bf16_f32.  Which pixels share a fragment does not enter a column's sum, so
-// the three maps are byte-identical to three colvo_conv_fwd calls in their one-tile form (tests/test_pose_front_gpu.py); the
-// planner selects the chain only where that is the form they would take.
+// mfma_result_guard, then the close the plain kernels use (conv_lane.h lane_close_bf16; DESIGN.md section 3.3 has the rule).  Which
+// pixels share a fragment does not enter a column's sum, so the three maps are byte-identical to three colvo_conv_fwd calls in their
+// one-tile form (tests/test_pose_front_gpu.py); the planner selects the chain only where conv_plain_form says that is the form
+// they would take.
 //
 // The padding trap: each level's zero padding is the border of that level's MAP.  A halo position outside conv1's (conv2's) map is
 // stored as zero in the LDS tile, never as the layer evaluated outside the image.
 #define COLVO_ACC_CONSTRAINT "+v"     // built with -mllvm -amdgpu-mfma-vgpr-form (coivo_amd/build.py)
-#include "conv_common.h"
+#include "conv_lane.h"
 
 namespace colvo {
 namespace {
@@ -94,16 +95,9 @@ __device__ __forceinline__ void pose_front_level(const char* sIn, int inW, const
         for (int m = 0; m < STEPS; ++m)
             acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, bv[m]), __builtin_bit_cast(bf16x8, av[m]), acc[0],
                                                              0, 0, 0);
-        const f32x4 bs = *reinterpret_cast<const f32x4*>(sBias + nf * 16 + kg * 4);
+        const u32x4 bs = *reinterpret_cast<const u32x4*>(sBias + nf * 16 + kg * 4);
         mfma_result_guard<bf16_t>(acc);
-        float v[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = acc[0][r] + bs[r];
-        if (relu) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.0f);
-        }
-        u32x2 o = {pack2bf(v[0], v[1]), pack2bf(v[2], v[3])};
+        u32x2 o = lane_close_bf16(acc[0], bs, relu, false, u32x2{0u, 0u});
         const int gy = gy0 + oy, gx = gx0 + ox;
         const bool inmap = valid && (unsigned)gy < (unsigned)Hm && (unsigned)gx < (unsigned)Wm;
         if (sOut != nullptr && valid) {
@@ -230,10 +224,9 @@ __global__ __launch_bounds__(PF_NT, 1) void k_pose_front_fwd(const PoseFrontK a,
 // a slightly larger patch of the level above: the parity classes of a stride-2 input gradient at position (gy, gx) read
 // dy[gy .. gy + 1][gx .. gx + 1], so the workgroup that owns a toh x tow tile of g3 positions writes 2 toh x 2 tow of g2, 4 toh x 4 tow
 // of g1 and 8 toh x 8 tow of each plane, and recomputes ONE extra row and column of g2 and of g1 (even parity: they need no further
-// g3).  Bits: per dy position the nine taps run once in k_dgrad_s2's order (slot m of the flipped slab holds tap 8 - m, chunk by
-// chunk) into the four class accumulators, closed by mfma_result_guard, then + 0 (the kernel's absent bias), the producer's ReLU mask
-// and one v_cvt_pk_bf16_f32; the planes are k_dgrad_planes_s2_mfma's six MFMAs per 16 blocks with its three-term bf16 split of the
-// fp32 master weights.
+// g3).  Bits: per dy position the nine taps run once in k_dgrad_s2's order (conv_lane.h s2_tap, chunk by chunk) into the four class
+// accumulators, closed by mfma_result_guard and lane_close_bf16 with no bias and the producer's ReLU mask; the planes are
+// k_dgrad_planes_s2_mfma's six MFMAs per 16 blocks with its three-term bf16 split of the fp32 master weights.
 constexpr int PB_PIX3 = pitch_bytes(128), PB_PIX2 = pitch_bytes(64), PB_PIX1 = pitch_bytes(32);
 constexpr int PB_WROW3 = wrow_bytes(72), PB_WROW2 = wrow_bytes(36);     // conv3: two 36-granule chunks per row; conv2: one
 
@@ -304,14 +297,13 @@ __device__ __forceinline__ void pose_back_level(const char* sIn, int inW, const 
             u32x4 av[9], bv[9];
 #pragma unroll
             for (int m = 0; m < 9; ++m) {
-                const int t = 8 - m, ky = t / 3, kx = t - 3 * ky;       // slot m of the flipped slab holds tap 8 - m
-                av[m] = ld16(pin + ((ky == 0 ? inW : 0) + (kx == 0 ? 1 : 0)) * IN_PIX + k * 64);
+                const S2Tap tp = s2_tap(m);
+                av[m] = ld16(pin + ((tp.dy ? inW : 0) + tp.dx) * IN_PIX + k * 64);
                 bv[m] = ld16(pw + (k * 36 + 4 * m) * 16);
             }
 #pragma unroll
             for (int m = 0; m < 9; ++m) {
-                const int t = 8 - m, ky = t / 3, kx = t - 3 * ky;
-                const int cls = (ky != 1 ? 2 : 0) | (kx != 1 ? 1 : 0);
+                const int cls = s2_tap(m).cls;
                 acc[cls] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, bv[m]), __builtin_bit_cast(bf16x8, av[m]),
                                                                    acc[cls], 0, 0, 0);
             }
@@ -319,17 +311,8 @@ __device__ __forceinline__ void pose_back_level(const char* sIn, int inW, const 
         mfma_result_guard<bf16_t>(acc);
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-            float v[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] = acc[c][r] + 0.0f;        // (k_dgrad_s2's epilogue adds its zero bias: -0 becomes +0)
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                // bf16 > 0  <=>  sign clear and magnitude non-zero
-                const uint32_t lo = pm[c][k] & 0xFFFFu, hi = pm[c][k] >> 16;
-                if (!(lo != 0 && lo < 0x8000u)) v[2 * k] = 0.0f;
-                if (!(hi != 0 && hi < 0x8000u)) v[2 * k + 1] = 0.0f;
-            }
-            const u32x2 o = {pack2bf(v[0], v[1]), pack2bf(v[2], v[3])};
+            // (k_dgrad_s2's epilogue adds its zero bias)
+            const u32x2 o = lane_close_bf16(acc[c], u32x4{0u, 0u, 0u, 0u}, 0, true, pm[c]);
             if (loff[c] >= 0) *reinterpret_cast<u32x2*>(sOut + loff[c]) = o;
             __builtin_amdgcn_raw_buffer_store_b64(o, rout, goff[c], 0, 0);                         // out of range: dropped
         }
@@ -502,14 +485,18 @@ bool pose_front_plan(const ColvoConvDesc* d1, int direction, PoseFrontPlan& p) {
     // directions, so that one batch size (13 pairs of 256x320, where conv2 goes to the stride-2 resident kernel) ends both chains --
     for (int i = 0; i < 3; ++i) {
         const ColvoConvDesc d = pose_front_layer(*d1, i);
-        if (!conv_fwd_is_one_tile(&d)) return false;
+        const PlainForm f = conv_plain_form(&d, PASS_FWD, "colvo_pose_front_plan");
+        // k_conv3x3, 256 threads, one chunk in flight: k-groups in ascending order into one accumulator
+        if (!(f.form == CONV_TILE && f.nth == NT && f.depth == 1)) return false;
     }
     if (direction == 1) {
         // ... and the three replaced launches theirs: k_dgrad_s2 with one chunk in flight for conv3 and conv2, k_dgrad_planes_s2_mfma
         // (the condition of colvo_conv_dgrad_planes, csrc/dgrad_planes.hip)
         for (int i = 1; i < 3; ++i) {
             const ColvoConvDesc d = pose_front_layer(*d1, i);
-            if (!conv_dgrad_is_s2_tile(&d)) return false;
+            const PlainForm f = conv_plain_form(&d, PASS_DGRAD, "colvo_pose_front_plan");
+            // k_dgrad_s2, K loop not unrolled: s2_tap's order, chunk by chunk
+            if (!(f.form == DGRAD_S2 && f.nch == 0)) return false;
         }
         if ((long long)d1->B * d1->Ho * d1->Wo * 32 >= 0x7fffffffLL || TUNE(planes_mfma) == 0) return false;
     }
@@ -552,10 +539,8 @@ int pose_front_fwd(const ColvoCmd& c, hipStream_t s) {
     k.tow = p.tow; k.tiles_x = p.tiles_x; k.tiles_y = p.tiles_y;
     k.m_pw0 = mdiv_magic(8 * p.tow + 7); k.m_w1 = mdiv_magic(4 * p.tow + 3); k.m_w2 = mdiv_magic(2 * p.tow + 1); k.m_w3 = mdiv_magic(p.tow);
     k.relu = d->relu;
-    if (int e = allow_dynamic_lds<k_pose_front_fwd>((size_t)p.lds, 160 * 1024, "colvo_conv_fwd (chain)")) return e;
-    colvo::launch(k_pose_front_fwd, dim3((unsigned)p.nwg), dim3(PF_NT), (unsigned)p.lds, s, k, pose_front_lds(p.tow));
-    COLVO_CHECK_LAUNCH("k_pose_front_fwd");
-    return 0;
+    return launch_resident<k_pose_front_fwd>((unsigned)p.nwg, PF_NT, p.lds, s, "colvo_conv_fwd (chain)", "k_pose_front_fwd", k,
+                                             pose_front_lds(p.tow));
 }
 
 // CMD_CONV_DGRAD_PLANES with g3 in p[3] (program.hip): p = g1, w_master (conv1), d_tr, g3, w_bwd3, w_bwd2, act2, act1, g2, g1;
@@ -577,10 +562,8 @@ int pose_front_bwd(const ColvoCmd& c, hipStream_t s) {
     k.B = d->B; k.H = d->Hi; k.W = d->Wi; k.c_begin = c.i[0];
     k.tow = p.tow; k.tiles_x = p.tiles_x; k.tiles_y = p.tiles_y;
     k.m_p3 = mdiv_magic(p.tow + 2); k.m_n3 = mdiv_magic(p.tow + 1); k.m_n2 = mdiv_magic(2 * p.tow + 1);
-    if (int e = allow_dynamic_lds<k_pose_front_bwd>((size_t)p.lds, 160 * 1024, "colvo_conv_dgrad_planes (chain)")) return e;
-    colvo::launch(k_pose_front_bwd, dim3((unsigned)p.nwg), dim3(PF_NT), (unsigned)p.lds, s, k, pose_back_lds(p.tow));
-    COLVO_CHECK_LAUNCH("k_pose_front_bwd");
-    return 0;
+    return launch_resident<k_pose_front_bwd>((unsigned)p.nwg, PF_NT, p.lds, s, "colvo_conv_dgrad_planes (chain)", "k_pose_front_bwd", k,
+                                             pose_back_lds(p.tow));
 }
 
 }  // namespace colvo

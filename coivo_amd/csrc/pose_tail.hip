@@ -18,14 +18,15 @@
 //   * WK_CONV (forward; conv7's input gradient = stride-1 conv over the zero-dilated dy): k_conv3x3's order -- one accumulator per
 //     element, the 32-channel chunks in ascending order, within a chunk k-group m = tap m (granule 4 m + kg: tap m, channel granule
 //     kg), one v_mfma_f32_16x16x32_bf16 per (chunk, tap) with A = weights, B = pixels; a tap outside the map or on an inserted zero
-//     multiplies the weights by zeros and IS issued (the accumulator may hold -0).  Then mfma_result_guard's in-place terminator,
-//     + bias (+ 0 without one), ReLU, the producer's ReLU mask, one v_cvt_pk_bf16_f32.
-//   * WK_DGRAD_S2 (conv6's and conv5's input gradient): k_dgrad_s2's order -- per chunk, slot m of the flipped slab is tap 8 - m and
-//     goes to the accumulator of the tap's parity class, reading dy at (+1 row if ky == 0, +1 column if kx == 0); closed the same way.
+//     multiplies the weights by zeros and IS issued (the accumulator may hold -0).  Then mfma_result_guard's in-place terminator
+//     and the plain kernels' close (conv_lane.h lane_close_bf16; DESIGN.md section 3.3 has the rule).
+//   * WK_DGRAD_S2 (conv6's and conv5's input gradient): k_dgrad_s2's order -- per chunk, slot m of the flipped slab goes to the
+//     accumulator of its tap's parity class, reading dy at the tap's offset (conv_lane.h s2_tap); closed the same way.
 // Which pixels share a fragment does not enter a column's sum, so fragments may span images and channel tiles may be 16 wide.
-// The planner selects a layer only where the plain call would run one of exactly these forms (tests/test_pose_tail_gpu.py).
+// The planner selects a layer only where conv_plain_form says the plain call would run one of exactly these forms
+// (tests/test_pose_tail_gpu.py).
 #define COLVO_ACC_CONSTRAINT "+v"     // built with -mllvm -amdgpu-mfma-vgpr-form (coivo_amd/build.py)
-#include "conv_common.h"
+#include "conv_lane.h"
 
 namespace colvo {
 namespace {
@@ -155,6 +156,8 @@ __global__ __launch_bounds__(WK_NT, 1) void k_conv_wholek(const WholeK a) {
                                                                      acc[0], 0, 0, 0);
             }
             mfma_result_guard<bf16_t>(acc);
+            // lane_close_bf16 with its first half (lane_bias_relu) written out: through the helper hipcc swaps the source operands of
+            // the four bias adds, the only change in the listing (profiles/conv_lane_ab.md)
             float v[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) v[r] = acc[0][r] + __uint_as_float(biasv[r]);
@@ -162,16 +165,8 @@ __global__ __launch_bounds__(WK_NT, 1) void k_conv_wholek(const WholeK a) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.0f);
             }
-            if (a.mask) {
-#pragma unroll
-                for (int k = 0; k < 2; ++k) {
-                    // bf16 > 0  <=>  sign clear and magnitude non-zero
-                    const uint32_t lo = pm[k] & 0xFFFFu, hi = pm[k] >> 16;
-                    if (!(lo != 0 && lo < 0x8000u)) v[2 * k] = 0.0f;
-                    if (!(hi != 0 && hi < 0x8000u)) v[2 * k + 1] = 0.0f;
-                }
-            }
-            const u32x2 o = {pack2bf(v[0], v[1]), pack2bf(v[2], v[3])};
+            if (a.mask) relu_mask_keep(pm[0], pm[1], v);
+            const u32x2 o = lane_pack_bf16(v);
             __builtin_amdgcn_raw_buffer_store_b64(o, rout, goff, 0, 0);            // out of range: dropped
         } else {
             // position (oy, ox) of dy: parity class (py, px) of the input gradient is pixel (2 oy + py, 2 ox + px)
@@ -202,28 +197,16 @@ __global__ __launch_bounds__(WK_NT, 1) void k_conv_wholek(const WholeK a) {
                 for (int m = 0; m < 9; ++m) bv[m] = ld16(pw + (m * CG + k * 4) * 16);
 #pragma unroll
                 for (int m = 0; m < 9; ++m) {
-                    const int t = 8 - m, ky = t / 3, kx = t - 3 * ky;             // slot m of the flipped slab holds tap 8 - m
-                    const int cls = (ky != 1 ? 2 : 0) | (kx != 1 ? 1 : 0);
-                    const int q = (ky == 0 ? 2 : 0) | (kx == 0 ? 1 : 0);
-                    acc[cls] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, bv[m]), __builtin_bit_cast(bf16x8, av[q]),
-                                                                       acc[cls], 0, 0, 0);
+                    const S2Tap tp = s2_tap(m);
+                    acc[tp.cls] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                        __builtin_bit_cast(bf16x8, bv[m]), __builtin_bit_cast(bf16x8, av[2 * tp.dy + tp.dx]), acc[tp.cls], 0, 0, 0);
                 }
             }
             mfma_result_guard<bf16_t>(acc);
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
-                float v[4];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) v[r] = acc[c][r] + 0.0f;              // (k_dgrad_s2's epilogue adds its zero bias: -0 becomes +0)
-                if (a.mask) {
-#pragma unroll
-                    for (int k = 0; k < 2; ++k) {
-                        const uint32_t lo = pm[c][k] & 0xFFFFu, hi = pm[c][k] >> 16;
-                        if (!(lo != 0 && lo < 0x8000u)) v[2 * k] = 0.0f;
-                        if (!(hi != 0 && hi < 0x8000u)) v[2 * k + 1] = 0.0f;
-                    }
-                }
-                const u32x2 o = {pack2bf(v[0], v[1]), pack2bf(v[2], v[3])};
+                // (k_dgrad_s2's epilogue adds its zero bias)
+                const u32x2 o = lane_close_bf16(acc[c], u32x4{0u, 0u, 0u, 0u}, 0, a.mask != nullptr, pm[c]);
                 __builtin_amdgcn_raw_buffer_store_b64(o, rout, goff[c], 0, 0);
             }
         }
@@ -244,17 +227,20 @@ bool pose_tail_plan(const ColvoConvDesc* d, int direction, PoseTailPlan& p) {
     WholeK& k = p.k;
     k = WholeK{};
     // the bit guarantee is against ONE reference per layer and direction: the form the plain call would take
+    const PlainForm f = conv_plain_form(d, direction == 0 ? PASS_FWD : PASS_DGRAD, "colvo_pose_tail_plan");
+    // k_conv3x3 over 32-channel chunks, in any of its one-tile forms (one chunk in flight, the two-chunk ring, 512 threads): the chunks
+    // in ascending order, tap by tap
+    const bool tile32 = f.form == CONV_TILE && f.ng == 4;
     if (direction == 0) {
-        if (!conv_fwd_is_tile_chunks32(d)) return false;
+        if (!tile32) return false;
         p.kind = WK_CONV;
         k.Hs = d->Hi; k.Ws = d->Wi; k.Ho = d->Ho; k.Wo = d->Wo; k.S = 2; k.dil = 0;
         k.pixp = pitch_bytes_s2(K * 2);            // consecutive fragment rows are two source pixels apart
     } else {
-        const int kind = conv_dgrad_kind(d);
-        if (kind == DGRAD_KIND_S2) {
+        if (f.form == DGRAD_S2) {                  // k_dgrad_s2: s2_tap's order, chunk by chunk
             p.kind = WK_DGRAD_S2;
             k.Hs = d->Ho; k.Ws = d->Wo; k.Ho = d->Ho; k.Wo = d->Wo; k.S = 1; k.dil = 0;
-        } else if (kind == DGRAD_KIND_DILATED_TILE) {
+        } else if (tile32 && f.dilated) {          // the same k_conv3x3 order over the zero-dilated dy
             p.kind = WK_CONV;
             k.Hs = d->Ho; k.Ws = d->Wo; k.Ho = d->Hi; k.Wo = d->Wi; k.S = 1; k.dil = 1;
         } else {
@@ -292,10 +278,7 @@ bool pose_tail_plan(const ColvoConvDesc* d, int direction, PoseTailPlan& p) {
 
 template <int NCH, int KIND>
 int launch_wholek(const PoseTailPlan& p, hipStream_t s, const char* who) {
-    if (int e = allow_dynamic_lds<k_conv_wholek<NCH, KIND>>((size_t)p.lds, 160 * 1024, who)) return e;
-    colvo::launch(k_conv_wholek<NCH, KIND>, dim3((unsigned)p.nwg), dim3(WK_NT), (unsigned)p.lds, s, p.k);
-    COLVO_CHECK_LAUNCH("k_conv_wholek");
-    return 0;
+    return launch_resident<k_conv_wholek<NCH, KIND>>((unsigned)p.nwg, WK_NT, p.lds, s, who, "k_conv_wholek", p.k);
 }
 
 int launch_pose_tail(const PoseTailPlan& p, hipStream_t s, const char* who) {

@@ -174,6 +174,65 @@ def test_forward_is_exact_on_exact_data(B, H, W):
             assert torch.equal(ref, y)
 
 
+# The mask decision every bf16 input gradient shares (csrc/conv_lane.h relu_mask_keep): the producer's value is > 0, read off its
+# bits.  Real activations are >= 0, so the tests above never show the kernels a set sign bit, a denormal or a NaN.
+MASK_PATTERNS = (0x0000, 0x8000, 0x0001, 0x8001, 0x3F80, 0xBF80, 0x7FC0, 0xFFC0)      # +0, -0, +-denormal, +-1, +-NaN
+
+
+def _mask_case(name):
+    """(descriptor, whole-K request, the form counters one plain launch moves or the whole-K kernel kind) at the smallest shape
+    where the form is selected."""
+    bf = torch.bfloat16
+    if name == "k_conv3x3":                     # one tile, one 32-channel chunk
+        return ops.conv_desc(bf, 1, 8, 8, 32, 32), False, ({"conv_tile": 1},)
+    if name == "k_dgrad_s2":
+        return ops.conv_desc(bf, 1, 8, 8, 32, 32, stride=2), False, ({"dgrad_s2": 1},)
+    if name == "k_conv_rt":                     # 16 x 16 tiles x 64 channels x 4 images = rt_min_wgs workgroups, two chunks
+        assert _lib.tune_get("rt_min_wgs") == 1024 and _lib.tune_get("rt_min_chunks") == 2
+        return ops.conv_desc(bf, 4, 256, 256, 64, 64), False, ({"conv_rt": 1},)
+    t = _descs(*SHAPES[0])                      # conv5: 2 x 2 -> 1 x 1, k_dgrad_s2's order; conv6: 1 x 1 -> 1 x 1, k_conv3x3's
+    return (t[0], True, 1) if name == "k_conv_wholek dgrad_s2" else (t[1], True, 0)
+
+
+@pytest.mark.parametrize("name", ["k_conv3x3", "k_dgrad_s2", "k_conv_rt", "k_conv_wholek conv", "k_conv_wholek dgrad_s2"])
+def test_the_relu_mask_keeps_exactly_the_positive_bit_patterns(name):
+    """One input gradient with a mask that cycles through MASK_PATTERNS and one without a mask: the masked result has the unmasked
+    bits where the mask's pattern has the sign clear and a non-zero magnitude (numpy, from the mask's uint16 view) and +0 elsewhere."""
+    import numpy as np
+    d, whole_k, form = _mask_case(name)
+    g = torch.Generator(device=dev()).manual_seed(len(name))
+    dy = torch.randn(d.B, d.Ho, d.Wo, d.Cout, generator=g, device=dev()).to(torch.bfloat16)
+    _, w_bwd = _pack(torch.randn(d.Cout, 9, d.C0, generator=g, device=dev()) * 0.1)
+    n = d.B * d.Hi * d.Wi * d.C0
+    flat = np.arange(n, dtype=np.int64)
+    pat = np.array(MASK_PATTERNS, dtype=np.uint16)[(flat + flat // d.C0) % len(MASK_PATTERNS)]     # shifts by one from pixel to pixel
+    mask = torch.from_numpy(pat.view(np.int16)).to(dev()).view(torch.bfloat16).view(d.B, d.Hi, d.Wi, d.C0)
+    if whole_k:
+        plan = ops.pose_tail_plan(d, 1)
+        assert plan is not None and plan[3] == form, plan
+    out = []
+    for m in (None, mask):
+        dx = torch.full((d.B, d.Hi, d.Wi, d.C0), SENTINEL, device=dev(), dtype=torch.bfloat16)
+        before = _lib.form_counts()
+        ops.conv_dgrad(d, 0, dy, w_bwd, m, dx, False, whole_k=whole_k)
+        torch.cuda.synchronize()
+        diff = X.forms_diff(before, _lib.form_counts())
+        assert (diff == {}) if whole_k else (diff in form), diff
+        out.append(dx.view(torch.int16).cpu().numpy().view(np.uint16).reshape(-1))
+    plain, masked = out
+    u = mask.view(torch.int16).cpu().numpy().view(np.uint16).reshape(-1)
+    keep = ((u & 0x8000) == 0) & ((u & 0x7FFF) != 0)
+    assert np.unique(u).tolist() == sorted(MASK_PATTERNS) and 0 < keep.sum() < n
+    sentinel = np.uint16(torch.tensor(SENTINEL, dtype=torch.bfloat16).view(torch.int16).item() & 0xFFFF)
+    assert not (plain == sentinel).any() and not (masked == sentinel).any()
+    for p in MASK_PATTERNS:                     # every pattern decides over some non-zero gradients
+        assert ((plain[u == p] & 0x7FFF) != 0).any(), hex(p)
+    want = np.where(keep, plain, np.uint16(0))
+    bad = np.flatnonzero(masked != want)
+    assert bad.size == 0, f"{name}: {bad.size} of {n} elements; first at {bad[0]}: mask {u[bad[0]]:#06x}, unmasked " \
+                          f"{plain[bad[0]]:#06x}, masked {masked[bad[0]]:#06x}"
+
+
 def _pose_step(pn, batch, seed):
     """One PoseNet forward + backward with fixed output gradients -> (outputs, depth gradients, the whole gradient arena)."""
     g = torch.Generator(device=dev()).manual_seed(seed)
