@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("COLVO_LIB_PATH") or os.path.join(_HERE, "lib", "libcolvo.so")
 
 F32, BF16 = 0, 1
-ABI_VERSION = 27
+ABI_VERSION = 28
 
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 
@@ -83,6 +83,7 @@ SIGNATURES = {
     "colvo_conv_fwd": (_i, [C.POINTER(ConvDesc)] + [_vp] * 6),
     "colvo_pose_front_plan": (_i, [C.POINTER(ConvDesc), _i, C.POINTER(C.c_int32)]),
     "colvo_pose_tail_plan": (_i, [C.POINTER(ConvDesc), _i, C.POINTER(C.c_int32)]),
+    "colvo_stem_plan": (_i, [C.POINTER(ConvDesc), C.POINTER(C.c_int32)]),
     "colvo_conv_dgrad": (_i, [C.POINTER(ConvDesc), _i, _vp, _vp, _vp, _vp, _i, _vp]),
     "colvo_conv_dgrad_both": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "colvo_conv_dgrad_planes": (_i, [C.POINTER(ConvDesc), _vp, _vp, _i, _i, _vp, _i, _vp]),

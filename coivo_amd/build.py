@@ -30,7 +30,7 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-
 FILE_FLAGS = {"conv.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "bwd16.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
               "fwd16.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "conv_rt.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
               "wgrad_rt.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "pose_front.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
-              "pose_tail.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
+              "pose_tail.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "stem.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
 
 
 def _deps():

@@ -158,6 +158,10 @@ int pose_front_bwd(const ColvoCmd& c, hipStream_t stream);
 int pose_tail_fwd(const ColvoCmd& c, hipStream_t stream);
 int pose_tail_dgrad(const ColvoCmd& c, hipStream_t stream);
 
+// csrc/stem.hip: COLVO_CMD_PACK_STEM_POSE with enc1a's weights in p[3] -- the packing pass, enc1a and enc1b of DepthNet's stem in one
+// launch (colvo_stem_plan)
+int stem_fused(const ColvoCmd& c, hipStream_t stream);
+
 __device__ __forceinline__ float uniform_f(float v) {
     return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)));
 }

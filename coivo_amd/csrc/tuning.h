@@ -130,6 +130,17 @@ namespace tune {
     X(pose_tail_images, 0, "... images per workgroup (0: the fewest at which the grid is at most 256 workgroups, as many as fit beyond; "          \
                            "tests force fragments that span images with it).  Alone at 8 pairs 1 image is the fastest or level on every "         \
                            "launch: conv6's input gradient 5.6 / 5.6 / 5.5 / 6.8 us at 1 / 2 / 4 / 8 images, conv7's 5.5 / 5.7 / 5.8 / 7.2")       \
+    X(stem_fused, 1, "DepthNet's stem -- the pair batch's packing pass, enc1a (8 -> 32, stride 2) and enc1b (32 -> 32), bf16 -- as ONE launch "  \
+                     "(k_stem, csrc/stem.hip: a persistent workgroup walks enc1b's tiles, both weight slabs resident in LDS, the packed "        \
+                     "input and enc1a's output are not read back from memory); same bits.  Reached only by explicit request in "               \
+                     "CMD_PACK_STEM_POSE where colvo_stem_plan selects the shape.  8 pairs of 256x320: the three launches 11.1 + 12.0 + 10.5 "  \
+                     "us -> 27.5; step in ms, three alternating rounds: parent 1.3150-1.3350, this switch off 1.3105-1.3258, on "               \
+                     "1.2898-1.3039 (profiles/stem_ab.md)")                                                                                     \
+    X(stem_max_pairs, 65535, "... batch ceiling: selected up to this many frame pairs.  No ceiling was found: configs[3] (32 pairs) and "     \
+                             "configs[2] (32 pairs of 512x640) are faster with it in every round too (profiles/stem_ab.md)")                  \
+    X(stem_max_wgs, 768, "... its grid: one workgroup per resident slot, at most this many (three per CU: 50 KB of LDS each at the 8 x 16 "    \
+                         "tile).  512 (two per CU) measured level in the step, 1.2925-1.2979; the tests lower it so that a small shape "     \
+                         "takes a second round")                                                                                           \
     X(fwd16, 1, "the 16 -> 16 full-resolution layer and the depth head behind it in one pass (k_fwd16_head, csrc/fwd16.hip)")          \
     X(fwd16_wgs, 1024, "... its grid (at least; one workgroup per 8 tiles beyond that)")                                              \
     X(fwd16_tiles_per_wg, 32, "... tiles per workgroup beyond fwd16_wgs (grid in whole rounds of 1024)")                                       \

@@ -217,7 +217,10 @@ class DepthNet(_ArenaModule):
         fuse_top = ops.conv_head_fused_ok(P["iconv1"]) and _lib.dev_env("COLVO_NO_FWD16") is None
         pose_fill = (pair and fuse_top and B % 2 == 0 and not torch.is_inference_mode_enabled()      # (its tag reads version counters)
                      and _lib.dev_env("COLVO_NO_POSE_FILL") is None)
-        inst = self._acquire((B, H, W, self.compute_dtype, pose_fill))
+        # the packing pass, enc1a and enc1b as one launch (csrc/stem.hip) where the planner selects the shape: its answer follows the
+        # tuning table (`stem_fused`), so it is asked per call and is part of the recorded pass's key
+        stem = pose_fill and ops.stem_plan(P["enc1a"]) is not None
+        inst = self._acquire((B, H, W, self.compute_dtype, pose_fill, stem))
 
         def body():
             A: Dict[str, torch.Tensor] = {}
@@ -225,11 +228,22 @@ class DepthNet(_ArenaModule):
                 x = torch.empty(B, H, W, 8, device=img.device, dtype=self.compute_dtype)
                 # (the two depth channels of every pixel are written by the head below, the six rgb channels here)
                 A["pose_in"] = torch.empty(B // 2, H, W, 8, device=img.device, dtype=self.compute_dtype)
-                ops.pack_stem_pose(img, x, A["pose_in"])
+                if stem:
+                    # all four tensors are written, the bits are the three launches'
+                    La, Lb, Pa = self.enc1a, self.enc1b, P["enc1a"]
+                    for name in ("enc1a", "enc1b"):
+                        A[name] = torch.empty(B, Pa.Ho, Pa.Wo, Pa.Cout, device=img.device, dtype=self.compute_dtype)
+                    ops.stem_fused(Pa, img, x, A["pose_in"], La.w_fwd, La.bias.data, A["enc1a"], Lb.w_fwd, Lb.bias.data, A["enc1b"])
+                else:
+                    ops.pack_stem_pose(img, x, A["pose_in"])
             else:
                 x = ops.pack_nchw([img], 8, self.compute_dtype)
             A["in"] = x
+            if stem:
+                x = A["enc1b"]
             for name, _, _, _, srcs in DEPTH_LAYERS[:-1]:
+                if stem and name in ("enc1a", "enc1b"):
+                    continue
                 if name == "iconv1" and fuse_top:
                     # the narrow full-resolution layer and the depth head in one pass: its 42 MB output is written, not read back
                     L = self.iconv1

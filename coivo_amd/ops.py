@@ -132,6 +132,23 @@ def pack_stem_pose(frames, stem, pose_in) -> None:
     _issue(_lib.CMD_PACK_STEM_POSE, None, (frames, stem, pose_in), (B2, H, W))
 
 
+def stem_plan(d: ConvDesc) -> Optional[Tuple[int, int, int, int]]:
+    """(workgroups, tile rows, tile columns, LDS bytes) of the one launch that replaces the pair batch's packing pass, enc1a (d: its
+    descriptor) and enc1b, or None where it is not selected (include/colvo.h colvo_stem_plan; no GPU needed)."""
+    out = (C.c_int32 * 4)()
+    if not _lib.load().colvo_stem_plan(C.byref(d), out):
+        return None
+    return tuple(int(v) for v in out)
+
+
+def stem_fused(d: ConvDesc, frames, stem, pose_in, w1, b1, y1, w2, b2, y2) -> None:
+    """pack_stem_pose with enc1a (w1, b1 -> y1; d its descriptor) and enc1b (w2, b2 -> y2) behind it in the same launch (the stem form
+    of CMD_PACK_STEM_POSE; refused where stem_plan(d) is None)."""
+    _need_cuda(frames, stem, pose_in, w1, b1, y1, w2, b2, y2)
+    B2, _, H, W = frames.shape
+    _issue(_lib.CMD_PACK_STEM_POSE, d, (frames, stem, pose_in, w1, b1, y1, w2, b2, y2), (B2, H, W))
+
+
 def conv_bwd_fused_ok(d: ConvDesc) -> bool:
     return bool(_lib.load().colvo_conv_bwd_fused_ok(C.byref(d)))
 

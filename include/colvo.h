@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define COLVO_ABI_VERSION 27
+#define COLVO_ABI_VERSION 28
 
 typedef void* colvo_stream_t; /* hipStream_t */
 
@@ -245,6 +245,19 @@ int colvo_conv_head_fused(const ColvoConvDesc* d, const void* x, const void* w_f
  * what colvo_pack_nchw writes) AND pose_in [pairs][H][W][8] bf16: rgb channels 0..2 / 3..5, channels 6 / 7 zeroed (the head's pass
  * writes them afterwards). */
 int colvo_pack_stem_pose(const float* frames, int B2, int H, int W, void* stem, void* pose_in, colvo_stream_t stream);
+
+/* DepthNet's stem at small batches in ONE launch (csrc/stem.hip): the packing pass above, enc1a (8 -> 32 channels, 3x3, stride 2) and
+ * enc1b (32 -> 32, stride 1) behind it, bf16 -- the stem form of COLVO_CMD_PACK_STEM_POSE (below).  A persistent workgroup walks
+ * enc1b's output tiles with both weight slabs resident in LDS: the packed input and enc1a's output are written (the backward pass and
+ * PoseNet read them) but not read back.  All four tensors hold the bits of colvo_pack_stem_pose and two colvo_conv_fwd calls.
+ * Plan query, no side effect: reads d -- ENC1A's descriptor, B = 2 * pairs images; enc1b's is derived from it -- and the tuning
+ * table, calls no HIP and counts no form.  Returns 0 when the launch is not selected: tuning entry `stem_fused` off, f32, channel
+ * counts other than 8 -> 32 (-> 32), not stride 2, an odd image count, more than `stem_max_pairs` pairs, H or W odd or below 16, a
+ * tensor of 1 GiB or more, a tile whose frame patch or LDS does not fit, or a shape at which one of the two plain calls would not run
+ * the form the bits are tied to (k_conv3x3 / k_conv3x3_res over one-granule chunks for enc1a, over one 32-channel chunk for enc1b).
+ * Otherwise 1, and out (may be NULL) receives {workgroups, tile rows, tile columns, LDS bytes}.  A request at a shape this query does
+ * not select is an error, never a fall-back. */
+int colvo_stem_plan(const ColvoConvDesc* d, int32_t* out);
 
 /* Input gradient AND weight / bias gradient of a narrow full-resolution layer in ONE pass (csrc/bwd16.hip): bf16, 16 -> 16 channels,
  * stride 1, one directly stored source -- DepthNet's iconv1.  Both backward kernels of such a layer are HBM-bound and read the same
@@ -1149,7 +1162,9 @@ enum {
                                    * (p[9] scratch != NULL: colvo_conv_bwd_fused_det; with p[4] dw == NULL the rows stay in the scratch) */
     COLVO_CMD_HEAD_WGRAD_REDUCE,  /* p: partials dw db; i: rows */
     COLVO_CMD_CONV_HEAD_FUSED,    /* p: x w_fwd bias head_w head_b y depth pose_in; f: min_depth max_depth */
-    COLVO_CMD_PACK_STEM_POSE,     /* p: frames stem pose_in; i: B2 H W */
+    COLVO_CMD_PACK_STEM_POSE,     /* p: frames stem pose_in; i: B2 H W; stem form (p[3] != NULL, colvo_stem_plan): p: frames stem pose_in
+                                   * w1 b1 y1 w2 b2 y2 (enc1a's and enc1b's w_fwd, bias and output; all three tensors and both
+                                   * outputs are written); desc: enc1a's */
     COLVO_CMD_HEAD_WGRAD_MFMA,    /* p: y dpre partials; i: B H W */
     COLVO_CMD_SIDE_SYNC           /* (side command) the side stream in use waits for everything enqueued so far on every other side
                                     stream: what follows reads what several FORKed commands wrote */
