@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("COLVO_LIB_PATH") or os.path.join(_HERE, "lib", "libcolvo.so")
 
 F32, BF16 = 0, 1
-ABI_VERSION = 28
+ABI_VERSION = 29
 
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 
@@ -162,6 +162,9 @@ SIGNATURES = {
     "colvo_mesh_clean_scratch_bytes": (_sz, [_i, _i]),
     "colvo_mesh_clean_plan": (_i, [_vp, _vp, _vp, _i, _i, _i] + [_vp] * 6),
     "colvo_mesh_clean_write": (_i, [_vp] * 5 + [_i, _i, _vp, _vp, _vp, _i, _i] + [_vp] * 6),
+    "colvo_mesh_fill_scratch_bytes": (_sz, [_i, _i, _i]),
+    "colvo_mesh_fill_plan": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _i] + [_vp] * 9),
+    "colvo_mesh_fill_write": (_i, [_vp] * 5 + [_i] * 6 + [_vp] * 13),
     "colvo_refine_workspace_bytes": (_sz, [_i] * 5),
     "colvo_refine_accumulate": (_i, [_vp] * 3 + [_i] * 3 + [_vp, _i] + [_vp] * 3 + [_f] * 4 + [_i, _f] + [_vp] * 4),
     "colvo_refine_edges": (_i, [_vp] * 3 + [_i] * 3 + [_vp, _i, _vp, _i] + [_f] * 4 + [C.c_double, _i, _i, _f] + [_vp] * 7),

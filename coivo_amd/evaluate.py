@@ -82,7 +82,7 @@ import torch
 
 from . import _lib
 from . import inference
-from ._args import f32 as _f32
+from ._args import f32 as _f32, int_range
 from .fusion import Mesh, Meshing
 from .topology import _mesh_arrays, clean_mesh, mesh_topology
 
@@ -763,7 +763,7 @@ def surface_reconstruction_metrics(pred_mesh: Mesh, pred_cam2world, gt_depths: t
     """A reconstructed surface against ground truth, point to surface: pred_mesh (reconstruct_sequence's `mesh`) in the frame of the
     trajectory pred_cam2world [N,4,4], against the mesh that fuse_tsdf + extract_mesh give from gt_depths [N,1,H,W] along gt_cam2world
     [N,4,4] at the same voxel_size under the pred side's policy `meshing` (trunc, min_obs; with min_faces > 0 the ground-truth mesh is
-    cleaned the same way).  pred is moved by align_trajectory(pred_cam2world, gt_cam2world, align) and the two are compared by
+    cleaned the same way, with fill_edges >= 3 its small holes are filled the same way).  pred is moved by align_trajectory(pred_cam2world, gt_cam2world, align) and the two are compared by
     surface_metrics.  max_dist defaults to 4 * voxel_size and thresholds to (voxel_size, 2 * voxel_size), as in
     reconstruction_metrics: choices, not tuned."""
     who = "surface_reconstruction_metrics"
@@ -771,6 +771,8 @@ def surface_reconstruction_metrics(pred_mesh: Mesh, pred_cam2world, gt_depths: t
         raise ValueError(f"{who}: pred_mesh must be a Mesh")
     if not isinstance(meshing, Meshing):
         raise ValueError(f"{who}: meshing must be a Meshing")
+    if not (type(meshing.fill_edges) is int and meshing.fill_edges == 0):      # (before the fusion runs)
+        int_range(who, "meshing.fill_edges (or 0: no filling)", meshing.fill_edges, 3)
     G = _poses(gt_cam2world, "gt_cam2world")
     G32 = G.to(gt_depths.device, torch.float32)
     volume = inference.fuse_tsdf(gt_depths, K, G32, voxel_size=voxel_size, trunc=meshing.trunc, colors=gt_colors, stride=stride,
@@ -778,6 +780,8 @@ def surface_reconstruction_metrics(pred_mesh: Mesh, pred_cam2world, gt_depths: t
     gt = inference.extract_mesh(volume, min_obs=meshing.min_obs)
     if meshing.min_faces > 0:
         gt = clean_mesh(gt, mesh_topology(gt, unit=voxel_size), min_faces=meshing.min_faces).mesh
+    if meshing.fill_edges != 0:
+        gt = inference.fill_holes(gt, mesh_topology(gt, unit=voxel_size), max_edges=meshing.fill_edges).mesh
     R, t, s = align_trajectory(pred_cam2world, G, align)
     vs = _f32(voxel_size)
     return surface_metrics(pred_mesh, gt, max_dist=4.0 * vs if max_dist is None else max_dist,

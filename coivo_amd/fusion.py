@@ -139,20 +139,25 @@ class Meshing(_MeshingFields):
     """reconstruct_sequence's meshing policy: fuse_tsdf's trunc and extract_mesh's min_obs.  The defaults are choices, not tuned
     values.  Behind the two fields -- it still unpacks into two and equals the pair -- a third, `min_faces` (positional or by
     keyword; 0, a choice: the mesh is left as extracted): with min_faces > 0 the components with fewer faces, and every vertex no
-    face uses, are removed (coivo_amd.topology.clean_mesh)."""
+    face uses, are removed (coivo_amd.topology.clean_mesh); and a fourth, `fill_edges` (likewise; 0, a choice: the holes stay open):
+    with fill_edges >= 3 the simple boundary rings of at most that many edges are then closed (coivo_amd.holes.fill_holes)."""
     min_faces = 0
+    fill_edges = 0
 
-    def __new__(cls, trunc=None, min_obs=2, min_faces=0):
+    def __new__(cls, trunc=None, min_obs=2, min_faces=0, fill_edges=0):
         self = super().__new__(cls, trunc, min_obs)
         self.min_faces = min_faces
+        self.fill_edges = fill_edges
         return self
 
     def _replace(self, **kw):
         min_faces = kw.pop("min_faces", self.min_faces)
-        return type(self)(*super()._replace(**kw), min_faces=min_faces)
+        fill_edges = kw.pop("fill_edges", self.fill_edges)
+        return type(self)(*super()._replace(**kw), min_faces=min_faces, fill_edges=fill_edges)
 
     def __repr__(self):
-        return f"Meshing(trunc={self.trunc!r}, min_obs={self.min_obs!r}, min_faces={self.min_faces!r})"
+        return (f"Meshing(trunc={self.trunc!r}, min_obs={self.min_obs!r}, min_faces={self.min_faces!r}, "
+                f"fill_edges={self.fill_edges!r})")
 
 
 def tsdf_voxels(who: str, voxel_size, trunc):

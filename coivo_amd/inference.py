@@ -9,7 +9,8 @@ stitch_point_cloud (oracle/SPEC.md §6c).  The per-pixel work runs in csrc/recon
 products of 4x4 matrices and is done on the host in float64 (it is control flow, not a kernel).  The fusion runs in
 csrc/fuse.hip.  render_cloud / render_fused draw a cloud back into camera views (csrc/render.hip).
   mesh_topology / clean_mesh say what the extracted surface is -- components, boundary loops, areas -- and remove its debris (DESIGN.md
-§3.6o, csrc/topology.hip).  The entry points of fusion, consistency, refine, render, topology and ply are re-exported here.
+§3.6o, csrc/topology.hip); fill_holes closes its small holes and measures every hole (csrc/fill.hip).  The entry points of
+fusion, consistency, refine, render, topology, holes and ply are re-exported here.
 """
 from __future__ import annotations
 
@@ -21,6 +22,7 @@ import torch
 from . import _lib, localize
 from ._args import MAX_DEPTH, depth_views, f32 as _f32, int_range, per_view_K      # (_f32: tools and tests round a voxel size with it)
 from .consistency import Consistency, ConsistencyResult, check_consistency, filter_depths
+from .holes import HoleFill, fill_holes
 from .fusion import (CloudNormals, FusedCloud, Mesh, Meshing, TsdfVolume, cloud_normals, extract_mesh, fuse_point_cloud, fuse_tsdf,
                      fusion_grid, tsdf_voxels)
 from .ply import write_ply
@@ -104,7 +106,8 @@ class Reconstruction(_ReconstructionFields):
     RenderedViews of `fused` in every frame's own camera along `cam2world`, else None; and `normals`: with Render(surfels=True) the
     CloudNormals of `fused` (`rendered` is then the SurfelViews drawn with them), else None; and `mesh`: with a Meshing policy the
     Mesh extracted from the TSDF volume of the same depths and trajectory, else None (with Render(mesh=True) `rendered` is the
-    MeshViews of that mesh); and `topology`: with a Meshing policy the MeshTopology of `mesh` (unit = the voxel size), else None."""
+    MeshViews of that mesh); and `topology`: with a Meshing policy the MeshTopology of `mesh` (unit = the voxel size), else None; and `holes`: with Meshing(fill_edges >= 3) the
+    HoleFill whose mesh `mesh` is, else None."""
     polyps = None               # Optional[PolypLocalization]
     consistency = None          # Optional[ConsistencyResult]
     refinement = None           # Optional[RefinementResult]
@@ -112,9 +115,10 @@ class Reconstruction(_ReconstructionFields):
     normals = None              # Optional[CloudNormals]
     mesh = None                 # Optional[Mesh]
     topology = None             # Optional[MeshTopology]
+    holes = None                # Optional[HoleFill]
 
     def __new__(cls, depths, rel_poses, cam2world, points, fused=None, polyps=None, consistency=None, refinement=None,
-                rendered=None, normals=None, mesh=None, topology=None):
+                rendered=None, normals=None, mesh=None, topology=None, holes=None):
         self = super().__new__(cls, depths, rel_poses, cam2world, points, fused)
         self.polyps = polyps
         self.consistency = consistency
@@ -123,6 +127,7 @@ class Reconstruction(_ReconstructionFields):
         self.normals = normals
         self.mesh = mesh
         self.topology = topology
+        self.holes = holes
         return self
 
     def _replace(self, **kw):
@@ -133,8 +138,9 @@ class Reconstruction(_ReconstructionFields):
         normals = kw.pop("normals", self.normals)
         mesh = kw.pop("mesh", self.mesh)
         topology = kw.pop("topology", self.topology)
+        holes = kw.pop("holes", self.holes)
         return type(self)(*super()._replace(**kw), polyps=polyps, consistency=consistency, refinement=refinement, rendered=rendered,
-                          normals=normals, mesh=mesh, topology=topology)
+                          normals=normals, mesh=mesh, topology=topology, holes=holes)
 
 
 @torch.no_grad()
@@ -180,7 +186,10 @@ def reconstruct_sequence(depth_net, pose_net, frames: torch.Tensor, K: torch.Ten
     max_depth and image size, culling off): `rendered` is then a MeshViews and `normals` stays None.  With a Meshing policy the
     topology of the mesh is computed as well (mesh_topology, unit = voxel_size; `topology`, else None); with policy.min_faces > 0 the
     components with fewer faces -- and every vertex no face uses -- are first removed (clean_mesh) and the topology is that of the
-    cleaned mesh, which is then `mesh` and what Render(mesh=True) draws; with min_faces = 0 `mesh` is extract_mesh's, bit for bit."""
+    cleaned mesh, which is then `mesh` and what Render(mesh=True) draws; with min_faces = 0 `mesh` is extract_mesh's, bit for bit.  With
+    policy.fill_edges >= 3 the simple boundary rings of at most that many edges are then closed (fill_holes, after the cleaning): the
+    HoleFill is `holes` (else None), its mesh is `mesh` and what Render(mesh=True) draws, and `topology` is recomputed on it; with
+    fill_edges = 0 (a choice, not a tuned value) every output is as without the field.  1 and 2 are refused."""
     who = "reconstruct_sequence"
     n = frames.shape[0]
     if n < 2:
@@ -206,12 +215,14 @@ def reconstruct_sequence(depth_net, pose_net, frames: torch.Tensor, K: torch.Ten
         if render.mesh and mesh is None:
             raise ValueError(f"{who}: Render(mesh=True) needs a Meshing policy (mesh=Meshing()): it draws the extracted mesh")
     if mesh is not None:
-        mesh = Meshing(*mesh, min_faces=mesh.min_faces) if isinstance(mesh, Meshing) else Meshing(*mesh)      # (a plain tuple may hold two or three)
+        mesh = Meshing(*mesh, min_faces=mesh.min_faces, fill_edges=mesh.fill_edges) if isinstance(mesh, Meshing) else Meshing(*mesh)      # (a plain tuple may hold two to four)
         if voxel_size is None:
             raise ValueError(f"{who}: mesh needs voxel_size (the TSDF volume's voxels)")
         tsdf_voxels(who, voxel_size, mesh.trunc)
         int_range(who, "mesh.min_obs", mesh.min_obs, 1)
         int_range(who, "mesh.min_faces", mesh.min_faces, 0)
+        if not (type(mesh.fill_edges) is int and mesh.fill_edges == 0):
+            int_range(who, "mesh.fill_edges (or 0: no filling)", mesh.fill_edges, 3)
     K = per_view_K(K, n).to(frames.device, torch.float32).contiguous()
     depths, rel = run_networks(depth_net, pose_net, frames, chunk=chunk)
     traj = integrate_trajectory(rel)
@@ -238,7 +249,7 @@ def reconstruct_sequence(depth_net, pose_net, frames: torch.Tensor, K: torch.Ten
             normals = cloud_normals(fused, depths, K, traj32, stride=stride, max_depth=max_depth)
         rendered = render_fused(fused, K, traj32, int(frames.shape[2]), int(frames.shape[3]), radius=render.radius,
                                 max_splat=render.max_splat, max_depth=max_depth, normals=normals)
-    surface = topology = None
+    surface = topology = holes = None
     if mesh is not None:
         volume = fuse_tsdf(depths, K, traj32, voxel_size=voxel_size, trunc=mesh.trunc, colors=frames.to(torch.float32).contiguous(),
                            stride=stride, max_depth=max_depth)
@@ -247,6 +258,10 @@ def reconstruct_sequence(depth_net, pose_net, frames: torch.Tensor, K: torch.Ten
         if mesh.min_faces > 0:
             surface = clean_mesh(surface, topology, min_faces=mesh.min_faces).mesh
             topology = mesh_topology(surface, unit=voxel_size)
+        if mesh.fill_edges != 0:
+            holes = fill_holes(surface, topology, max_edges=mesh.fill_edges)
+            surface = holes.mesh
+            topology = mesh_topology(surface, unit=voxel_size)
         if render is not None and render.mesh:
             rendered = render_mesh(surface, K, traj32, int(frames.shape[2]), int(frames.shape[3]), max_depth=max_depth)
-    return Reconstruction(raw, rel, traj, cloud, fused, polyps, checked, refined, rendered, normals, surface, topology)
+    return Reconstruction(raw, rel, traj, cloud, fused, polyps, checked, refined, rendered, normals, surface, topology, holes)

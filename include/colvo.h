@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define COLVO_ABI_VERSION 28
+#define COLVO_ABI_VERSION 29
 
 typedef void* colvo_stream_t; /* hipStream_t */
 
@@ -856,6 +856,63 @@ int colvo_mesh_clean_write(const float* vertices, const float* colors, const flo
                            const int32_t* faces, int V, int F, const int32_t* vertex_map, const int32_t* vertex_index,
                            const int32_t* face_index, int V2, int F2, float* out_vertices, float* out_colors, float* out_normals,
                            int32_t* out_cells, int32_t* out_faces, colvo_stream_t stream);
+
+/* Hole filling: the boundary loops of a mesh as ordered rings, the area each hole spans, and the mesh with the short rings closed by a
+ * fan to the ring's mean (csrc/fill.hip; replica tests/fill_ref.py, which every output equals bit for bit).  Inputs:
+ * the mesh of colvo_mesh_topology_* (liveness, edges, multiplicity and loops as defined there), that call's vertex_loop [V] and loops
+ * [L][4], its `unit`, and the policy max_edges >= 3.
+ * Definitions.  A live face (a, b, c) has the directed sides a->b, b->c, c->a.  A side is a BOUNDARY HALF-EDGE iff its unordered edge
+ *   has multiplicity 1.  out[v] / in[v] count the boundary half-edges that leave / enter v; succ(v) is the end of the one that leaves v
+ *   where out[v] = 1.  A loop is SIMPLE iff every one of its vertices has out = in = 1: its n = loops[l][2] >= 3 half-edges then form one
+ *   directed cycle through all its vertices.  Rings that touch in a vertex, borders that run into non-manifold vertices and
+ *   inconsistently wound neighbours are not simple.  The RING of a simple loop: ring[0] = loops[l][0] (its smallest vertex), ring[k+1]
+ *   = succ(ring[k]).
+ * Centre of a simple loop, float64 in the order written (no FMA contraction), q = (double)unit * 2^-16: per ring vertex and coordinate
+ *   t = (double)x / q; the loop is UNMEASURED if any t is NaN or |t| >= 2^32; else S = sum of llrint(t) (int64, ties to even) and the
+ *   centre's coordinate is (float)(((double)S / (double)n) * q).  Colours (if given) likewise with q = 2^-16; a colour whose t is NaN or
+ *   |t| >= 2^32 adds 0 and marks nothing.
+ * Fan.  n > 3: ring edge k gives the face (ring[(k+1) mod n], ring[k], c), c the centre's vertex: it holds the reversed half-edge, so
+ *   it is wound like its neighbour across the border.  n = 3: the single face (ring[0], ring[2], ring[1]), no new vertex.
+ * Hole area: the sum over the fan's faces (i, j, k) of colvo_mesh_topology_*'s face quanta -- a = p_j - p_i, b = p_k - p_i, n = a x b, s
+ *   = (n_x n_x + n_y n_y) + n_z n_z, llrint((0.5 * sqrt(s)) / qa) -- with the stored float32 centre widened to double.  A face whose
+ *   quotient is NaN or >= 2^62 makes the loop UNMEASURED.  It is computed for every simple loop, filled or not.
+ * Centre normal: per fan face the three components 0.5 * n_x, 0.5 * n_y, 0.5 * n_z, each llrint(. / qa) under |t| < 2^62, each summed
+ *   as int64 (no second UNMEASURED criterion: |0.5 n_x| <= 0.5 sqrt(s) and a NaN component makes s NaN, so a component fails only on a
+ *   face whose area already failed, and such a loop gets no vertex) to (X, Y, Z); len = sqrt((X X + Y Y) + Z Z) in float64; the normal is
+ *   ((float)(X / len), (float)(Y / len), (float)(Z / len)), or (0, 0, 0) where len is 0.
+ * status [L] int32, the first that applies: 2 NOT_SIMPLE, 3 UNMEASURED, 1 TOO_LONG (n > max_edges), 0 FILLED.
+ * Two calls on one stream with one scratch of colvo_mesh_fill_scratch_bytes(V, F, L) bytes (16-byte aligned) that carries state from
+ * the first to the second.
+ *   plan   status [L]; hole [L][2] int64: the fan faces the write call appends (n, or 1 for n = 3, for a FILLED loop, else 0) and the
+ *          hole area in quanta (0 for a NOT_SIMPLE or UNMEASURED loop); ring_offsets [L+1] int32 and ring_vertices [V] int32 (the
+ *          first R = ring_offsets[L] entries; the rest 0): the rings of the simple loops in loop order, an empty range for the others;
+ *          counts (device int32[8]): [0] R, [1] new vertices, [2] new faces, [3] the longest simple loop's edges, [4] not zero iff a
+ *          ranking did not end at its ring's last vertex, [5] simple loops, [6] sides of live faces, [7] not zero iff vertex_loop / loops
+ *          are not this mesh's topology.  With [4] or [7] set the outputs are not valid: the caller must raise ([7] is set where a
+ *          loop's edge or vertex count, its loops[l][0] not being the smallest vertex on it, or a half-edge off every loop says so).
+ *          The ring positions come from ceil(log2(counts[3])) rounds of pointer jumping, one launch each, over (next, distance)
+ *          pairs of a list cut at the loop's smallest vertex; the host, which does not know counts[3], launches ceil(log2(min(V,
+ *          3 F))) rounds, and those beyond leave at their first instruction.
+ *   write  out_vertices, out_colors, out_normals [V + new vertices][3] float32, out_cells likewise int32, out_faces [F + new faces][3]
+ *          int32: rows 0 .. V-1 and 0 .. F-1 are the input's bits (dead faces included; colors, normals and cells may each be NULL
+ *          with their output).  New vertices in ascending loop number: centre, centre colour, centre normal, cell (-1, -1, -1);
+ *          new_vertex_loop [new vertices] int32 their loops.  New faces in (loop, k) order; face_loop [F + new faces] int32: -1 for
+ *          the input's faces, else the loop.
+ * Every in-kernel loop has a bound known on entry; no thread waits for another thread's store; every index read from vertex_loop,
+ * loops or the scratch is checked against its buffer before a gather.  Integer sums: identical bits on every call and stream, and
+ * under a permutation of the faces.  One thread per side scans its bucket as in colvo_mesh_topology_edges.
+ * Limits, refused before any HIP call with a message that starts with the entry's name: 1 <= V < 2^30, 1 <= F < 2^29, 1 <= L <= V (the
+ * caller handles V = 0, F = 0 and L = 0 without a call), unit finite and positive, max_edges >= 3, 0 <= R <= V, new
+ * vertices <= L, new faces <= R.  The size function returns 0 for what the calls refuse. */
+size_t colvo_mesh_fill_scratch_bytes(int V, int F, int L);
+int colvo_mesh_fill_plan(const float* vertices, const int32_t* faces, const float* colors, int V, int F, int L, float unit,
+                         int max_edges, const int32_t* vertex_loop, const int64_t* loops, void* scratch, int32_t* status,
+                         int64_t* hole, int32_t* ring_offsets, int32_t* ring_vertices, int32_t* counts, colvo_stream_t stream);
+int colvo_mesh_fill_write(const float* vertices, const float* colors, const float* normals, const int32_t* cells, const int32_t* faces,
+                          int V, int F, int L, int R, int n_new_vertices, int n_new_faces, const void* scratch,
+                          const int32_t* vertex_loop, const int32_t* status, const int32_t* ring_offsets, const int32_t* ring_vertices,
+                          float* out_vertices, float* out_colors, float* out_normals, int32_t* out_cells, int32_t* out_faces,
+                          int32_t* face_loop, int32_t* new_vertex_loop, colvo_stream_t stream);
 
 /* Pose refinement by dense depth and intensity alignment: a few Gauss-Newton steps per edge on the per-pixel geometric
  * and photometric residuals of the two frames it connects, starting from the pose given.  depths [N,1,H,W], frames [N,3,H,W], K [N,3,3]
