@@ -14,6 +14,7 @@ The weight gradient sums B * Ho * Wo products per element: rho is chosen from th
 max|x| * sum_p |dy[p, co]| stays within 2^22 quanta (headroom for the accumulating second call and for the bf16 MFMA, whose exact
 addition of representable partial sums is assumed, not documented).  bound_* state the bounds analytically (tests/test_abi_cpu.py
 checks them for every production descriptor); check_wgrad_bound measures the drawn tensors before anything is compared."""
+import ctypes
 import math
 
 import torch
@@ -236,20 +237,28 @@ def check_layer(lay, dtype, g, dev, fused=True, data=None):
     """Every pass of `lay` in `dtype` on exact data against the float64 reference: forward with ReLU, input gradient of each source
     plain and masked + accumulate, both sources in one launch (concat layers), weight / bias gradient in the atomic, clean-arena,
     deterministic (twice) and slab + grouped-reduction forms, plus the accumulating second call; the fused kernels where their _ok
-    allows them.  Returns {pass: forms counted}.  `data`: operands shared between the dtypes of one layer (made here when None)."""
+    allows them.  Returns {pass: forms counted}.  `data`: operands shared between the dtypes of one layer (made here when None).
+    Every operand is a guarded copy (tests/guarded.py Pool.place) and every destination and scratch comes from the pool, poisoned with
+    0xFF bytes (NaN): an element a kernel leaves unwritten fails the comparison, a load from outside an operand that reaches a sum makes
+    it NaN, and the guards of everything live are checked after each pass."""
     from coivo_amd import _lib, ops
+    from tests import guarded
+    pool = guarded.Pool(dev)
     data = data if data is not None else make_data(lay, g, dev)
     x0f, x1f, wm, bias, dyd_f, dyw_f, hw = (data[k] for k in ("x0", "x1", "w", "bias", "dy_dense", "dy_wgrad", "head_w"))
     desc = ops.conv_desc(dtype, lay.B, lay.Hi, lay.Wi, lay.C0, lay.Cout, stride=lay.stride, relu=True, C1=lay.C1, up0=lay.up0,
                          up1=lay.up1)
     cast = lambda t: None if t is None else t.to(dtype)
-    x0, x1, dyd, dyw = cast(x0f), cast(x1f), cast(dyd_f), cast(dyw_f)
-    w_fwd = torch.empty(lay.Cout, 9, lay.Cin, device=dev, dtype=dtype)
-    w_bwd = torch.empty(lay.Cin, 9, lay.Cout, device=dev, dtype=dtype)
-    ops.pack_weights(wm, dtype, w_fwd, w_bwd)
+    x0, x1, dyd, dyw = (pool.place(cast(t), n) for t, n in ((x0f, "x0"), (x1f, "x1"), (dyd_f, "dy dense"), (dyw_f, "dy wgrad")))
+    wm_g, bias, hw = pool.place(wm, "master weights"), pool.place(bias, "bias"), pool.place(hw, "head weights")
+    w_fwd = pool.empty((lay.Cout, 9, lay.Cin), dtype, label="w_fwd")
+    w_bwd = pool.empty((lay.Cin, 9, lay.Cout), dtype, label="w_bwd")
+    ops.pack_weights(wm_g, dtype, w_fwd, w_bwd)
+    tag = f"{lay.__dict__} {dtype}"
+    pool.check(f"pack_weights {tag}", release=False)
     assert torch.equal(w_fwd.float(), wm)
     forms = {}
-    tag = f"{lay.__dict__} {dtype}"
+    poisoned = lambda like, label: pool.empty(like.shape, like.dtype, label=label)
 
     def run(name, fn):
         torch.cuda.synchronize()
@@ -257,40 +266,46 @@ def check_layer(lay, dtype, g, dev, fused=True, data=None):
         fn()
         torch.cuda.synchronize()
         forms[name] = forms_diff(before, _lib.form_counts())
+        pool.check(f"{name} {tag}", release=False)
 
     # ---- forward ----
-    y = torch.empty(lay.B, lay.Ho, lay.Wo, lay.Cout, device=dev, dtype=dtype)
+    y = pool.empty((lay.B, lay.Ho, lay.Wo, lay.Cout), dtype, label="y")
     run("fwd", lambda: ops.conv_fwd(desc, x0, x1, w_fwd, bias, y))
     yh = None
     if fused and ops.conv_head_fused_ok(desc):
-        yh = torch.full_like(y, 9.0)
-        depth = torch.empty(lay.B, 1, lay.Ho, lay.Wo, device=dev)
-        run("fwd16_head", lambda: ops.conv_head_fused(desc, x0, w_fwd, bias, hw, torch.zeros(1, device=dev), yh, depth))
+        yh = poisoned(y, "conv_head_fused y")
+        depth = pool.empty((lay.B, 1, lay.Ho, lay.Wo), torch.float32, label="conv_head_fused depth")
+        hb = pool.filled((1,), 0.0, label="head bias")
+        run("fwd16_head", lambda: ops.conv_head_fused(desc, x0, w_fwd, bias, hw, hb, yh, depth))
+        assert bool(torch.isfinite(depth).all()), f"conv_head_fused depth {tag}: elements left unwritten"
+        pool.forget(depth, hb)
+        del depth, hb
     for b0, b1 in lay.slices():
         r = _ref(data, ("fwd", b0), lambda: lay.ref_fwd(x0f, x1f, wm, bias, b0, b1))
         expect_exact(y[b0:b1], r, QB, f"fwd {tag} images {b0}..{b1}")
         if yh is not None:
             expect_exact(yh[b0:b1], r, QB, f"conv_head_fused y {tag} images {b0}..{b1}")
+    pool.forget(y, yh)
     del y, yh
 
     # ---- input gradients ----
     srcs = [(0, x0, x0f), (1, x1, x1f)] if lay.C1 else [(0, x0, x0f)]
     outs = {}
     for si, xs, _ in srcs:
-        dx = torch.full_like(xs, 7.0)
+        dx = poisoned(xs, f"dx{si}")
         run(f"dgrad{si}", lambda: ops.conv_dgrad(desc, si, dyd, w_bwd, None, dx, False))
         base = make_base(xs.shape, g, dev).to(dtype)
-        dxm = base.clone()
+        dxm = pool.place(base, f"dx{si} masked + accumulate")
         run(f"dgrad{si}_masked_acc", lambda: ops.conv_dgrad(desc, si, dyd, w_bwd, xs, dxm, True))
         outs[si] = (dx, base, dxm)
     both = None
     if lay.C1:
-        both = (torch.full_like(x0, 5.0), torch.full_like(x1, 5.0))
+        both = (poisoned(x0, "dgrad_both dx0"), poisoned(x1, "dgrad_both dx1"))
         run("dgrad_both", lambda: ops.conv_dgrad_both(desc, dyd, w_bwd, x0, x1, both[0], both[1]))
     planes = None
     if fused and lay.stride == 2 and lay.C0 == 8 and lay.C1 == 0 and lay.Cout == 16:      # PoseNet conv1: the two depth channels
-        planes = torch.full((2, lay.B, 1, lay.Hi, lay.Wi), 7.0, device=dev)
-        run("dgrad_planes", lambda: ops.conv_dgrad_planes(desc, dyd, wm, 6, 2, planes))
+        planes = pool.empty((2, lay.B, 1, lay.Hi, lay.Wi), torch.float32, label="planes")
+        run("dgrad_planes", lambda: ops.conv_dgrad_planes(desc, dyd, wm_g, 6, 2, planes))
     for b0, b1 in lay.slices():
         refs = _ref(data, ("dgrad", b0), lambda: lay.ref_dgrad(dyd_f, wm, b0, b1))
         for si, xs, xsf in srcs:
@@ -303,13 +318,14 @@ def check_layer(lay, dtype, g, dev, fused=True, data=None):
         if planes is not None:
             expect_exact(planes[:, b0:b1, 0], refs[0][..., 6:8].permute(3, 0, 1, 2), QBASE,
                          f"conv_dgrad_planes {tag} images {b0}..{b1}")
+    pool.forget(planes, *(both or ()), *(t for dx, _, dxm in outs.values() for t in (dx, dxm)))
     del outs, both, planes
 
     # ---- weight / bias gradient ----
     check_wgrad_bound([x0f, x1f], dyw_f, tag)
     rdw, rdb = _ref(data, "wgrad", lambda: lay.ref_wgrad(x0f, x1f, dyw_f))
     qw = QX * QDY
-    zeros = lambda: (torch.zeros(lay.Cout, 9, lay.Cin, device=dev), torch.zeros(lay.Cout, device=dev))
+    zeros = lambda: (pool.filled((lay.Cout, 9, lay.Cin), 0.0, label="dw"), pool.filled((lay.Cout,), 0.0, label="db"))
     dw, db = zeros()
     run("wgrad", lambda: ops.conv_wgrad(desc, x0, x1, dyw, dw, db))
     expect_exact(dw, rdw, qw, f"wgrad (atomics) {tag}")
@@ -321,7 +337,11 @@ def check_layer(lay, dtype, g, dev, fused=True, data=None):
     run("wgrad_clean", lambda: ops.conv_wgrad(desc, x0, x1, dyw, dwc, dbc, arena_is_zero=True))
     expect_exact(dwc, rdw, qw, f"wgrad (clean arena) {tag}")
     expect_exact(dbc, rdb, QDY, f"bgrad (clean arena) {tag}")
-    scr = ops.conv_wgrad_scratch(desc, dev)
+    with guarded.guarded_allocations(pool):          # the slabs: colvo_conv_wgrad_scratch_bytes and not a byte more
+        served = len(pool.served)
+        scr = ops.conv_wgrad_scratch(desc, dev)
+    nb = _lib.load().colvo_conv_wgrad_scratch_bytes(ctypes.byref(desc))
+    guarded.assert_served(pool, served, (nb + 3) // 4 * 4, f"conv_wgrad_scratch {tag}")
     dets = []
     for i in range(2):
         dwd, dbd = zeros()
@@ -339,10 +359,11 @@ def check_layer(lay, dtype, g, dev, fused=True, data=None):
         run("wgrad_slabs", grouped)
         expect_exact(dwg, rdw, qw, f"wgrad (slabs + grouped reduction) {tag}")
         expect_exact(dbg, rdb, QDY, f"bgrad (slabs + grouped reduction) {tag}")
+    pool.forget(dw, db, dwc, dbc, scr, *(t for d in dets for t in d))
     del dw, db, dwc, dbc, dets, scr
     if fused and ops.conv_bwd_fused_ok(desc):
         # the 16 -> 16 layer's input and weight gradient in one pass (without the head term), on the sparse dy of the weight gradient
-        dx = torch.full_like(x0, 3.0)
+        dx = poisoned(x0, "conv_bwd_fused dx")
         dwf, dbf = zeros()
         run("bwd16", lambda: ops.conv_bwd_fused(desc, dyw, w_bwd, x0, True, dx, dwf, dbf))
         expect_exact(dwf, rdw, qw, f"conv_bwd_fused dw {tag}")
@@ -350,6 +371,7 @@ def check_layer(lay, dtype, g, dev, fused=True, data=None):
         for b0, b1 in lay.slices():
             r = _ref(data, ("dgrad_sparse", b0), lambda: lay.ref_dgrad(dyw_f, wm, b0, b1)[0]) * (x0f[b0:b1] > 0)
             expect_exact(dx[b0:b1], r, QBASE, f"conv_bwd_fused dx {tag} images {b0}..{b1}")
+    pool.check(f"end {tag}")
     return forms
 
 

@@ -269,3 +269,43 @@ def test_augmented_batches_feed_a_training_step(tmp_path):
         losses.append(loss.item())
     ld.close()
     assert len(losses) == 2 and all(np.isfinite(losses))
+
+
+@pytest.mark.parametrize("h,w,H,W", [(7, 5, 32, 32), (100, 130, 64, 96)])
+def test_memory_discipline(h, w, H, W):
+    """colvo_frames_u8_augment with the source frames and the parameter table between guard bands and the destination from
+    tests/guarded.py's pool, under both poisons: general rows (fractional crop origins, zoom 1.15, a mirrored frame, gamma 1.25 at 100 x 130) held
+    to the float64 reference as in _check_against_reference, and native-scale crops that touch the source's bottom-right corner, exact.
+    No tap may leave the source, every output element must be written, nothing may be written outside the destination.  One launch:
+    the augmenting conversion kernel."""
+    from coivo_amd import _lib, data as D
+    from tests import guarded as G
+    lib = _lib.load()
+    u8 = _frames(h, w)
+    gamma, bar_extra = (1.25, GAMMA_BAR) if (h, w) == (100, 130) else (1.0, 0.0)      # the shapes each bar is stated for above
+    rows = _general_rows(h, w, gamma)
+    cases = [("general", rows)]
+    if h >= H and w >= W:
+        cases.append(("corner crops", [D.FrameAug(oy, ox, H, W, 0, 1.0) for oy, ox in ((0, 0), (h - H, w - W), (7, 3))]))
+    for what, recs in cases:
+        table = D.aug_table(recs, H, W)
+        outs = []
+        for poison in G.POISONS:
+            pool = G.Pool(dev(), poison)
+            src, tab = pool.place(u8.to(dev()), "frames"), pool.place(torch.from_numpy(table).to(dev()), "table")
+            out = pool.empty((N, 3, H, W), torch.float32, label="out")
+            _lib.check(lib.colvo_frames_u8_augment(_lib.ptr(src), N, h, w, H, W, _lib.ptr(tab), _lib.ptr(out), _lib.stream_ptr()), "augment")
+            pool.check(f"colvo_frames_u8_augment {what} {h}x{w} -> {H}x{W}, poison {poison:#04x}")
+            assert torch.equal(src.cpu(), u8) and torch.equal(tab.cpu(), torch.from_numpy(table))
+            outs.append(out)
+        G.assert_same_bits(outs[0], outs[1], what)
+        got = outs[0].cpu()
+        if what == "general":
+            want = R.augment_frames(u8.numpy(), recs, H, W)
+            for i, r in enumerate(recs):
+                err = np.abs(got[i].double().numpy() - want[i]).max(axis=(1, 2))
+                assert (err <= gamma * R.channel_bound(r.A) + bar_extra).all(), (what, i, err)
+        else:
+            for i, r in enumerate(recs):
+                oy, ox = int(r.oy), int(r.ox)
+                assert torch.equal(got[i], u8[i, oy:oy + H, ox:ox + W].permute(2, 0, 1).float() / 255.0), (oy, ox)

@@ -18,9 +18,12 @@ import torch
 from coivo_amd import synth
 from tests import conv_exact as CX
 from tests import head_exact as HX
+from tests import guarded
 from tests.gpu_util import bf16_rounded_state, dev, to_dev
 
 pytestmark = pytest.mark.gpu
+
+_guarded = guarded.fixture(dev)          # every test here allocates from tests/guarded.py's pool; the guards are checked at its end
 
 ROW = 16 * 9 * 16 + 16                    # floats of one workgroup's row: the weight slab and the bias slab
 # (shape, bwd16_wgs, rows): 15 tiles per image of 33x47 -> 30 tiles over 4 workgroups = 8, 8, 8, 6; 64x96 at the production tuning
@@ -97,9 +100,15 @@ def _desc(shape):
 
 
 def _scratch(desc, mode, rows, fill=None):
-    from coivo_amd import ops
+    import ctypes
+    from coivo_amd import _lib, ops
+    pool = guarded.active_pool()
+    served = len(pool.served)
     scr = ops.conv_bwd_fused_scratch(desc, 0 if mode == "dy" else 1, dev())
     assert scr.numel() == rows * ROW, (scr.numel(), rows)
+    # the rows come from the pool, of the size the query gives and not a byte more: a row written past the last one lands in a guard
+    nbytes = _lib.load().colvo_conv_bwd_fused_scratch_bytes(ctypes.byref(desc), 0 if mode == "dy" else 1)
+    guarded.assert_served(pool, served, nbytes, f"conv_bwd_fused_scratch mode {mode}")
     if fill is not None:
         scr.fill_(fill)
     return scr
@@ -107,7 +116,8 @@ def _scratch(desc, mode, rows, fill=None):
 
 def _call(desc, c, dx, dw, db, scratch):
     from coivo_amd import ops
-    ops.conv_bwd_fused(desc, *c["args"], dx, dw, db, *c["head"], scratch=scratch)
+    pool = guarded.active_pool()             # the operands as guarded copies: a load past the end of dy, x, d(pre) or the weights reads NaN
+    ops.conv_bwd_fused(desc, *pool.place_tree(c["args"]), dx, dw, db, *pool.place_tree(c["head"]), scratch=scratch)
 
 
 def _zeros():

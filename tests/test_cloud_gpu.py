@@ -341,3 +341,23 @@ def test_reconstruction_metrics_end_to_end():
                      transform_=(A[0].numpy(), A[1].numpy(), A[2]))
     _assert_metrics(m, want)
     assert 0.0 < m.accuracy < 0.4
+
+
+# ---- memory discipline ------------------------------------------------------------------------------------------------------- #
+def test_memory_discipline():
+    """nearest_neighbors under tests/guarded.py, both directions of the random clouds (3000 and 2500 points, 8000 cells: more than one
+    scan chunk): query and reference between guard bands; the workspace (colvo_cloud_workspace_bytes: the grid, the cell offsets, the
+    sorted points), dist, dist2, nearest and the statistics from the pool under both poisons.  Outputs equal the replica, are the same
+    bytes under either poison, and no guard byte changes.  Launches reached: the bounding box, the cell count, the scan over two
+    chunks, the scatter and the query with three thresholds."""
+    from coivo_amd import _lib, evaluate as E
+    from tests import guarded as G
+    Q, P = _random_clouds()
+    th = (0.02, 0.035, 0.05)
+    for a, b in ((Q, P), (P, Q)):
+        want = R.nearest(a, b, 0.05, th)
+        outs, pools = G.under_both_poisons(dev(), lambda pool: E.nearest_neighbors(pool.place(_t(a)), pool.place(_t(b)), max_dist=0.05,
+                                                                                  thresholds=th), f"nearest_neighbors {len(a)} -> {len(b)}")
+        for got, pool in zip(outs, pools):
+            _assert_equal(got, want, len(a))
+            G.assert_served(pool, 0, _lib.load().colvo_cloud_workspace_bytes(len(a), len(b)), "nearest_neighbors")

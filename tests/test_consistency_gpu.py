@@ -248,3 +248,24 @@ def test_argument_errors_on_the_device():
             I.filter_depths(d, K, M, **bad)
     out = I.filter_depths(d[:, :, ::2][:, :, :, ::2], K, M, max_depth=MAX_DEPTH)        # non-contiguous input: taken as it reads
     assert out.depths.shape == (3, 1, 9, 12)
+
+
+@pytest.mark.parametrize("N,H,W,window,step", [(3, 17, 23, 2, 1), (4, 33, 47, 3, 2)])
+def test_memory_discipline(N, H, W, window, step):
+    """filter_depths under tests/guarded.py: depths, intrinsics and poses between guard bands -- the bilinear taps of a sample that lands
+    on the first or last row of frame 0 or N - 1 border a guard --; the workspace (colvo_consistency_workspace_bytes), the filtered
+    depths, the votes and the statistics from the pool under both poisons.  Outputs equal the replica, are the same bytes under either
+    poison, and no guard byte changes.  Launches reached: the transform set-up and the filter kernel of colvo_consistency_filter, at
+    a frame smaller than one tile row (17 x 23, window * step past the sequence's ends) and at one with several ragged tiles
+    (33 x 47, step 2)."""
+    from coivo_amd import _lib, inference as I
+    from tests import guarded as G
+    d, K, M = _scene(N, H, W)
+    kw = dict(window=window, step=step, rel_tol=REL_TOL, max_depth=MAX_DEPTH)
+    want = R.filter_depths(d, K, M, **kw)
+    assert want["stats"][:, 1].sum() > 0
+    outs, pools = G.under_both_poisons(dev(), lambda pool: I.filter_depths(pool.place(_t(d)), pool.place(_t(K)), pool.place(_t(M)), **kw),
+                                       f"filter_depths {N}x{H}x{W}")
+    for got, pool in zip(outs, pools):
+        _assert_equal(got, want, (N, H, W, window, step))
+        G.assert_served(pool, 0, _lib.load().colvo_consistency_workspace_bytes(N, window), "filter_depths")

@@ -7,9 +7,12 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests import guarded
 from tests.gpu_util import dev
 
 pytestmark = pytest.mark.gpu
+
+_guarded = guarded.fixture(dev, allocates_nothing=("test_every_kernel_form_is_covered",))          # every test here allocates from tests/guarded.py's pool; the guards are checked at its end
 
 
 def _nhwc(t):   # NCHW -> NHWC contiguous
@@ -238,7 +241,7 @@ def test_conv_fwd_dgrad_wgrad(case, dtype, form):
         ops.conv_dgrad(desc, si, dyd, w_bwd, None, dx, False)
         _close_out(_nchw(dx), xr.grad, dtype, f"dgrad src{si}")
         base = torch.randn(xs.shape, generator=g).to(dtype)
-        dx2 = base.to(d).clone()
+        dx2 = guarded.active_pool().place(base.to(d), "accumulate base")
         ops.conv_dgrad(desc, si, dyd, w_bwd, xs, dx2, True)
         ref2 = _nchw(base.float()) + xr.grad * (xr > 0)
         _close_out(_nchw(dx2), ref2, dtype, f"dgrad src{si} masked+accumulate", atol_scale=4e-5)

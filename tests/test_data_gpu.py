@@ -130,3 +130,27 @@ def test_decoder_process_errors_reach_the_caller(tmp_path):
                 pass
     finally:
         ld.close()
+
+
+@pytest.mark.parametrize("h,w,H,W", [(7, 5, 32, 32), (100, 130, 64, 96)])
+def test_memory_discipline(h, w, H, W):
+    """colvo_frames_u8_to_f32 with the source frames between guard bands and the destination from tests/guarded.py's pool, under both
+    poisons.  The bilinear taps of the last row and column of the last frame -- and of a 7 x 5 source stretched to 32 x 32, where every
+    output pixel's taps are clamped somewhere -- must stay inside the source, every output element must be written, and nothing may be
+    written outside the destination.  One launch: the conversion kernel, here with a ragged last block."""
+    from coivo_amd import _lib
+    from oracle import colvo_spec as S
+    from tests import guarded as G
+    lib = _lib.load()
+    g = torch.Generator().manual_seed(h * 7 + W)
+    u8 = torch.randint(0, 256, (3, h, w, 3), generator=g, dtype=torch.uint8)
+    want = S.resize_frames_u8(u8, H, W)
+    outs = []
+    for poison in G.POISONS:
+        pool = G.Pool(dev(), poison)
+        src, out = pool.place(u8.to(dev()), "frames"), pool.empty((3, 3, H, W), torch.float32, label="out")
+        _lib.check(lib.colvo_frames_u8_to_f32(_lib.ptr(src), 3, h, w, H, W, _lib.ptr(out), _lib.stream_ptr()), "frames")
+        pool.check(f"colvo_frames_u8_to_f32 {h}x{w} -> {H}x{W}, poison {poison:#04x}")
+        assert torch.equal(src.cpu(), u8) and (out.cpu() - want).abs().max().item() < PIXEL_TOL
+        outs.append(out)
+    G.assert_same_bits(outs[0], outs[1], "colvo_frames_u8_to_f32")

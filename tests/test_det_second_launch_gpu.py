@@ -8,9 +8,12 @@ bitwise equality, so every comparison here is torch.equal on pre-filled (non-zer
 import pytest
 import torch
 
+from tests import guarded
 from tests.gpu_util import dev
 
 pytestmark = pytest.mark.gpu
+
+_guarded = guarded.fixture(dev)          # every test here allocates from tests/guarded.py's pool; the guards are checked at its end
 
 
 class _tuned:

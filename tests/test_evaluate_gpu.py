@@ -271,3 +271,27 @@ def test_argument_errors():
         E.depth_metrics(t, t, torch.ones(2, 1, 8, 8, device=d))                  # float mask
     with pytest.raises(ValueError):
         E.depth_metrics(t, t, min_depth=5.0, max_depth=1.0)
+
+
+@pytest.mark.parametrize("name", ["ragged", "mask", "one_valid", "ragged_one_empty"])
+def test_memory_discipline(name):
+    """depth_metrics under tests/guarded.py: prediction, ground truth and mask between guard bands; the workspace
+    (colvo_depth_metrics_workspace_bytes: the histogram levels of the exact median and the sums), per_image, scale and n_valid from the
+    pool under both poisons.  Outputs meet the reference as in _check, are the same bytes under either poison, and no guard byte
+    changes.  Launches reached: k_eval_init, the radix passes of both medians and the sums, at a ragged 17 x 23 (one image of it with
+    no valid pixel in the last case), with a mask, and with a single valid pixel per image."""
+    from coivo_amd import _lib, evaluate as E
+    from tests import guarded as G
+    pred, gt, mask = _case(name.split("_one_empty")[0])
+    if name == "ragged_one_empty":
+        gt[1] = 50.0
+    ref = _reference(pred, gt, mask)
+    d = dev()
+    run = lambda pool: E.depth_metrics(pool.place(pred.to(d)), pool.place(gt.to(d)), None if mask is None else pool.place(mask.to(d)))
+    outs, pools = G.under_both_poisons(d, run, f"depth_metrics {name}")
+    N, _, H, W = pred.shape
+    for res, pool in zip(outs, pools):
+        _check(res, ref)
+        G.assert_served(pool, 0, _lib.load().colvo_depth_metrics_workspace_bytes(N, H, W), "depth_metrics")
+    if name == "ragged_one_empty":
+        assert int(outs[0].n_valid[1]) == 0 and torch.isnan(outs[0].per_image[1]).all()

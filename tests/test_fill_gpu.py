@@ -308,3 +308,28 @@ def test_reconstruct_sequence_fills_and_returns_the_holes():
     assert int(rec.rendered.index.max()) < rec.mesh.faces.shape[0]
     drawn = I.render_mesh(rec.mesh, K, rec.cam2world.to(dev(), torch.float32), 64, 96, max_depth=0.5)
     assert torch.equal(rec.rendered.index, drawn.index)
+
+
+# ---- 9. memory discipline -------------------------------------------------------------------------------------------------------------- #
+def test_memory_discipline():
+    """fill_holes under tests/guarded.py: the mesh and its topology between guard bands, the scratch of colvo_mesh_fill_scratch_bytes, the
+    ring tables and the filled mesh from the pool under both poisons.  Outputs equal the replica, are the same bytes under either poison,
+    and no guard byte changes.  Launches reached: the hand meshes with max_edges = 8 run colvo_mesh_fill_plan and colvo_mesh_fill_write
+    with every status (filled with and without a new vertex, too long, not simple), colours and dead faces; 5000 separate squares take
+    the loops, the new vertices and the new faces past one scan chunk of 4096."""
+    from coivo_amd import _lib, inference as I
+    from tests import guarded as G
+    lib = _lib.load()
+    mesh, wt = _hand_mesh()
+    v, f = R.separate_squares(5000)
+    for name, mesh, wt, unit in (("hand meshes", mesh, wt, 0.5), ("5000 squares", R.as_mesh(v, f, seed=8), T.mesh_topology(v, f, 1.0), 1.0)):
+        want = R.fill_holes(mesh, wt, 8)
+        assert int((want["status"] == R.FILLED).sum()) > 0 and len(want["vertices"]) > len(mesh["vertices"])
+        m = _gpu(mesh)
+        topo = I.mesh_topology(m, unit=unit)
+        outs, pools = G.under_both_poisons(dev(), lambda pool: I.fill_holes(pool.place_tree(m), pool.place_tree(topo), max_edges=8),
+                                           f"fill_holes {name}")
+        V, F, L = m.vertices.shape[0], m.faces.shape[0], topo.loops.shape[0]
+        for got, pool in zip(outs, pools):
+            _assert_fill(got, want, name)
+            G.assert_served(pool, 0, lib.colvo_mesh_fill_scratch_bytes(V, F, L), name)

@@ -291,3 +291,31 @@ def test_argument_errors():
                 dict(voxel_size=0.25, origin=(0.0, 0.0, 0.0), dims=(8, 8, 0))):
         with pytest.raises(ValueError):
             I.fuse_point_cloud(d, k, m, **bad)
+
+
+@pytest.mark.parametrize("case", ["3x17x23_colours_min_obs_2", "more_than_256_scan_chunks"])
+def test_memory_discipline(case):
+    """fuse_point_cloud under tests/guarded.py: depths, colours, intrinsics and poses between guard bands; the plan's workspace
+    (colvo_fuse_plan_workspace_bytes), the voxel pool (colvo_fuse_pool_bytes), the extraction workspace
+    (colvo_fuse_extract_workspace_bytes) and every output from the pool under both poisons.  The cloud equals the replica, is the same
+    bytes under either poison, and no guard byte changes.  Launches reached: colvo_fuse_plan, colvo_fuse_accumulate, colvo_fuse_count
+    and colvo_fuse_write, with colours and min_obs = 2 in the first case; the second case's 1024^3 grid is a brick table of 512 scan
+    chunks, where the scan's top-level workgroup takes two chunk sums per thread."""
+    from coivo_amd import _lib, inference as I
+    from tests import guarded as G
+    lib = _lib.load()
+    depths, colors, K, M = _scene(3, 17, 23)
+    if case == "3x17x23_colours_min_obs_2":
+        origin, dims = _default_grid(K, M, 17, 23, 0.25)
+        kw = dict(stride=1, max_depth=MAX_DEPTH, voxel_size=0.25, origin=origin, dims=dims, min_obs=2)
+    else:
+        kw = dict(stride=1, max_depth=MAX_DEPTH, voxel_size=0.0078125, origin=(-4.0, -4.0, -1.0), dims=(1024, 1024, 1024), min_obs=1)
+    want = _ref(depths, colors, K, M, **kw)
+    assert want["n_bricks"] > 0 and 0 < want["points"].shape[0] and (kw["min_obs"] == 1 or want["points"].shape[0] < want["n_voxels"])
+    outs, pools = G.under_both_poisons(dev(), lambda pool: I.fuse_point_cloud(pool.place(_t(depths)), pool.place(_t(K)), pool.place(_t(M)),
+                                                                              colors=pool.place(_t(colors)), **kw), case)
+    for got, pool in zip(outs, pools):
+        _assert_equal(got, want, case)
+        for nbytes in (lib.colvo_fuse_plan_workspace_bytes(3, 17, 23, 1, *kw["dims"]), lib.colvo_fuse_pool_bytes(want["n_bricks"]),
+                       lib.colvo_fuse_extract_workspace_bytes(want["n_bricks"])):
+            G.assert_served(pool, 0, nbytes, case)

@@ -16,9 +16,12 @@ import torch
 
 from tests import conv_exact as CX
 from tests import head_exact as HX
+from tests import guarded
 from tests.gpu_util import dev
 
 pytestmark = pytest.mark.gpu
+
+_guarded = guarded.fixture(dev, allocates_nothing=("test_production_tuning_of_the_head_switches",))          # every test here allocates from tests/guarded.py's pool; the guards are checked at its end
 
 DEPTH_SHAPES = [(16, 256, 320), (64, 256, 320), (128, 256, 320), (64, 512, 640)]
 POSE_SHAPES = [(8, 256, 320), (32, 256, 320), (64, 256, 320), (32, 512, 640)]
@@ -29,6 +32,8 @@ PRODUCTION = {"head_fwd_lds": 1, "head_dgrad_generic": 0, "head_wgrad_rows": 1, 
 
 def _free():
     gc.collect()
+    if guarded._ACTIVE:                      # check the guards of everything allocated so far and let go of what the test has dropped
+        guarded.active_pool().check("before freeing", release=False)
     torch.cuda.synchronize()
     torch.cuda.empty_cache()
 
@@ -77,6 +82,11 @@ def test_production_tuning_of_the_head_switches():
 # --------------------------------------------------------------------------------------------------------------------------- #
 # depth head forward                                                                                                           #
 # --------------------------------------------------------------------------------------------------------------------------- #
+def _p(t, label=""):
+    """A guarded copy of an operand (tests/guarded.py): what a kernel loads past its end is NaN."""
+    return guarded.active_pool().place(t, label)
+
+
 def _head_inputs(B, H, W, C, g, d, y_max=HX.Y_FWD):
     y = HX.make_y((B, H, W, C), y_max, g, d)
     w = HX.make_head_w_saturating(C, g, d) if C == 16 else HX.make_head_w(C, g, d)
@@ -106,7 +116,7 @@ def test_depth_head_forward(shape, dtype):
         ref = HX.ref_depth(pre)
         depth = torch.full((B, 1, H, W), 7.0, device=d)
         with tuned(**sw):
-            ops.depth_head_fwd(y.to(dtype), w, b, depth)
+            ops.depth_head_fwd(_p(y.to(dtype), "y"), _p(w, "w"), _p(b, "b"), depth)
         _record(lab, f"depth fwd {form}", HX.expect_within(depth[:, 0], ref, HX.depth_rel_bound(pre) * ref, f"depth fwd {form} {lab}"))
         del y, pre, ref, depth
         _free()
@@ -130,12 +140,12 @@ def test_depth_head_dpre_and_input_gradient(shape, dtype):
     C = 16
     y, w, b = _head_inputs(B, H, W, C, g, d)
     pre = HX.ref_pre(y, w, b)
-    yk = y.to(dtype)
+    yk, wk, bk = _p(y.to(dtype), "y"), _p(w, "w"), _p(b, "b")
     depth = torch.empty(B, 1, H, W, device=d)
-    ops.depth_head_fwd(yk, w, b, depth)
+    ops.depth_head_fwd(yk, wk, bk, depth)
     lab = _label(B, H, W, dtype)
     n = B * H * W
-    dd = HX.make_d_depth((B, 1, H, W), g, d)
+    dd = _p(HX.make_d_depth((B, 1, H, W), g, d), "d depth")
     scratch = torch.full((n,), 7.0, device=d)
     # plain form: k_depth_head_dpre, then the granule form (production), the generic form by its switch, and a misaligned view
     for form, sw, view in (("granule", {}, False), ("generic (switch)", {"head_dgrad_generic": 1}, False), ("generic (misaligned)", {}, True)):
@@ -145,7 +155,7 @@ def test_depth_head_dpre_and_input_gradient(shape, dtype):
         else:
             dx = torch.full_like(yk, 5.0)
         with tuned(**sw):
-            ops.depth_head_bwd(yk, w, depth, dd, scratch, dx, None, None)
+            ops.depth_head_bwd(yk, wk, depth, dd, scratch, dx, None, None)
         dpre = scratch.view(B, H, W).clone()
         _record(lab, "d(pre)", HX.expect_within(dpre, HX.ref_dpre(pre, dd[:, 0].double()), HX.dpre_bound(pre, dd[:, 0].double()),
                                                 f"d(pre) {lab}"))
@@ -154,12 +164,12 @@ def test_depth_head_dpre_and_input_gradient(shape, dtype):
     # parts form (the training step's): device scales a power of two (exact) and general; g_raw on both halves
     Bh = B // 2
     if B % 2 == 0:
-        gf, gsec, gr, gr2 = (HX.make_d_depth((Bh, 1, H, W), g, d) for _ in range(4))
+        gf, gsec, gr, gr2 = (_p(HX.make_d_depth((Bh, 1, H, W), g, d), "gradient part") for _ in range(4))
         for sa, sb in ((0.5, 0.125), (0.3, 0.7)):
-            ta, tb = torch.tensor([sa], device=d), torch.tensor([sb], device=d)
+            ta, tb = _p(torch.tensor([sa], device=d), "scale a"), _p(torch.tensor([sb], device=d), "scale b")
             sa32, sb32 = float(ta), float(tb)
             dx = torch.full_like(yk, 5.0)
-            ops.depth_head_bwd_parts(yk, w, depth, gf, gsec, gr, ta, tb, scratch, dx, gr2)
+            ops.depth_head_bwd_parts(yk, wk, depth, gf, gsec, gr, ta, tb, scratch, dx, gr2)
             g0 = torch.cat([gf, gsec])[:, 0]
             graw = torch.cat([gr, gr2])[:, 0]
             gdd, gerr = HX.parts_g(g0, graw, sa32, sb32)
@@ -170,12 +180,12 @@ def test_depth_head_dpre_and_input_gradient(shape, dtype):
             del dx
     if shape in RAGGED:            # the generic C != 16 kernels
         y2, w2, b2 = _head_inputs(B, H, W, 8, g, d)
-        yk2 = y2.to(dtype)
+        yk2, wk2 = _p(y2.to(dtype), "y C=8"), _p(w2, "w C=8")
         dep2 = torch.empty(B, 1, H, W, device=d)
-        ops.depth_head_fwd(yk2, w2, b2, dep2)
+        ops.depth_head_fwd(yk2, wk2, _p(b2, "b C=8"), dep2)
         pre2 = HX.ref_pre(y2, w2, b2)
         dx = torch.full_like(yk2, 5.0)
-        ops.depth_head_bwd(yk2, w2, dep2, dd, scratch, dx, None, None)
+        ops.depth_head_bwd(yk2, wk2, dep2, dd, scratch, dx, None, None)
         dpre = scratch.view(B, H, W).clone()
         _record(lab, "d(pre) C=8", HX.expect_within(dpre, HX.ref_dpre(pre2, dd[:, 0].double()), HX.dpre_bound(pre2, dd[:, 0].double()),
                                                      f"d(pre) C=8 {lab}"))
@@ -194,17 +204,18 @@ def test_depth_head_bwd_equals_bwd_parts(shape, dtype):
     from coivo_amd import ops
     B, H, W = shape
     d, g = dev(), _gen("bwd = parts", shape)
-    dd = HX.make_d_depth((B, 1, H, W), g, d)
+    dd = _p(HX.make_d_depth((B, 1, H, W), g, d), "d depth")
+    lo, hi = _p(dd[:B // 2].contiguous(), "first half"), _p(dd[B // 2:].contiguous(), "second half")
     for form, C, sw in (("granule", 16, {"head_dgrad_generic": 0}), ("generic (switch)", 16, {"head_dgrad_generic": 1}), ("C=8", 8, {})):
         y, w, b = _head_inputs(B, H, W, C, g, d)
-        yk = y.to(dtype)
+        yk, w, b = _p(y.to(dtype), "y"), _p(w, "w"), _p(b, "b")
         depth = torch.empty(B, 1, H, W, device=d)
         ops.depth_head_fwd(yk, w, b, depth)
         s1, s2 = torch.full((B * H * W,), 7.0, device=d), torch.full((B * H * W,), 9.0, device=d)
         dx1, dx2 = torch.full_like(yk, 5.0), torch.full_like(yk, 3.0)
         with tuned(**sw):
             ops.depth_head_bwd(yk, w, depth, dd, s1, dx1, None, None)
-            ops.depth_head_bwd_parts(yk, w, depth, dd[:B // 2].contiguous(), dd[B // 2:].contiguous(), None, None, None, s2, dx2)
+            ops.depth_head_bwd_parts(yk, w, depth, lo, hi, None, None, None, s2, dx2)
         lab = f"{form} {_label(B, H, W, dtype)}"
         assert _same_bits(s1, s2), f"d(pre) of depth_head_bwd and depth_head_bwd_parts differ: {lab}"
         assert _same_bits(dx1, dx2), f"dx of depth_head_bwd and depth_head_bwd_parts differ: {lab}"
@@ -219,7 +230,7 @@ def _wgrad_operands(B, H, W, C, g, d):
     worst = float(y.abs().max()) / HX.QY * float(dpre.abs().sum(dtype=torch.float64)) / CX.QDY
     assert worst <= CX.BOUND, f"head weight gradient: {worst:.0f} quanta > 2^22"
     assert worst <= CX.bound_wgrad(B * H * W)
-    return y, dpre
+    return y, _p(dpre, "d(pre)")
 
 
 def _wgrad_atomic(y, dpre, dw, db):
@@ -243,7 +254,7 @@ def test_depth_head_weight_gradient_exact(shape, dtype):
     y, dpre = _wgrad_operands(B, H, W, 16, g, d)
     rdw, rdb = HX.ref_head_wgrad(y, dpre)
     q = HX.QY * CX.QDY
-    yk = y.to(dtype)
+    yk = _p(y.to(dtype), "y")
     for rows in (1, 3):
         with tuned(head_wgrad_rows=rows):
             dw, db = _zeros(16, d)
@@ -270,7 +281,7 @@ def test_depth_head_weight_gradient_exact(shape, dtype):
         y2, dp2 = _wgrad_operands(B, H, W, 8, g, d)
         rdw2, rdb2 = HX.ref_head_wgrad(y2, dp2)
         dw, db = _zeros(8, d)
-        ops.depth_head_wgrad(y2.to(dtype), dp2, dw, db)
+        ops.depth_head_wgrad(_p(y2.to(dtype), "y C=8"), dp2, dw, db)
         _exact(lab, "head wgrad generic C=8", dw, rdw2, q)
         _exact(lab, "head bgrad generic C=8", db, rdb2, CX.QDY)
     _free()
@@ -328,17 +339,18 @@ def test_fused_backward_head_form_exact(shape):
     w_fwd = torch.empty(16, 9, 16, device=d, dtype=torch.bfloat16)
     w_bwd = torch.empty(16, 9, 16, device=d, dtype=torch.bfloat16)
     ops.pack_weights(wm, torch.bfloat16, w_fwd, w_bwd)
-    xb, yb = x.bfloat16(), y.bfloat16()
+    xb, yb = _p(x.bfloat16(), "x"), _p(y.bfloat16(), "y")
+    dpre_k, wh_k = _p(dpre, "d(pre)"), _p(wh, "head weights")
     qg = CX.QDY * HX.QH_OP
     for form in ("HEAD", "HEAD + head partials"):
         dx = torch.full_like(xb, 3.0)
         dw, db = torch.zeros(16, 9, 16, device=d), torch.zeros(16, device=d)
         if form == "HEAD":
-            ops.conv_bwd_fused(desc, yb, w_bwd, xb, True, dx, dw, db, dpre, wh)
+            ops.conv_bwd_fused(desc, yb, w_bwd, xb, True, dx, dw, db, dpre_k, wh_k)
         else:
             rows = ops.conv_bwd_fused_head_rows(desc)
             hp = torch.full((rows * 145,), float("nan"), device=d)
-            ops.conv_bwd_fused(desc, yb, w_bwd, xb, True, dx, dw, db, dpre, wh, hp)
+            ops.conv_bwd_fused(desc, yb, w_bwd, xb, True, dx, dw, db, dpre_k, wh_k, hp)
             hw_, hb_ = _zeros(16, d)
             ops.depth_head_wgrad_reduce(hp, rows, hw_, hb_)
             _exact(lab, "bwd16 head partials: head wgrad", hw_, hdw, HX.QY * CX.QDY)
@@ -378,20 +390,20 @@ def test_fused_forward_depth_and_pose_input(shape):
     ref = HX.ref_depth(pre)
     bound = HX.depth_rel_bound(pre) * ref
     print(f"HEAD-ERR {lab} fused fwd: |pre| max {float(pre.abs().max()):.3g}, saturated pixels {int((pre.abs() > HX.SAT_PRE).sum())}")
-    xb = x.bfloat16()
+    xb, bias_k, wh_k, hb_k = _p(x.bfloat16(), "x"), _p(bias, "bias"), _p(wh, "head weights"), _p(hb, "head bias")
     depths = []
     for with_pose in ((True, False) if B % 2 == 0 else (False,)):
         y = torch.full((B, H, W, 16), 9.0, device=d, dtype=torch.bfloat16)
         depth = torch.full((B, 1, H, W), 7.0, device=d)
         pose_in = None
         if with_pose:
-            frames = torch.rand(B, 3, H, W, generator=g, device=d)
+            frames = _p(torch.rand(B, 3, H, W, generator=g, device=d), "frames")
             stem = torch.full((B, H, W, 8), 3.0, device=d, dtype=torch.bfloat16)
             pose_in = torch.full((B // 2, H, W, 8), 3.0, device=d, dtype=torch.bfloat16)
             ops.pack_stem_pose(frames, stem, pose_in)
             want = torch.cat([frames.permute(0, 2, 3, 1), torch.zeros(B, H, W, 5, device=d)], 3).bfloat16()
             assert torch.equal(stem.view(torch.int16), want.view(torch.int16)), "pack_stem_pose: stem"
-        ops.conv_head_fused(desc, xb, w_fwd, bias, wh, hb, y, depth, pose_in)
+        ops.conv_head_fused(desc, xb, w_fwd, bias_k, wh_k, hb_k, y, depth, pose_in)
         form = "fused fwd + pose_in" if with_pose else "fused fwd"
         for b0, b1 in lay.slices():
             CX.expect_exact(y[b0:b1], yref[b0:b1], CX.QB, f"{form} y {lab}")
@@ -426,7 +438,8 @@ def test_pose_head(shape, dtype):
     x = CX.make_source((B, H, W, C), g, d)
     w = CX._ints(-CX.W_MAX, CX.W_MAX, (8, 1, C), g, d) * CX.QW
     b = CX.make_bias(8, g, d)
-    xk = x.to(dtype)
+    pool = guarded.active_pool()
+    xk, w, b = pool.place(x.to(dtype), "x"), pool.place(w, "w"), pool.place(b, "b")         # a load past the end of x or w reads NaN
     out = torch.full((8 * B,), 7.0, device=d)
     ops.pose_head_fwd(xk, w, b, out)
     got = torch.cat([out[:6 * B].view(B, 6), out[6 * B:7 * B].view(B, 1), out[7 * B:].view(B, 1)], 1)
@@ -439,16 +452,21 @@ def test_pose_head(shape, dtype):
         tb = None if sb is None else torch.tensor([sb], device=d)
         sa32, sb32 = (1.0, 1.0) if sa is None else (float(ta), float(tb))
         r = HX.pose_bwd_refs(x, w, dout, sa32, sb32)
-        for det in (False, True):
+        parts = [pool.place(dout[:, lo:hi].contiguous(), f"d_out[:, {lo}:{hi}]") for lo, hi in ((0, 6), (6, 7), (7, 8))]
+        # the atomic form, then the deterministic one in both of its forms: the parallel one (the default) twice, then the serial walk
+        # (tuning pose_head_det_parallel = 0), which must give the parallel form's bits
+        for det, pars in ((False, (None,)), (True, (1, 1, 0))):
             outs = []
-            for _ in range(2 if det else 1):
+            for par in pars:
                 dx = torch.full_like(xk, 5.0)
                 dw, db = torch.zeros(8, 1, C, device=d), torch.zeros(8, device=d)
-                ops.pose_head_bwd(xk, w, dout[:, :6].contiguous(), dout[:, 6:7].contiguous(), dout[:, 7:8].contiguous(), dx, dw, db,
-                                  ta, tb, deterministic=det)
+                with contextlib.nullcontext() if par is None else tuned(pose_head_det_parallel=par):
+                    ops.pose_head_bwd(xk, w, parts[0], parts[1], parts[2], dx, dw, db, ta, tb, deterministic=det)
+                    torch.cuda.synchronize()
                 outs.append((dx, dw, db))
             if det:
                 assert all(torch.equal(a, c) for a, c in zip(outs[0], outs[1])), "deterministic pose head: not repeatable"
+                assert all(_same_bits(a, c) for a, c in zip(outs[0], outs[2])), "pose head: the serial walk and the parallel form differ"
             dx, dw, db = outs[0]
             dxb, dwb, dbb = HX.pose_bwd_bounds(r, B, dtype, det)
             form = f"pose bwd {'det' if det else 'atomics'} s={sa}*{sb}"

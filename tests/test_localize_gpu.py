@@ -216,3 +216,24 @@ def test_argument_errors():
         Z.localize_polyps(d, lab, narrow, M, num_labels=3)
     with pytest.raises(ValueError, match="2\\^62"):
         Z.localize_polyps(d, lab, K, M, num_labels=3, max_depth=2.0 ** 18)
+
+
+@pytest.mark.parametrize("clip", [None, R.CLIP_SIGMA], ids=["plain", "clip_sigma"])
+def test_memory_discipline(clip):
+    """localize_polyps under tests/guarded.py on 4 frames of 64 x 96 at stride 2 with four labels, min_samples 40: depths, labels,
+    intrinsics and poses between guard bands; the records (colvo_localize_workspace_bytes), the clip bounds and every per-observation
+    and per-label output from the pool under both poisons.  Outputs equal the replica, are the same bytes under either poison, and no
+    guard byte changes.  Launches reached: the clearing of the records, the accumulation pass and the write-out; with clip_sigma the
+    bounds pass and the second, clipped accumulation as well."""
+    from coivo_amd import _lib, localize as Z
+    from tests import guarded as G
+    key = (4, 64, 96, 2, 4)
+    d, lab, K, M = _scene(key)
+    want = _want(key, clip, 40)
+    assert want["n_labelled"] > 0
+    run = lambda pool: Z.localize_polyps(pool.place(_t(d)), pool.place(_t(lab)), pool.place(_t(K)), pool.place(_t(M)), num_labels=4, stride=2,
+                                         max_depth=R.MAX_DEPTH, clip_sigma=clip, min_samples=40)
+    outs, pools = G.under_both_poisons(dev(), run, f"localize_polyps clip {clip}")
+    for got, pool in zip(outs, pools):
+        _assert_equal(got, want, clip)
+        G.assert_served(pool, 0, _lib.load().colvo_localize_workspace_bytes(4, 4), "localize_polyps")

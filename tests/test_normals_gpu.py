@@ -201,3 +201,24 @@ def test_argument_errors_on_the_device_path_launch_nothing():
             I.cloud_normals(fused, *bad, max_depth=MAX_DEPTH)
     with pytest.raises(ValueError, match="voxels"):
         I.cloud_normals(fused._replace(voxels=fused.voxels.cpu()), dt, Kt, Mt, max_depth=MAX_DEPTH)
+
+
+# ---- memory discipline ------------------------------------------------------------------------------------------------- #
+def test_memory_discipline():
+    """cloud_normals under tests/guarded.py on the 5 x 17 x 23 tube, stride 2, a cloud of min_obs = 2 (matched and unmatched samples):
+    depths, intrinsics, poses and the cloud's tensors between guard bands -- a one-sided difference at the first or last image row of
+    frame 0 or 4 borders a guard --; the scratch (colvo_cloud_normals_scratch_bytes: the integer sums per row), normals, counts,
+    coherence and statistics from the pool under both poisons.  Outputs equal the replica, are the same bytes under either poison, and
+    no guard byte changes.  Launches reached: the clearing of the sums, the sample pass with its binary search and the write-out."""
+    from coivo_amd import _lib, inference as I
+    from tests import guarded as G
+    d, K, M = _tube(17, 23)
+    fused = _fuse(d, K, M, stride=2, min_obs=2)
+    want = _want(fused, d, K, M, stride=2, rel_edge=0.2)
+    assert want["stats"][2] > 0 and want["stats"][3] > 0
+    run = lambda pool: I.cloud_normals(pool.place_tree(fused), pool.place(_t(d)), pool.place(_t(K)), pool.place(_t(M)), stride=2,
+                                       max_depth=MAX_DEPTH, rel_edge=0.2)
+    outs, pools = G.under_both_poisons(dev(), run, "cloud_normals")
+    for got, pool in zip(outs, pools):
+        _assert_equal(got, want, "guarded")
+        G.assert_served(pool, 0, _lib.load().colvo_cloud_normals_scratch_bytes(fused.voxels.shape[0]), "cloud_normals")

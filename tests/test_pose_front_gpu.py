@@ -15,9 +15,12 @@ import torch
 
 from coivo_amd import _lib, ops
 from tests import conv_exact as X
+from tests import guarded
 from tests.gpu_util import dev
 
 pytestmark = pytest.mark.gpu
+
+_guarded = guarded.fixture(dev)          # every test here allocates from tests/guarded.py's pool; the guards are checked at its end
 
 SHAPES = [(1, 32, 32), (2, 64, 96), (3, 96, 160), (8, 256, 320)]
 CH = (8, 16, 32, 64)

@@ -339,3 +339,36 @@ def test_argument_errors_on_the_device_path_launch_nothing():
     out = I.render_mesh(v[::2], f, K, M, 17, 23, colors=c[::2], max_depth=MAX_DEPTH)             # non-contiguous input: taken as it reads
     assert out.depth.shape == (5, 1, 17, 23) and out.colors.shape == (5, 3, 17, 23)
     assert int(out.stats[:, 0].sum()) < int(I.render_mesh(v, f, K, M, 17, 23, max_depth=MAX_DEPTH).stats[:, 0].sum())   # half the faces are dead
+
+
+# ---- memory discipline ------------------------------------------------------------------------------------------------- #
+def test_memory_discipline():
+    """render_mesh under tests/guarded.py: vertices, faces, colours, intrinsics and the pose between guard bands; the scratch
+    (colvo_render_scratch_bytes), depth, index, colours, normals, the per-face pixel counts and the statistics from the pool under both
+    poisons.  Outputs equal the replica, are the same bytes under either poison, and no guard byte changes.  Launches reached: the
+    clearing of the keys, the draw kernel in both forms -- 400 faces below a pixel on the lane walk, four large ones (two larger than
+    the 40 x 40 image, one leaving it on two sides: their clamped boxes end on the image's last row) on the wave walk, at the default
+    threshold and with every face on the wave walk -- and the resolve with colours, normals and face counts; then the tube's 5 views
+    of 17 x 23 with back-face culling."""
+    from coivo_amd import _lib, inference as I
+    from tests import guarded as G
+    lib = _lib.load()
+    v, f, c, K, M = _large_and_small_faces()
+    kw = dict(max_depth=MAX_DEPTH, want_normals=True, want_face_pixels=True)
+    want = R.render(v, f, K, M, 40, 40, colors=c, **kw)
+    run = lambda pool: I.render_mesh(pool.place(_t(v)), pool.place(_t(f)), pool.place(_t(K)), pool.place(_t(M)), 40, 40,
+                                     colors=pool.place(_t(c)), **kw)
+    for coop in (256, 0):
+        with _tuned("raster_coop_min_pixels", coop):
+            outs, pools = G.under_both_poisons(dev(), run, f"render_mesh, wave walk from {coop} pixels")
+        for got, pool in zip(outs, pools):
+            _assert_equal(got, want, coop)
+            G.assert_served(pool, 0, lib.colvo_render_scratch_bytes(1, 40, 40), "render_mesh")
+    v, f, c, _, K, M = _tube(17, 23)
+    want = _tube_want(17, 23, True)
+    run = lambda pool: I.render_mesh(pool.place(_t(v)), pool.place(_t(f)), pool.place(_t(K)), pool.place(_t(M)), 17, 23,
+                                     colors=pool.place(_t(c)), cull_back=True, **kw)
+    outs, pools = G.under_both_poisons(dev(), run, "render_mesh, the tube")
+    for got, pool in zip(outs, pools):
+        _assert_equal(got, want, "tube")
+        G.assert_served(pool, 0, lib.colvo_render_scratch_bytes(M.shape[0], 17, 23), "render_mesh")

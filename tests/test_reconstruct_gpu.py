@@ -183,3 +183,29 @@ def test_reconstruct_sequence_is_held_to_the_replica():
             n_inf = int(torch.isinf(depths).sum().item())
             assert 0 < n_inf < depths.numel() and got.shape[0] < depths.numel()
         _hold("reconstruct_sequence", "12x64x96 stride 1" + ("" if policy is None else " consistency"), got, ref, bound)
+
+
+def test_memory_discipline():
+    """backproject and stitch_point_cloud under tests/guarded.py: depths, intrinsics and poses between guard bands; the points, the
+    count and the block workspace (colvo_stitch_workspace_ints) from the pool under both poisons.  Outputs hold the replica's bound as
+    above, are the same bytes under either poison, and no guard byte changes.  Launches reached: k_backproject at 3 x 17 x 23 (a ragged
+    last block); k_stitch_count, k_scan_top and k_stitch_write at n600 (300 frames of 17 x 23: 600 blocks, three per thread of the
+    scan's top-level workgroup, the last share ragged)."""
+    from coivo_amd import _lib, inference as I
+    from tests import guarded as G
+    depth, K, M, ref, bound, _ = R.backproject_case(3, 17, 23)
+    outs, pools = G.under_both_poisons(dev(), lambda pool: I.backproject(pool.place(_d(depth)), pool.place(_d(K)), pool.place(_d(M))),
+                                       "backproject")
+    for got, pool in zip(outs, pools):
+        _hold("k_backproject", "3x17x23 guarded", got.cpu().numpy(), ref, bound)
+        G.assert_served(pool, 0, 3 * 17 * 23 * 3 * 4, "backproject")
+    c = R.stitch_case("n600", "plain")
+    assert c["n_blocks"] == 600 > 256
+    outs, pools = G.under_both_poisons(dev(), lambda pool: I.stitch_point_cloud(pool.place(_d(c["depth"])), pool.place(_d(c["K"])),
+                                                                                pool.place(_d(c["M"])), stride=c["stride"],
+                                                                                max_depth=c["max_depth"]), "stitch_point_cloud")
+    N, _, H, W = c["depth"].shape
+    for got, pool in zip(outs, pools):
+        assert got.shape == (len(c["idx"]), 3)
+        _hold("k_stitch_write", "n600 plain guarded", got.cpu().numpy(), c["ref"], c["bound"])
+        G.assert_served(pool, 0, 4 * int(_lib.load().colvo_stitch_workspace_ints(N, H, W, c["stride"])), "stitch_point_cloud")

@@ -315,3 +315,31 @@ def test_argument_errors_on_the_device():
             I.refine_edges(d, f, k, ok, bad_T)
     out = I.refine_edges(d, f, k, torch.tensor(ok), T.cpu(), iterations=1, min_samples=16, max_depth=MAX_DEPTH)     # host T, tensor edges
     assert tuple(out.T.shape) == (2, 4, 4) and out.T.is_cuda
+
+
+# ---- memory discipline ------------------------------------------------------------------------------------------------------ #
+def test_memory_discipline():
+    """refine_edges (six iterations) and refine_accumulate under tests/guarded.py: depths, frames, intrinsics and the starting edges
+    between guard bands; the workspace (colvo_refine_workspace_bytes for that many iterations), T, gain, offset, the history and the
+    status from the pool under both poisons.  The loop meets the replica as in test_loop_equals_the_replica, every output is the same
+    bytes under either poison, and no guard byte changes.  Launches reached, at 5 frames of 48 x 64 and 4 edges: the strip sums, their
+    fixed-order reduction and the float64 solve of every iteration, the final evaluation and the revert decision."""
+    from coivo_amd import _lib, inference as I
+    from tests import guarded as G
+    lib = _lib.load()
+    depths, frames, K, M, Tt, T0 = _start(48, 64)
+    want = _replica_loop(48, 64, ())
+
+    def run(pool):
+        args = (pool.place(_t(depths)), pool.place(_t(frames)), pool.place(_t(K)), _pairs(5), pool.place(_t(T0)))
+        return I.refine_edges(*args, max_depth=MAX_DEPTH), I.refine_accumulate(*args, max_depth=MAX_DEPTH)
+    outs, pools = G.under_both_poisons(dev(), run, "refine_edges")
+    for (got, (sums, counts)), pool in zip(outs, pools):
+        assert got.status.cpu().tolist() == want["status"].tolist() and tuple(got.history.shape) == (4, 7, 5)
+        assert np.abs(got.T.cpu().numpy() - want["T"]).max() <= 1e-6
+        assert np.abs(got.gain.cpu().numpy() - want["gain"]).max() <= 1e-6 and np.abs(got.offset.cpu().numpy() - want["offset"]).max() <= 1e-6
+        h, hw = got.history.cpu().numpy(), want["history"]
+        assert np.array_equal(h[:, 0, [0, 1, 3]], hw[:, 0, [0, 1, 3]]) and np.allclose(h[:, 0, [2, 4]], hw[:, 0, [2, 4]], rtol=1e-12, atol=0)
+        assert bool(torch.isfinite(sums).all()) and not bool(sums[:, 46:].any()) and not bool(counts[:, 3].any())
+        G.assert_served(pool, 0, lib.colvo_refine_workspace_bytes(4, 5, 48, 64, 6), "refine_edges")
+        G.assert_served(pool, 0, lib.colvo_refine_workspace_bytes(4, 5, 48, 64, 1), "refine_accumulate")

@@ -281,3 +281,31 @@ def test_argument_errors_on_the_device():
     assert int(out.status) == E.REGISTER_OK and torch.equal(out.R, out2.R) and tuple(out.history.shape) == (2, 5)
     m = E.cloud_metrics(q, p, max_dist=0.3, thresholds=(0.1,), register=E.Registration(metric="point", iterations=2))
     assert int(m.registration.status) == E.REGISTER_OK and tuple(m.registration.history.shape) == (3, 5)
+
+
+# ---- memory discipline ---------------------------------------------------------------------------------------------------- #
+@pytest.mark.parametrize("mode", ["se3", "sim3"])
+def test_memory_discipline(mode):
+    """register_clouds (point to plane, eight iterations) under tests/guarded.py on the small tube: source, target and normals between
+    guard bands; the target's index (colvo_cloud_workspace_bytes(0, M)), the scratch (colvo_register_scratch_bytes), the state, the
+    history, the status and the normal matrix from the pool under both poisons.  The loop meets the replica as in
+    test_loop_equals_the_replica, every output is the same bytes under either poison, and no guard byte changes.  Launches reached:
+    colvo_cloud_index_build, and per iteration the pair search with its partial rows, the row reduction and the float64 solve, with
+    the scale column in sim3."""
+    from coivo_amd import _lib, evaluate as E
+    from tests import guarded
+    lib = _lib.load()
+    sc, want = _replica_loop(True, mode, "plane")
+    run = lambda pool: E.register_clouds(pool.place(_t(sc["source"])), pool.place(_t(sc["target"])), target_normals=pool.place(_t(sc["normals"])),
+                                         max_dist=sc["max_dist"], mode=mode, metric="plane", iterations=ITER)
+    outs, pools = guarded.under_both_poisons(dev(), run, f"register_clouds {mode}")
+    for got, pool in zip(outs, pools):
+        assert int(got.status) == want["status"] == G.OK
+        h, hw = got.history.cpu().numpy(), want["history"]
+        assert np.array_equal(h[:, :3], hw[:, :3]) and np.allclose(h[0, 3:], hw[0, 3:], rtol=1e-12, atol=0)
+        d = max(np.abs(got.R.cpu().numpy() - want["R"]).max(), np.abs(got.t.cpu().numpy() - want["t"]).max(), abs(float(got.s) - want["s"]))
+        assert d <= 1e-6, d
+        nm = got.normal_matrix.cpu().numpy()
+        assert np.array_equal(nm, nm.T) and np.allclose(nm, want["normal_matrix"], rtol=1e-6, atol=1e-6 * np.abs(want["normal_matrix"]).max())
+        guarded.assert_served(pool, 0, lib.colvo_cloud_workspace_bytes(0, len(sc["target"])), "the target's index")
+        guarded.assert_served(pool, 0, lib.colvo_register_scratch_bytes(len(sc["source"])), "register_clouds")

@@ -333,3 +333,33 @@ def test_argument_errors_on_the_device():
             I.render_cloud(pts, K, M, 17, 23, **kw)
     out = I.render_cloud(pts[::2], K, M, 17, 23, radius=0.02, colors=col[::2], max_depth=MAX_DEPTH)      # non-contiguous input: taken as it reads
     assert out.depth.shape == (3, 1, 17, 23) and out.colors.shape == (3, 3, 17, 23)
+
+
+# ---- memory discipline ------------------------------------------------------------------------------------------------- #
+@pytest.mark.parametrize("case", ["37_views_17x23", "tube_64x96_clipped"])
+def test_memory_discipline(case):
+    """render_cloud under tests/guarded.py: points, colours, intrinsics and poses between guard bands; the scratch
+    (colvo_render_scratch_bytes: the 64-bit keys), depth, index, colours and statistics from the pool under both poisons.  Outputs
+    equal the replica, are the same bytes under either poison, and no guard byte changes -- a square that hangs over the image's first or
+    last row of view 0 or N - 1 would land in one.  Launches reached: the clearing of the keys, the splat kernel and the resolve; 37
+    views are three frame groups, the last ragged, with per-frame intrinsics; the 64 x 96 tube at max_splat 2 runs the clip path."""
+    from coivo_amd import _lib, inference as I
+    from tests import guarded as G
+    if case == "37_views_17x23":
+        H, W = 17, 23
+        _, K, M = _cams(37, H, W, per_frame_K=True)
+        pts = _frustum_points(500, 7, K, M, H, W)
+        col = np.random.default_rng(3).random((500, 3), dtype=np.float32)
+        kw = dict(radius=0.04, max_splat=8, max_depth=MAX_DEPTH)
+    else:
+        H, W = 64, 96
+        pts, col, _, K, M = _tube(3, H, W)
+        K, M = K[1:2], M[1:2]
+        kw = dict(radius=0.05, max_splat=2, max_depth=MAX_DEPTH)
+    want = R.render(pts, K, M, H, W, colors=col, **kw)
+    assert want["stats"][:, 1].min() > 0 and (case.startswith("37") or want["stats"][0, 2] > 0)
+    run = lambda pool: I.render_cloud(pool.place(_t(pts)), pool.place(_t(K)), pool.place(_t(M)), H, W, colors=pool.place(_t(col)), **kw)
+    outs, pools = G.under_both_poisons(dev(), run, case)
+    for got, pool in zip(outs, pools):
+        _assert_equal(got, want, case)
+        G.assert_served(pool, 0, _lib.load().colvo_render_scratch_bytes(M.shape[0], H, W), case)

@@ -2,8 +2,9 @@
 colvo_pack_stem_pose, enc1a (8 -> 32, stride 2) and enc1b (32 -> 32) through colvo_conv_fwd.
 
 The launch must give the same BITS in all four tensors it writes -- the packed stem input, the frame channels of PoseNet's input,
-enc1a and enc1b -- torch.equal against the plain launches in one process.  Every destination sits inside a larger buffer filled with
-a sentinel: an element the kernel leaves unwritten shows, and so does a byte written outside the tensor.  The plain calls' form
+enc1a and enc1b -- torch.equal against the plain launches in one process.  Every destination comes from tests/guarded.py's pool:
+poisoned with 0xFF bytes (NaN in bf16) between guard bands, so an element the kernel leaves unwritten shows, and so does a byte
+written outside the tensor; the frames, weights and biases are guarded copies, so a tap outside a frame reads NaN.  The plain calls' form
 counters say that the references are the forms the bits are tied to.  Frame sizes (2 and 3 pairs of each):
     32 x 48     enc1 maps of 16 x 24: several tiles, none ragged
     36 x 52     18 x 26: the planner's tile adapts to it (9 x 13: odd tile width, 117 pixels, the last fragments partly empty)
@@ -19,14 +20,13 @@ import torch
 
 from coivo_amd import _lib, ops
 from tests import conv_exact as X
+from tests import guarded
 from tests.gpu_util import dev
 
 pytestmark = pytest.mark.gpu
 
 SIZES = [(32, 48), (36, 52), (46, 58), (16, 16)]
 PAIRS = (2, 3)
-SENTINEL = 77.0
-GUARD = 4096                                    # bytes in front of and behind every destination
 
 
 class _tune:
@@ -59,59 +59,50 @@ def _pack(wm):
     return w_fwd
 
 
-class _Guarded:
-    """A bf16 tensor of `shape` inside a sentinel-filled buffer with GUARD bytes on either side."""
-
-    def __init__(self, shape):
-        n = 1
-        for s in shape:
-            n *= s
-        self.buf = torch.full((n + GUARD,), SENTINEL, device=dev(), dtype=torch.bfloat16)       # (GUARD bytes = GUARD / 2 elements a side)
-        self.t = self.buf[GUARD // 2:GUARD // 2 + n].view(shape)
-        assert self.t.data_ptr() % 16 == 0
-
-    def guards_intact(self):
-        g = GUARD // 2
-        return bool((self.buf[:g] == SENTINEL).all()) and bool((self.buf[-g:] == SENTINEL).all())
-
-
 def _dests(pairs, H, W, da):
+    """(pool, the four destinations): bf16 tensors of NaN between guard bands."""
     B = 2 * pairs
-    return [_Guarded((B, H, W, 8)), _Guarded((pairs, H, W, 8)), _Guarded((B, da.Ho, da.Wo, 32)), _Guarded((B, da.Ho, da.Wo, 32))]
+    pool = guarded.Pool(dev())
+    shapes = ((B, H, W, 8), (pairs, H, W, 8), (B, da.Ho, da.Wo, 32), (B, da.Ho, da.Wo, 32))
+    return pool, [pool.empty(shape, torch.bfloat16, label=name) for shape, name in zip(shapes, NAMES)]
 
 
 NAMES = ("stem input", "PoseNet input", "enc1a", "enc1b")
+OPERANDS = ("frames", "enc1a weights", "enc1a bias", "enc1b weights", "enc1b bias")
 
 
 def _plain(da, db, frames, w1, b1, w2, b2):
-    """The three launches, into guarded sentinel-filled destinations; the form counters of the two conv calls."""
+    """The three launches, into guarded poisoned destinations; the form counters of the two conv calls."""
     pairs, (_, _, H, W) = da.B // 2, frames.shape
-    out = _dests(pairs, H, W, da)
-    ops.pack_stem_pose(frames, out[0].t, out[1].t)
+    pool, out = _dests(pairs, H, W, da)
+    frames, w1, b1, w2, b2 = (pool.place(t, n) for t, n in zip((frames, w1, b1, w2, b2), OPERANDS))
+    ops.pack_stem_pose(frames, out[0], out[1])
     forms = []
-    for d, x, w, b, y in ((da, out[0].t, w1, b1, out[2].t), (db, out[2].t, w2, b2, out[3].t)):
+    for d, x, w, b, y in ((da, out[0], w1, b1, out[2]), (db, out[2], w2, b2, out[3])):
         before = _lib.form_counts()
         ops.conv_fwd(d, x, None, w, b, y)
         torch.cuda.synchronize()
         forms.append(X.forms_diff(before, _lib.form_counts()))
+    pool.check("the three launches")
     return out, forms
 
 
 def _fused(da, frames, w1, b1, w2, b2):
     pairs, (_, _, H, W) = da.B // 2, frames.shape
-    out = _dests(pairs, H, W, da)
+    pool, out = _dests(pairs, H, W, da)
+    frames, w1, b1, w2, b2 = (pool.place(t, n) for t, n in zip((frames, w1, b1, w2, b2), OPERANDS))
     before = _lib.form_counts()
-    ops.stem_fused(da, frames, out[0].t, out[1].t, w1, b1, out[2].t, w2, b2, out[3].t)
+    ops.stem_fused(da, frames, out[0], out[1], w1, b1, out[2], w2, b2, out[3])
     torch.cuda.synchronize()
     assert _lib.form_counts() == before                                 # the launch counts no form
+    pool.check("the fused stem")                                         # no byte outside a destination or an operand was written
     return out
 
 
 def _bits_equal(ref, got, what):
     for name, r, y in zip(NAMES, ref, got):
-        assert r.guards_intact() and y.guards_intact(), f"{what}: bytes outside {name} were written"
-        assert not bool((y.t == SENTINEL).any()), f"{what}: {name} has unwritten elements"
-        ri, yi = r.t.view(torch.int16), y.t.view(torch.int16)
+        assert not bool(torch.isnan(y).any()) and not bool(torch.isnan(r).any()), f"{what}: {name} has unwritten elements"
+        ri, yi = r.view(torch.int16), y.view(torch.int16)
         assert torch.equal(ri, yi), f"{what}: {name}: {int((ri != yi).sum())} of {ri.numel()} elements differ"
 
 
@@ -168,7 +159,7 @@ def test_the_launch_gives_the_bits_of_the_three_launches(H, W, pairs, wgs):
         got = _fused(da, frames, w1, b1, w2, b2)
     _bits_equal([r for r in ref], got, f"{pairs} pairs of {H}x{W}, {nwg} workgroups")
     # the border of enc1b depends on the halo being zero: with a halo of relu(bias) it would differ from this reference
-    frac = float((ref[3].t == 0).float().mean())
+    frac = float((ref[3] == 0).float().mean())
     assert 0.02 < frac < 0.98, f"enc1b's ReLU mask is not mixed ({frac:.2f} zeros)"
 
 
@@ -181,9 +172,9 @@ def test_the_frame_channels_are_the_rounded_frames():
     frames = _frames(pairs, H, W, g)
     got = _fused(da, frames, *_operands(g))
     want = frames.to(torch.bfloat16).permute(0, 2, 3, 1)                  # torch rounds to nearest even
-    assert torch.equal(got[0].t[..., :3], want) and not bool(got[0].t[..., 3:].any())
-    assert torch.equal(got[1].t[..., :3], want[:pairs]) and torch.equal(got[1].t[..., 3:6], want[pairs:])
-    assert not bool(got[1].t[..., 6:].any())
+    assert torch.equal(got[0][..., :3], want) and not bool(got[0][..., 3:].any())
+    assert torch.equal(got[1][..., :3], want[:pairs]) and torch.equal(got[1][..., 3:6], want[pairs:])
+    assert not bool(got[1][..., 6:].any())
 
 
 @pytest.mark.parametrize("pairs,H,W", [(2, 36, 52), (3, 32, 48)])
@@ -203,10 +194,10 @@ def test_both_layers_are_exact_on_exact_data(pairs, H, W):
     x8[..., :3] = frames.permute(0, 2, 3, 1)
     want1 = X.Layer.of_desc(da).ref_fwd(x8, None, wm1, b1, 0, B)
     got = _fused(da, frames, _pack(wm1), b1, _pack(wm2), b2)
-    X.expect_exact(got[2].t, want1, X.QB, "enc1a inside the fused stem")
-    assert torch.equal(got[2].t.double(), want1)                          # ... and exact in bf16: enc1b's input is exact data
-    want2 = X.Layer.of_desc(db).ref_fwd(got[2].t.float(), None, wm2, b2, 0, B)
-    X.expect_exact(got[3].t, want2, X.QB * X.QW, "enc1b inside the fused stem")
+    X.expect_exact(got[2], want1, X.QB, "enc1a inside the fused stem")
+    assert torch.equal(got[2].double(), want1)                          # ... and exact in bf16: enc1b's input is exact data
+    want2 = X.Layer.of_desc(db).ref_fwd(got[2].float(), None, wm2, b2, 0, B)
+    X.expect_exact(got[3], want2, X.QB * X.QW, "enc1b inside the fused stem")
     ref, _ = _plain(da, db, frames, _pack(wm1), b1, _pack(wm2), b2)
     _bits_equal(ref, got, "exact data")
 
@@ -272,10 +263,10 @@ def test_a_request_is_refused_where_the_stem_is_not_selected():
     da, _ = _descs(pairs, H, W)
     frames = _frames(pairs, H, W, g)
     ops_ = _operands(g)
-    out = _dests(pairs, H, W, da)
+    pool, out = _dests(pairs, H, W, da)
     with _tune(stem_fused=0):
         assert ops.stem_plan(da) is None
         with pytest.raises(RuntimeError, match="the fused stem is not selected"):
-            ops.stem_fused(da, frames, out[0].t, out[1].t, ops_[0], ops_[1], out[2].t, ops_[2], ops_[3], out[3].t)
-    torch.cuda.synchronize()
-    assert all(bool((o.buf == SENTINEL).all()) for o in out)
+            ops.stem_fused(da, frames, out[0], out[1], ops_[0], ops_[1], out[2], ops_[2], ops_[3], out[3])
+    pool.check("a refused request")
+    assert all(bool((o.view(torch.uint8) == guarded.GUARD_BYTE).all()) for o in out)           # ... and nothing inside them either

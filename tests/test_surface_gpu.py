@@ -362,3 +362,36 @@ def test_surface_reconstruction_metrics_equals_the_pipeline_of_the_replicas():
                                             max_depth=T.TUBE_MAX_DEPTH, align="none")
     _assert_metrics(none, S.metrics((pred.vertices.cpu().numpy(), pred.faces.cpu().numpy()), (gt_mesh["vertices"], gt_mesh["faces"]),
                                     4.0 * vs, (vs, 2.0 * vs)), "align none")
+
+
+# ---- memory discipline ---------------------------------------------------------------------------------------------------------------- #
+def test_memory_discipline():
+    """point_to_surface under tests/guarded.py: queries, vertices and faces between guard bands, the scratch of
+    colvo_surface_scratch_bytes, the index and every output from the pool under both poisons, with both record forms.  Outputs equal the
+    replica, are the same bytes under either poison, and no guard byte changes.  Launches reached: the thin tube's mesh with one
+    triangle across its bounding box runs colvo_surface_index_plan, the index fill and the query with a non-empty oversize list
+    (stats[18] = 1) and three threshold counts."""
+    from coivo_amd import _lib, evaluate as E
+    from tests import guarded as G
+    lib = _lib.load()
+    v, f, vox = _scene("thin")
+    md = 1.5 * vox
+    rng = np.random.default_rng(32)
+    Q = (v[rng.integers(0, len(v), 1500)] + rng.normal(0, 0.8 * vox, (1500, 3))).astype(f32)
+    lo, hi = v.min(axis=0), v.max(axis=0)
+    v1 = np.concatenate([v, [lo, [hi[0], lo[1], lo[2]], hi]]).astype(f32)
+    f1 = np.concatenate([f, [[len(v), len(v) + 1, len(v) + 2]]]).astype(np.int32)
+    th = (0.5 * vox, vox, md)
+    want = S.full_stats(Q, v1, f1, md, th)
+    assert want["stats"][18] == 1 and (want["face"] == len(f)).sum() > 0
+    saved = _lib.tune_get("surface_copy_records")
+    try:
+        for copy in (0, 1):
+            _lib.tune_set("surface_copy_records", copy)
+            outs, pools = G.under_both_poisons(dev(), lambda pool: E.point_to_surface(pool.place(_t(Q)), pool.place(_t(v1)), pool.place(_t(f1)),
+                                                                                     max_dist=md, thresholds=th), f"point_to_surface, copy {copy}")
+            for got, pool in zip(outs, pools):
+                _assert_equal(got, want, f"oversize, copy {copy}")
+                G.assert_served(pool, 0, lib.colvo_surface_scratch_bytes(len(v1), len(f1)), f"point_to_surface, copy {copy}")
+    finally:
+        _lib.tune_set("surface_copy_records", saved)

@@ -385,3 +385,27 @@ def test_argument_errors_on_the_device_path_launch_nothing():
         I.render_surfels(pts, nrm, K, M, 17, 23, radius=0.02, colors=col[:-1])
     out = I.render_surfels(pts[::2], nrm[::2], K, M, 17, 23, radius=0.02, colors=col[::2], max_depth=MAX_DEPTH)     # non-contiguous: taken as it reads
     assert out.depth.shape == (3, 1, 17, 23) and out.colors.shape == (3, 3, 17, 23) and out.normal is None
+
+
+# ---- memory discipline ------------------------------------------------------------------------------------------------- #
+def test_memory_discipline():
+    """render_surfels under tests/guarded.py, 500 discs (a third with random normals, a seventh with none) in 37 views of 17 x 23 with
+    per-frame intrinsics: points, normals, colours, intrinsics and poses between guard bands; the scratch (colvo_render_scratch_bytes),
+    depth, index, colours, the normal planes and the statistics from the pool under both poisons.  Outputs equal the replica, are the
+    same bytes under either poison, and no guard byte changes.  Launches reached: the clearing of the keys, the disc kernel (three frame
+    groups, the last ragged; culled, flat and clipped points) and the resolve with colours and normals."""
+    from coivo_amd import _lib, inference as I
+    from tests import guarded as G
+    H, W = 17, 23
+    _, K, M = _cams(37, H, W, per_frame_K=True)
+    pts, nrm = _frustum_points(500, 7, K, M, H, W)
+    col = np.random.default_rng(3).random((500, 3), dtype=np.float32)
+    kw = dict(radius=0.04, max_splat=8, max_depth=MAX_DEPTH)
+    want = S.render(pts, nrm, K, M, H, W, colors=col, **kw)
+    assert want["stats"][:, 1].min() > 0 and want["stats"][:, 4].max() > 0 and want["stats"][:, 5].max() > 0
+    run = lambda pool: I.render_surfels(pool.place(_t(pts)), pool.place(_t(nrm)), pool.place(_t(K)), pool.place(_t(M)), H, W,
+                                        colors=pool.place(_t(col)), want_normals=True, **kw)
+    outs, pools = G.under_both_poisons(dev(), run, "render_surfels")
+    for got, pool in zip(outs, pools):
+        _assert_equal(got, want, "guarded")
+        G.assert_served(pool, 0, _lib.load().colvo_render_scratch_bytes(37, H, W), "render_surfels")

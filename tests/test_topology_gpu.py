@@ -292,3 +292,38 @@ def test_reconstruct_sequence_returns_the_topology_and_cleans():
     _same(rec.topology, I.mesh_topology(rec.mesh, unit=0.005))
     assert rec.topology.vertex_component.shape[0] == rec.mesh.vertices.shape[0] < raw.vertices.shape[0]
     assert int(rec.rendered.index.max()) < rec.mesh.faces.shape[0]
+
+
+# ---- 10. memory discipline -------------------------------------------------------------------------------------------------------------- #
+def test_memory_discipline():
+    """mesh_topology and clean_mesh under tests/guarded.py: inputs between guard bands, every tensor the wrappers allocate (the scratch of
+    colvo_mesh_topology_scratch_bytes / colvo_mesh_clean_scratch_bytes, the label arrays, the tables, the gathered mesh) from the pool
+    under both poisons.  Outputs equal the replica, are the same bytes under either poison, and no guard byte changes.
+    Launches reached: the hand mesh runs colvo_mesh_topology_components, _edges and _loops (4 loops, dead faces, a lone vertex); 5000
+    separate triangles take the roots and the loops past one scan chunk of 4096; clean_mesh(min_faces=5) on the thin tube's mesh runs
+    colvo_mesh_clean_plan and colvo_mesh_clean_write with colours."""
+    from coivo_amd import _lib, inference as I
+    from tests import guarded as G
+    lib = _lib.load()
+    for name, (v, f), unit in (("hand mesh", _hand_mesh(), 0.25), ("5000 triangles", T.separate_triangles(5000), 1.0)):
+        want = T.mesh_topology(v, f, unit)
+        outs, pools = G.under_both_poisons(dev(), lambda pool: I.mesh_topology(pool.place(_t(v)), pool.place(_t(f)), unit=unit),
+                                           f"mesh_topology {name}")
+        for got, pool in zip(outs, pools):
+            _assert_topology(got, want, name)
+            G.assert_served(pool, 0, lib.colvo_mesh_topology_scratch_bytes(len(v), len(f)), name)
+    scene = _scene("thin")
+    wm = scene[0]
+    want = T.clean_mesh(wm, T.mesh_topology(wm["vertices"], wm["faces"], 0.1), min_faces=5)
+    mesh = _gpu_mesh(scene)
+    topo = I.mesh_topology(mesh, unit=0.1)
+    assert mesh.colors is not None and 0 < len(want["faces"]) < len(wm["faces"])
+    outs, pools = G.under_both_poisons(dev(), lambda pool: I.clean_mesh(pool.place_tree(mesh), pool.place_tree(topo), min_faces=5),
+                                       "clean_mesh")
+    for got, pool in zip(outs, pools):
+        G.assert_served(pool, 0, lib.colvo_mesh_clean_scratch_bytes(mesh.vertices.shape[0], mesh.faces.shape[0]), "clean_mesh")
+        for g, k in ((got.kept, "kept"), (got.vertex_index, "vertex_index"), (got.face_index, "face_index"), (got.mesh.faces, "faces"),
+                     (got.mesh.cells, "cells")):
+            assert torch.equal(g.cpu(), torch.from_numpy(want[k])), k
+        for k in ("vertices", "normals", "colors"):
+            assert torch.equal(_bits(getattr(got.mesh, k)).cpu(), _bits(torch.from_numpy(want[k]))), k

@@ -265,3 +265,37 @@ def test_reconstruct_sequence_also_meshes():
     want = I.extract_mesh(vol, min_obs=2)
     assert isinstance(rec.mesh, I.Mesh) and rec.mesh.vertices.shape[0] > 0 and rec.mesh.faces.shape[0] > 0 and rec.mesh.colors is not None
     _same(rec.mesh, want)
+
+
+# ---- 8. memory discipline ---------------------------------------------------------------------------------------------------------- #
+@pytest.mark.parametrize("case", ["tube_5x17x23_colours", "more_bricks_than_one_scan_chunk"])
+def test_memory_discipline(case):
+    """fuse_tsdf and extract_mesh under tests/guarded.py: depths, colours, intrinsics and poses between guard bands; the plan's scratch
+    (colvo_tsdf_plan_scratch_bytes), the table, the brick list, the voxel pool, the colour sums, the meshing scratch
+    (colvo_tsdf_mesh_scratch_bytes), the vertex ids and every output from the pool under both poisons.  Volume and mesh equal the
+    replica, are the same bytes under either poison, and no guard byte changes.  Launches reached: colvo_tsdf_plan, colvo_tsdf_integrate
+    (with colours in the first case), colvo_tsdf_mesh_count, _vertices and _faces; the second case's 4096+ bricks take the plan's and
+    the meshing's scans past one chunk."""
+    from coivo_amd import _lib, inference as I
+    from tests import guarded as G
+    lib = _lib.load()
+    if case == "tube_5x17x23_colours":
+        (depths, colors, K, M), voxel, trunc, stride, min_obs = _tube(5, 17, 23), 0.1, None, 2, 2
+    else:
+        (depths, _, K, M), colors, voxel, trunc, stride, min_obs = _tube(3, 32, 40), None, 0.01, 7 * 0.01, 1, 1
+    N, H, W = depths.shape[0], depths.shape[-2], depths.shape[-1]
+    origin, dims = _default_grid(K, M, H, W, voxel)
+    kw = dict(voxel_size=voxel, trunc=trunc, stride=stride, max_depth=MAX_DEPTH)
+    want = R.fuse_tsdf(depths, K, M, colors=colors, origin=origin, dims=dims, **kw)
+    wm = R.extract_mesh(want, min_obs=min_obs)
+    assert len(wm["faces"]) > 50 and (case.startswith("tube") or want["n_bricks"] > 4096)
+
+    def run(pool):
+        vol = I.fuse_tsdf(pool.place(_t(depths)), pool.place(_t(K)), pool.place(_t(M)), colors=pool.place(_t(colors)), **kw)
+        return vol, I.extract_mesh(vol, min_obs=min_obs)
+    outs, pools = G.under_both_poisons(dev(), run, case)
+    for (vol, mesh), pool in zip(outs, pools):
+        _assert_volume(vol, want, case)
+        _assert_mesh(mesh, wm, case)
+        G.assert_served(pool, 0, lib.colvo_tsdf_plan_scratch_bytes(N, H, W, stride, *dims), case + " plan")
+        G.assert_served(pool, 0, lib.colvo_tsdf_mesh_scratch_bytes(want["n_bricks"]), case + " mesh")
