@@ -280,6 +280,13 @@ def ptr(t) -> int:
     return 0 if t is None else t.data_ptr()
 
 
+def call(name: str, *args) -> None:
+    """lib.<name>(*args) for an entry that returns a status: a torch tensor goes as its device pointer, None as NULL, everything else
+    as it is; a non-zero status raises through check() under the same name.  Not for the training path: it looks at every argument."""
+    import torch
+    check(getattr(load(), name)(*(a.data_ptr() if isinstance(a, torch.Tensor) else 0 if a is None else a for a in args)), name)
+
+
 def stream_ptr() -> int:
     """hipStream_t of torch's current stream on the current device (the raw C call: torch.cuda.current_stream() builds a
     Python Stream object through four layers of device-index helpers, ~10 us a call and nine calls a step)."""

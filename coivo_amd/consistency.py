@@ -62,7 +62,6 @@ def filter_depths(depths: torch.Tensor, K: torch.Tensor, cam2world: torch.Tensor
     out = torch.empty(N, 1, H, W, device=dev, dtype=torch.float32)
     votes = torch.empty(N, 3, H, W, device=dev, dtype=torch.uint8)
     stats = torch.empty(N, 5, device=dev, dtype=torch.int32)
-    _lib.check(lib.colvo_consistency_filter(_lib.ptr(depths), _lib.ptr(K), _lib.ptr(cam2world), N, H, W, window, min(step, 1 << 30),
-                                            float(rel_tol), min_agree, max_violated, float(max_depth), _lib.ptr(ws), _lib.ptr(out),
-                                            _lib.ptr(votes), _lib.ptr(stats), _lib.stream_ptr()), "colvo_consistency_filter")
+    _lib.call("colvo_consistency_filter", depths, K, cam2world, N, H, W, window, min(step, 1 << 30), float(rel_tol), min_agree,
+              max_violated, float(max_depth), ws, out, votes, stats, _lib.stream_ptr())
     return ConsistencyResult(out, votes, stats)

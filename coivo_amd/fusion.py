@@ -7,7 +7,7 @@ from typing import NamedTuple, Optional, Tuple
 import torch
 
 from . import _lib
-from ._args import MAX_DEPTH, depth_views, device_f32, f32, finite_pos32, frames_shape, int_range, voxel_grid
+from ._args import MAX_DEPTH, Mesh, depth_views, device_f32, f32, finite_pos32, frames_shape, int_range, voxel_grid
 
 
 class FusedCloud(NamedTuple):
@@ -76,8 +76,7 @@ def fuse_point_cloud(depths: torch.Tensor, K: torch.Tensor, cam2world: torch.Ten
     ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
     stats = torch.empty(3, device=dev, dtype=torch.int32)
     stream = _lib.stream_ptr()
-    _lib.check(lib.colvo_fuse_plan(_lib.ptr(depths), _lib.ptr(K), _lib.ptr(cam2world), *geom, _lib.ptr(ws), _lib.ptr(stats),
-                                   stream), "colvo_fuse_plan")
+    _lib.call("colvo_fuse_plan", depths, K, cam2world, *geom, ws, stats, stream)
     n_input, n_outside, n_bricks = (int(v) for v in stats.tolist())
     n_voxels = m = 0
     if n_bricks > 0:
@@ -85,12 +84,10 @@ def fuse_point_cloud(depths: torch.Tensor, K: torch.Tensor, cam2world: torch.Ten
         if pool_bytes == 0:
             raise RuntimeError(f"{who}: {n_bricks} occupied bricks, the limit is 2^22 - 1: use a larger voxel_size")
         pool = torch.empty(pool_bytes, device=dev, dtype=torch.uint8)
-        _lib.check(lib.colvo_fuse_accumulate(_lib.ptr(depths), _lib.ptr(colors), _lib.ptr(K), _lib.ptr(cam2world), *geom,
-                                             _lib.ptr(ws), n_bricks, _lib.ptr(pool), stream), "colvo_fuse_accumulate")
+        _lib.call("colvo_fuse_accumulate", depths, colors, K, cam2world, *geom, ws, n_bricks, pool, stream)
         ews = torch.empty(int(lib.colvo_fuse_extract_workspace_bytes(n_bricks)), device=dev, dtype=torch.uint8)
         stats2 = torch.empty(3, device=dev, dtype=torch.int32)
-        _lib.check(lib.colvo_fuse_count(_lib.ptr(pool), n_bricks, min_obs, _lib.ptr(ews), _lib.ptr(stats2), stream),
-                   "colvo_fuse_count")
+        _lib.call("colvo_fuse_count", pool, n_bricks, min_obs, ews, stats2, stream)
         n_voxels, m, overflow = (int(v) for v in stats2.tolist())
         if overflow:
             raise RuntimeError(f"{who}: overflow: a voxel received 2^24 or more samples (its 32-bit sums may have "
@@ -100,9 +97,7 @@ def fuse_point_cloud(depths: torch.Tensor, K: torch.Tensor, cam2world: torch.Ten
     counts = torch.empty(m, device=dev, dtype=torch.int32)
     voxels = torch.empty(m, 3, device=dev, dtype=torch.int32)
     if m > 0:
-        _lib.check(lib.colvo_fuse_write(_lib.ptr(ws), _lib.ptr(pool), n_bricks, min_obs, *origin, vs, *dims, _lib.ptr(ews),
-                                        m, _lib.ptr(points), _lib.ptr(out_colors), _lib.ptr(counts), _lib.ptr(voxels), stream),
-                   "colvo_fuse_write")
+        _lib.call("colvo_fuse_write", ws, pool, n_bricks, min_obs, *origin, vs, *dims, ews, m, points, out_colors, counts, voxels, stream)
     return FusedCloud(points, out_colors, counts, voxels, origin, dims, vs, n_input, n_outside, n_bricks, n_voxels)
 
 
@@ -119,15 +114,6 @@ class TsdfVolume(NamedTuple):
     n_input: int                    # walked samples with 0 < depth < max_depth
     n_outside: int                  # ... of which outside the grid
     n_bricks: int                   # allocated 8x8x8 bricks
-
-
-class Mesh(NamedTuple):
-    vertices: torch.Tensor          # [V,3] float32: one per active cell, in (brick, voxel in brick) order of the cell's minimum corner
-    faces: torch.Tensor             # [F,3] int32: triangles, wound so that the normal points to free space (the camera side)
-    colors: Optional[torch.Tensor]  # [V,3] float32 in [0,1] (None without colours)
-    normals: torch.Tensor           # [V,3] float32: unit gradient of the distance field, towards free space; 0 for a zero gradient
-    cells: torch.Tensor             # [V,3] int32: the cell (ix, iy, iz) of each vertex
-    n_open: int                     # cells with a sign change among their observed corners and one or more corners not observed
 
 
 class _MeshingFields(NamedTuple):
@@ -207,18 +193,16 @@ def fuse_tsdf(depths: torch.Tensor, K: torch.Tensor, cam2world: torch.Tensor, *,
     brick_list = torch.empty(min(total, 1 << 22), device=dev, dtype=torch.int32)
     stats = torch.empty(3, device=dev, dtype=torch.int32)
     stream = _lib.stream_ptr()
-    _lib.check(lib.colvo_tsdf_plan(_lib.ptr(depths), _lib.ptr(K), _lib.ptr(cam2world), N, H, W, stride, float(max_depth), *origin, vs,
-                                   *dims, T, _lib.ptr(scratch), _lib.ptr(table), _lib.ptr(brick_list), _lib.ptr(stats), stream),
-               "colvo_tsdf_plan")
+    _lib.call("colvo_tsdf_plan", depths, K, cam2world, N, H, W, stride, float(max_depth), *origin, vs, *dims, T, scratch, table,
+              brick_list, stats, stream)
     n_input, n_outside, n_bricks = (int(v) for v in stats.tolist())
     if n_bricks >= 1 << 22:
         raise RuntimeError(f"{who}: {n_bricks} allocated bricks, the limit is 2^22 - 1: use a larger voxel_size")
     pool = torch.empty(n_bricks * 512, 2, device=dev, dtype=torch.int32)
     sums = torch.empty(n_bricks * 512, 4, device=dev, dtype=torch.int32) if colors is not None else None
     if n_bricks > 0:
-        _lib.check(lib.colvo_tsdf_integrate(_lib.ptr(depths), _lib.ptr(colors), _lib.ptr(K), _lib.ptr(cam2world), N, H, W,
-                                            float(max_depth), *origin, vs, *dims, T, _lib.ptr(brick_list), n_bricks, _lib.ptr(pool),
-                                            _lib.ptr(sums), 0, stream), "colvo_tsdf_integrate")
+        _lib.call("colvo_tsdf_integrate", depths, colors, K, cam2world, N, H, W, float(max_depth), *origin, vs, *dims, T, brick_list,
+                  n_bricks, pool, sums, 0, stream)
     return TsdfVolume(pool, sums, brick_list[:n_bricks], table, origin, dims, vs, f32(f32(T) * vs), colors is not None, n_input,
                       n_outside, n_bricks)
 
@@ -253,9 +237,8 @@ def extract_mesh(volume: TsdfVolume, *, min_obs: int = 1) -> Mesh:
             raise ValueError(f"{who}: n_bricks {n_bricks} beyond the kernels' limits")
         scratch = torch.empty(scratch_bytes, device=dev, dtype=torch.uint8)
         stats2 = torch.empty(3, device=dev, dtype=torch.int32)
-        bricks = (_lib.ptr(volume.table), _lib.ptr(volume.brick_list), n_bricks)
-        _lib.check(lib.colvo_tsdf_mesh_count(_lib.ptr(volume.pool), *bricks, min_obs, *dims, _lib.ptr(scratch), _lib.ptr(stats2),
-                                             stream), "colvo_tsdf_mesh_count")
+        bricks = (volume.table, volume.brick_list, n_bricks)
+        _lib.call("colvo_tsdf_mesh_count", volume.pool, *bricks, min_obs, *dims, scratch, stats2, stream)
         V, n_open = (int(v) for v in stats2[:2].tolist())
     vertices = torch.empty(V, 3, device=dev, dtype=torch.float32)
     normals = torch.empty(V, 3, device=dev, dtype=torch.float32)
@@ -263,15 +246,12 @@ def extract_mesh(volume: TsdfVolume, *, min_obs: int = 1) -> Mesh:
     cells = torch.empty(V, 3, device=dev, dtype=torch.int32)
     if V > 0:
         vid = torch.empty(n_bricks * 512, device=dev, dtype=torch.int32)
-        _lib.check(lib.colvo_tsdf_mesh_vertices(_lib.ptr(volume.pool), _lib.ptr(volume.color_sums), *bricks, min_obs, *origin, vs,
-                                                *dims, _lib.ptr(scratch), V, _lib.ptr(vertices), _lib.ptr(colors), _lib.ptr(normals),
-                                                _lib.ptr(cells), _lib.ptr(vid), stats2[2:].data_ptr(), stream),
-                   "colvo_tsdf_mesh_vertices")
+        _lib.call("colvo_tsdf_mesh_vertices", volume.pool, volume.color_sums, *bricks, min_obs, *origin, vs, *dims, scratch, V, vertices,
+                  colors, normals, cells, vid, stats2[2:], stream)
         F = int(stats2[2].item())
     faces = torch.empty(F, 3, device=dev, dtype=torch.int32)
     if F > 0:
-        _lib.check(lib.colvo_tsdf_mesh_faces(_lib.ptr(volume.pool), *bricks, *dims, _lib.ptr(scratch), _lib.ptr(vid), F,
-                                             _lib.ptr(faces), stream), "colvo_tsdf_mesh_faces")
+        _lib.call("colvo_tsdf_mesh_faces", volume.pool, *bricks, *dims, scratch, vid, F, faces, stream)
     return Mesh(vertices, faces, colors, normals, cells, n_open)
 
 
@@ -319,8 +299,6 @@ def cloud_normals(fused: FusedCloud, depths: torch.Tensor, K: torch.Tensor, cam2
     counts = torch.empty(m, device=dev, dtype=torch.int32)
     coherence = torch.empty(m, device=dev, dtype=torch.float32)
     stats = torch.empty(4, device=dev, dtype=torch.int32)
-    _lib.check(lib.colvo_cloud_normals(_lib.ptr(depths), _lib.ptr(K), _lib.ptr(cam2world), N, H, W, stride, float(max_depth), *origin,
-                                       vs, *dims, _lib.ptr(voxels), m, float(rel_edge), _lib.ptr(scratch), _lib.ptr(normals),
-                                       _lib.ptr(counts), _lib.ptr(coherence), _lib.ptr(stats), _lib.stream_ptr()),
-               "colvo_cloud_normals")
+    _lib.call("colvo_cloud_normals", depths, K, cam2world, N, H, W, stride, float(max_depth), *origin, vs, *dims, voxels, m,
+              float(rel_edge), scratch, normals, counts, coherence, stats, _lib.stream_ptr())
     return CloudNormals(normals, counts, coherence, stats)

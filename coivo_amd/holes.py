@@ -6,9 +6,8 @@ from typing import NamedTuple
 import torch
 
 from . import _lib
-from ._args import device_f32, int_range
-from .fusion import Mesh
-from .topology import MeshTopology, _mesh_arrays
+from ._args import Mesh, int_range, mesh_arrays, mesh_attributes, own_topology
+from .topology import MeshTopology
 
 FILLED, TOO_LONG, NOT_SIMPLE, UNMEASURED = 0, 1, 2, 3
 MAX_VERTICES = (1 << 30) - 1
@@ -60,14 +59,11 @@ def fill_holes(mesh: Mesh, topology: MeshTopology, *, max_edges: int) -> HoleFil
     if not isinstance(topology, MeshTopology):
         raise ValueError(f"{who}: topology must be a MeshTopology (mesh_topology of this mesh)")
     int_range(who, "max_edges", max_edges, 3, (1 << 31) - 1)
-    vertices, faces, V, F = _mesh_arrays(who, mesh, None)
+    vertices, faces, V, F = mesh_arrays(who, mesh, None)
     dev = vertices.device
+    own_topology(who, topology, V, F, dev, ("loops",))
     loops, vertex_loop = topology.loops, topology.vertex_loop
     L = int(loops.shape[0])
-    if tuple(vertex_loop.shape) != (V,) or tuple(topology.face_component.shape) != (F,) or loops.device != dev or loops.dim() != 2 \
-            or loops.shape[1] != 4 or loops.dtype != torch.int64 or vertex_loop.dtype != torch.int32 or vertex_loop.device != dev \
-            or (L > 0 and (V == 0 or F == 0)):
-        raise ValueError(f"{who}: topology is not this mesh's (V = {V}, F = {F} on {dev})")
     if V > MAX_VERTICES:
         raise ValueError(f"{who}: V = {V} beyond the kernels' limit (V < 2^30)")
     unit = float(topology.unit)
@@ -77,12 +73,7 @@ def fill_holes(mesh: Mesh, topology: MeshTopology, *, max_edges: int) -> HoleFil
     if V == 0 or L == 0:                    # nothing to launch: the mesh comes back as it is
         return HoleFill(mesh, status, hole, torch.zeros(L + 1, **i32), torch.empty(0, **i32), torch.full((F,), -1, **i32),
                         torch.empty(0, **i32), unit)
-    colors = None if mesh.colors is None else device_f32(who, "mesh.colors", mesh.colors, (V, 3))
-    normals = device_f32(who, "mesh.normals", mesh.normals, (V, 3))
-    cells = mesh.cells
-    if not isinstance(cells, torch.Tensor) or cells.dtype != torch.int32 or tuple(cells.shape) != (V, 3) or cells.device != dev:
-        raise ValueError(f"{who}: mesh.cells must be [V,3] int32 on the device of the vertices")
-    cells = cells.contiguous()
+    colors, normals, cells = mesh_attributes(who, mesh, V, dev)
     loops, vertex_loop = loops.contiguous(), vertex_loop.contiguous()
     lib = _lib.load()
     stream = _lib.stream_ptr()
@@ -90,9 +81,8 @@ def fill_holes(mesh: Mesh, topology: MeshTopology, *, max_edges: int) -> HoleFil
     ring_offsets = torch.empty(L + 1, **i32)
     ring_vertices = torch.empty(V, **i32)
     counts = torch.empty(8, **i32)
-    _lib.check(lib.colvo_mesh_fill_plan(_lib.ptr(vertices), _lib.ptr(faces), _lib.ptr(colors), V, F, L, unit, max_edges,
-                                        _lib.ptr(vertex_loop), _lib.ptr(loops), _lib.ptr(scratch), _lib.ptr(status), _lib.ptr(hole),
-                                        _lib.ptr(ring_offsets), _lib.ptr(ring_vertices), _lib.ptr(counts), stream), "colvo_mesh_fill_plan")
+    _lib.call("colvo_mesh_fill_plan", vertices, faces, colors, V, F, L, unit, max_edges, vertex_loop, loops, scratch, status, hole,
+              ring_offsets, ring_vertices, counts, stream)
     R, n_v, n_f, _, gave_up, _, _, mismatch = (int(c) for c in counts.tolist())
     if mismatch != 0:
         raise RuntimeError(f"{who}: topology is not this mesh's: its loops do not match the mesh's boundary half-edges")
@@ -107,10 +97,8 @@ def fill_holes(mesh: Mesh, topology: MeshTopology, *, max_edges: int) -> HoleFil
     out_faces = torch.empty(F + n_f, 3, **i32)
     face_loop = torch.empty(F + n_f, **i32)
     new_vertex_loop = torch.empty(n_v, **i32)
-    _lib.check(lib.colvo_mesh_fill_write(_lib.ptr(vertices), _lib.ptr(colors), _lib.ptr(normals), _lib.ptr(cells), _lib.ptr(faces), V, F, L,
-                                         R, n_v, n_f, _lib.ptr(scratch), _lib.ptr(vertex_loop), _lib.ptr(status), _lib.ptr(ring_offsets),
-                                         _lib.ptr(ring_vertices), _lib.ptr(out_vertices), _lib.ptr(out_colors), _lib.ptr(out_normals),
-                                         _lib.ptr(out_cells), _lib.ptr(out_faces), _lib.ptr(face_loop),
-                                         _lib.ptr(new_vertex_loop) if n_v > 0 else 0, stream), "colvo_mesh_fill_write")
+    _lib.call("colvo_mesh_fill_write", vertices, colors, normals, cells, faces, V, F, L, R, n_v, n_f, scratch, vertex_loop, status,
+              ring_offsets, ring_vertices, out_vertices, out_colors, out_normals, out_cells, out_faces, face_loop,
+              new_vertex_loop if n_v > 0 else 0, stream)
     return HoleFill(Mesh(out_vertices, out_faces, out_colors, out_normals, out_cells, mesh.n_open), status, hole, ring_offsets,
                     ring_vertices[:R].clone(), face_loop, new_vertex_loop, unit)      # (a clone: a view would keep all V entries alive)

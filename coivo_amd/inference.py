@@ -20,7 +20,7 @@ from typing import NamedTuple, Optional
 import torch
 
 from . import _lib, localize
-from ._args import MAX_DEPTH, depth_views, f32 as _f32, int_range, per_view_K      # (_f32: tools and tests round a voxel size with it)
+from ._args import MAX_DEPTH, depth_views, int_range, per_view_K
 from .consistency import Consistency, ConsistencyResult, check_consistency, filter_depths
 from .holes import HoleFill, fill_holes
 from .fusion import (CloudNormals, FusedCloud, Mesh, Meshing, TsdfVolume, cloud_normals, extract_mesh, fuse_point_cloud, fuse_tsdf,
@@ -63,11 +63,9 @@ def integrate_trajectory(rel_poses: torch.Tensor) -> torch.Tensor:
 
 def backproject(depth: torch.Tensor, K: torch.Tensor, cam2world: torch.Tensor) -> torch.Tensor:
     """depth [B,1,H,W], K [B,3,3], cam2world [B,4,4] -> world points [B,H*W,3] (spec: backproject)."""
-    lib = _lib.load()
     depth, K, cam2world, B, H, W = depth_views("backproject", depth, K, cam2world, name="depth")
     points = torch.empty(B, H * W, 3, device=depth.device, dtype=torch.float32)
-    _lib.check(lib.colvo_backproject(_lib.ptr(depth), _lib.ptr(K), _lib.ptr(cam2world), B, H, W, _lib.ptr(points),
-                                     _lib.stream_ptr()), "colvo_backproject")
+    _lib.call("colvo_backproject", depth, K, cam2world, B, H, W, points, _lib.stream_ptr())
     return points
 
 
@@ -83,9 +81,7 @@ def stitch_point_cloud(depths: torch.Tensor, K: torch.Tensor, cam2world: torch.T
     ws = torch.empty(int(lib.colvo_stitch_workspace_ints(N, H, W, stride)), device=depths.device, dtype=torch.int32)
     count = torch.empty(1, device=depths.device, dtype=torch.int32)
     points = torch.empty(cap, 3, device=depths.device, dtype=torch.float32)
-    _lib.check(lib.colvo_stitch_point_cloud(_lib.ptr(depths), _lib.ptr(K), _lib.ptr(cam2world), N, H, W, stride,
-                                            float(max_depth), _lib.ptr(ws), _lib.ptr(points), _lib.ptr(count),
-                                            _lib.stream_ptr()), "colvo_stitch_point_cloud")
+    _lib.call("colvo_stitch_point_cloud", depths, K, cam2world, N, H, W, stride, float(max_depth), ws, points, count, _lib.stream_ptr())
     return points[: int(count.item())]
 
 

@@ -29,8 +29,8 @@ from typing import NamedTuple, Optional
 import torch
 
 from . import _lib
-from . import evaluate
 from ._args import MAX_DEPTH, depth_views, f32
+from .trajectory import align_trajectory
 
 
 class PolypLocalization(NamedTuple):
@@ -114,22 +114,19 @@ def localize_polyps(depths: torch.Tensor, labels: torch.Tensor, K: torch.Tensor,
     geom = (N, H, W, int(stride), float(max_depth), L)
 
     def accumulate(bounds):
-        _lib.check(lib.colvo_localize_accumulate(_lib.ptr(depths), _lib.ptr(labels), _lib.ptr(K), *geom, _lib.ptr(bounds),
-                                                 _lib.ptr(records), stream), "colvo_localize_accumulate")
+        _lib.call("colvo_localize_accumulate", depths, labels, K, *geom, bounds, records, stream)
 
     accumulate(None)
     if clip_sigma is not None:
         bounds = torch.empty(N, L, 2, device=dev, dtype=torch.float64)
-        _lib.check(lib.colvo_localize_bounds(_lib.ptr(records), N, L, float(clip_sigma), _lib.ptr(bounds), stream),
-                   "colvo_localize_bounds")
+        _lib.call("colvo_localize_bounds", records, N, L, float(clip_sigma), bounds, stream)
         accumulate(bounds)
     i32 = lambda *s: torch.empty(*s, device=dev, dtype=torch.int32)
     f64 = lambda *s: torch.empty(*s, device=dev, dtype=torch.float64)
     obs = (i32(N, L), i32(N, L), i32(N, L, 4), f64(N, L, 2), f64(N, L, 3), f64(N, L, 6), f64(N, L, 3))
     per = (i32(L), torch.empty(L, device=dev, dtype=torch.int64), i32(L), i32(L), f64(L, 3), f64(L, 6))
     stats = torch.empty(2, device=dev, dtype=torch.int64)
-    _lib.check(lib.colvo_localize_finish(_lib.ptr(records), _lib.ptr(cam2world), N, L, int(min_samples), *(_lib.ptr(t) for t in obs),
-                                         *(_lib.ptr(t) for t in per), _lib.ptr(stats), stream), "colvo_localize_finish")
+    _lib.call("colvo_localize_finish", records, cam2world, N, L, int(min_samples), *obs, *per, stats, stream)
     n_labelled, n_ignored = (int(v) for v in stats.tolist())
     # the square root is taken on the host, one correctly rounded math.sqrt per polyp: no device or vectorised sqrt enters a result
     trace = [(c[0] + c[3]) + c[5] for c in per[5].tolist()]
@@ -153,7 +150,7 @@ def localization_error(pred_positions, gt_positions, pred_cam2world=None, gt_cam
             raise ValueError(f'localization_error: without trajectories there is nothing to align: mode must be "none", got {mode!r}')
         aligned = P
     else:
-        R, t, s = evaluate.align_trajectory(pred_cam2world, gt_cam2world, mode)
+        R, t, s = align_trajectory(pred_cam2world, gt_cam2world, mode)
         aligned = s * (P @ R.t()) + t
     d = G - aligned
     return torch.sqrt((d * d).sum(dim=1))

@@ -1,13 +1,12 @@
 """Trajectory refinement by dense depth and intensity alignment (csrc/refine.hip): refine_edges / refine_trajectory
 correct the trajectory against the depth maps and frames it connects.  coivo_amd.inference re-exports every name here.
 """
-import math
 from typing import NamedTuple, Optional
 
 import torch
 
 from . import _lib
-from ._args import MAX_DEPTH, depth_views, device_f32, finite_pos32, int_range
+from ._args import MAX_DEPTH, depth_views, device_f32, finite_nonneg64, finite_pos32, int_range
 
 
 class Refinement(NamedTuple):
@@ -43,12 +42,7 @@ def check_refinement(who: str, policy: Refinement, max_depth) -> int:
     for name in ("sigma_geo", "sigma_photo", "gate_geo", "gate_photo"):
         finite_pos32(who, name, getattr(policy, name))
     finite_pos32(who, "max_depth", max_depth)
-    try:                                                         # (damping is a double in the C ABI: judged in float64)
-        ok = math.isfinite(float(policy.damping)) and float(policy.damping) >= 0.0
-    except (TypeError, ValueError):
-        ok = False
-    if not ok:
-        raise ValueError(f"{who}: damping must be finite and >= 0, got {policy.damping!r}")
+    finite_nonneg64(who, "damping", policy.damping)              # (damping is a double in the C ABI: judged in float64)
     for name in ("geometric", "photometric", "brightness"):
         if not isinstance(getattr(policy, name), (bool, int)):
             raise ValueError(f"{who}: {name} must be a bool, got {getattr(policy, name)!r}")
@@ -105,10 +99,8 @@ def refine_accumulate(depths: torch.Tensor, frames: torch.Tensor, K: torch.Tenso
     ws = torch.empty(int(lib.colvo_refine_workspace_bytes(E, N, H, W, 1)), device=dev, dtype=torch.uint8)
     sums = torch.empty(E, 48, device=dev, dtype=torch.float64)
     counts = torch.empty(E, 4, device=dev, dtype=torch.int32)
-    _lib.check(lib.colvo_refine_accumulate(_lib.ptr(depths), _lib.ptr(frames), _lib.ptr(K), N, H, W, _lib.ptr(edges), E, _lib.ptr(T),
-                                           _lib.ptr(gain), _lib.ptr(offset), float(sigma_geo), float(sigma_photo), float(gate_geo),
-                                           float(gate_photo), terms, float(max_depth), _lib.ptr(ws), _lib.ptr(sums), _lib.ptr(counts),
-                                           _lib.stream_ptr()), "colvo_refine_accumulate")
+    _lib.call("colvo_refine_accumulate", depths, frames, K, N, H, W, edges, E, T, gain, offset, float(sigma_geo), float(sigma_photo),
+              float(gate_geo), float(gate_photo), terms, float(max_depth), ws, sums, counts, _lib.stream_ptr())
     return sums, counts
 
 
@@ -138,10 +130,9 @@ def refine_edges(depths: torch.Tensor, frames: torch.Tensor, K: torch.Tensor, ed
     offset = torch.empty(E, device=dev, dtype=torch.float64)
     history = torch.empty(E, iterations + 1, 5, device=dev, dtype=torch.float64)
     status = torch.empty(E, device=dev, dtype=torch.int32)
-    _lib.check(lib.colvo_refine_edges(_lib.ptr(depths), _lib.ptr(frames), _lib.ptr(K), N, H, W, _lib.ptr(edges), E, _lib.ptr(T_init),
-                                      iterations, float(sigma_geo), float(sigma_photo), float(gate_geo), float(gate_photo),
-                                      float(damping), min_samples, terms, float(max_depth), _lib.ptr(ws), _lib.ptr(T), _lib.ptr(gain),
-                                      _lib.ptr(offset), _lib.ptr(history), _lib.ptr(status), _lib.stream_ptr()), "colvo_refine_edges")
+    _lib.call("colvo_refine_edges", depths, frames, K, N, H, W, edges, E, T_init, iterations, float(sigma_geo), float(sigma_photo),
+              float(gate_geo), float(gate_photo), float(damping), min_samples, terms, float(max_depth), ws, T, gain, offset, history,
+              status, _lib.stream_ptr())
     return RefinementResult(T, gain, offset, history, status)
 
 

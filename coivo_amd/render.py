@@ -103,10 +103,8 @@ def render_cloud(points: torch.Tensor, K: torch.Tensor, cam2world: torch.Tensor,
     who = "render_cloud"
     points, colors, K, cam2world, M, N = _check_cloud(who, points, colors, K, cam2world, H, W, radius, max_splat, max_depth)
     scratch, depth, index, out_colors, _, stats = _outputs(points.device, N, H, W, 4, colors is not None, False)
-    _lib.check(_lib.load().colvo_render_cloud(_lib.ptr(points), _lib.ptr(colors), M, _lib.ptr(K), _lib.ptr(cam2world), N, H, W,
-                                              float(radius), max_splat, float(max_depth), _lib.ptr(scratch), _lib.ptr(depth),
-                                              _lib.ptr(index), _lib.ptr(out_colors), _lib.ptr(stats), _lib.stream_ptr()),
-               "colvo_render_cloud")
+    _lib.call("colvo_render_cloud", points, colors, M, K, cam2world, N, H, W, float(radius), max_splat, float(max_depth), scratch, depth,
+              index, out_colors, stats, _lib.stream_ptr())
     return RenderedViews(depth, index, out_colors, stats)
 
 
@@ -136,10 +134,8 @@ def render_surfels(points: torch.Tensor, normals: torch.Tensor, K: torch.Tensor,
     points, colors, K, cam2world, M, N = _check_cloud(who, points, colors, K, cam2world, H, W, radius, max_splat, max_depth)
     normals = device_f32(who, "normals", normals, (M, 3))
     scratch, depth, index, out_colors, out_normal, stats = _outputs(points.device, N, H, W, 6, colors is not None, want_normals)
-    _lib.check(_lib.load().colvo_render_surfels(_lib.ptr(points), _lib.ptr(normals), _lib.ptr(colors), M, _lib.ptr(K),
-                                                _lib.ptr(cam2world), N, H, W, float(radius), max_splat, float(max_depth),
-                                                _lib.ptr(scratch), _lib.ptr(depth), _lib.ptr(index), _lib.ptr(out_colors),
-                                                _lib.ptr(out_normal), _lib.ptr(stats), _lib.stream_ptr()), "colvo_render_surfels")
+    _lib.call("colvo_render_surfels", points, normals, colors, M, K, cam2world, N, H, W, float(radius), max_splat, float(max_depth),
+              scratch, depth, index, out_colors, out_normal, stats, _lib.stream_ptr())
     return SurfelViews(depth, index, out_colors, out_normal, stats)
 
 
@@ -221,8 +217,6 @@ def render_mesh(mesh_or_vertices, faces: Optional[torch.Tensor] = None, K: Optio
     dev = vertices.device
     scratch, depth, index, out_colors, out_normal, stats = _outputs(dev, N, H, W, 8, colors is not None, want_normals)
     face_pixels = torch.empty(F, device=dev, dtype=torch.int32) if want_face_pixels else None
-    _lib.check(_lib.load().colvo_render_mesh(_lib.ptr(vertices), _lib.ptr(faces), _lib.ptr(colors), V, F, _lib.ptr(K),
-                                             _lib.ptr(cam2world), N, H, W, float(max_depth), int(cull_back), _lib.ptr(scratch),
-                                             _lib.ptr(depth), _lib.ptr(index), _lib.ptr(out_colors), _lib.ptr(out_normal),
-                                             _lib.ptr(face_pixels), _lib.ptr(stats), _lib.stream_ptr()), "colvo_render_mesh")
+    _lib.call("colvo_render_mesh", vertices, faces, colors, V, F, K, cam2world, N, H, W, float(max_depth), int(cull_back), scratch,
+              depth, index, out_colors, out_normal, face_pixels, stats, _lib.stream_ptr())
     return MeshViews(depth, index, out_colors, out_normal, stats, face_pixels)

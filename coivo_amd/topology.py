@@ -7,10 +7,7 @@ from typing import NamedTuple, Optional
 import torch
 
 from . import _lib
-from ._args import device_f32, finite_pos32, int_range
-from .fusion import Mesh
-
-MAX_FACES = (1 << 29) - 1
+from ._args import MAX_FACES, Mesh, finite_pos32, int_range, mesh_arrays, mesh_attributes, own_topology
 
 
 class MeshTopology(NamedTuple):
@@ -60,26 +57,6 @@ class CleanedMesh(NamedTuple):
     kept: torch.Tensor              # [C] bool: which components stayed
 
 
-def _mesh_arrays(who: str, mesh_or_vertices, faces):
-    if isinstance(mesh_or_vertices, Mesh):
-        if faces is not None:
-            raise ValueError(f"{who}: with a Mesh give no faces")
-        vertices, faces = mesh_or_vertices.vertices, mesh_or_vertices.faces
-    else:
-        vertices = mesh_or_vertices
-    if not isinstance(vertices, torch.Tensor) or vertices.dim() != 2 or vertices.shape[1] != 3:
-        raise ValueError(f"{who}: vertices must be [V,3]")
-    if not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int32:
-        raise ValueError(f"{who}: faces must be [F,3] int32")
-    V, F = int(vertices.shape[0]), int(faces.shape[0])
-    if V >= 1 << 31 or F > MAX_FACES:
-        raise ValueError(f"{who}: V = {V}, F = {F} beyond the kernels' limits (V < 2^31, F < 2^29)")
-    vertices = device_f32(who, "vertices", vertices, (V, 3))
-    if faces.device != vertices.device or not faces.is_contiguous():
-        raise ValueError(f"{who}: faces must be contiguous and on the device of vertices")
-    return vertices, faces, V, F
-
-
 def mesh_topology(mesh_or_vertices, faces: Optional[torch.Tensor] = None, *, unit: float) -> MeshTopology:
     """The topology of a triangle mesh -- `mesh_topology(mesh, unit=...)` with a Mesh, or vertices [V,3] float32 and faces [F,3] int32
     on the device (contract: include/colvo.h colvo_mesh_topology_*; csrc/topology.hip).  A face with an index outside
@@ -94,7 +71,7 @@ def mesh_topology(mesh_or_vertices, faces: Optional[torch.Tensor] = None, *, uni
     meant for meshes of bounded degree, as extract_mesh's are (12 at most).  No hole filling, no simplification."""
     who = "mesh_topology"
     unit = finite_pos32(who, "unit", unit)
-    vertices, faces, V, F = _mesh_arrays(who, mesh_or_vertices, faces)
+    vertices, faces, V, F = mesh_arrays(who, mesh_or_vertices, faces)
     dev = vertices.device
     i32 = dict(device=dev, dtype=torch.int32)
     components = torch.empty(0, 8, device=dev, dtype=torch.int64)
@@ -108,21 +85,18 @@ def mesh_topology(mesh_or_vertices, faces: Optional[torch.Tensor] = None, *, uni
     vertex_loop = torch.empty(V, **i32)
     stats = torch.empty(8, **i32)
     stream = _lib.stream_ptr()
-    _lib.check(lib.colvo_mesh_topology_components(_lib.ptr(faces), V, F, _lib.ptr(scratch), _lib.ptr(vertex_component),
-                                                  _lib.ptr(face_component), _lib.ptr(stats), stream), "colvo_mesh_topology_components")
+    _lib.call("colvo_mesh_topology_components", faces, V, F, scratch, vertex_component, face_component, stats, stream)
     C = int(stats[0].item())
     if not 1 <= C <= V:
         raise RuntimeError(f"{who}: {C} components of {V} vertices: the component pass failed")
     components = torch.empty(C, 8, device=dev, dtype=torch.int64)
-    _lib.check(lib.colvo_mesh_topology_edges(_lib.ptr(vertices), _lib.ptr(faces), V, F, unit, C, _lib.ptr(scratch),
-                                             _lib.ptr(vertex_component), _lib.ptr(face_component), _lib.ptr(components),
-                                             _lib.ptr(vertex_loop), _lib.ptr(stats), stream), "colvo_mesh_topology_edges")
+    _lib.call("colvo_mesh_topology_edges", vertices, faces, V, F, unit, C, scratch, vertex_component, face_component, components,
+              vertex_loop, stats, stream)
     L = int(stats[2].item())
     if L > 0:
         loops = torch.empty(L, 4, device=dev, dtype=torch.int64)
-        _lib.check(lib.colvo_mesh_topology_loops(_lib.ptr(vertices), V, F, unit, C, L, _lib.ptr(scratch), _lib.ptr(vertex_component),
-                                                 _lib.ptr(vertex_loop), _lib.ptr(components), _lib.ptr(loops), _lib.ptr(stats), stream),
-                   "colvo_mesh_topology_loops")
+        _lib.call("colvo_mesh_topology_loops", vertices, V, F, unit, C, L, scratch, vertex_component, vertex_loop, components, loops,
+                  stats, stream)
     st = stats.tolist()
     if st[5] != 0:
         raise RuntimeError(f"{who}: a thread exhausted the bound of a union-find loop (gave_up = {st[5]}): the result is not valid")
@@ -148,13 +122,11 @@ def clean_mesh(mesh: Mesh, topology: MeshTopology, *, min_faces: int = 1, min_ar
         raise ValueError(f"{who}: min_area must be finite and >= 0, got {min_area!r}")
     if largest is not None:
         int_range(who, "largest", largest, 1)
-    vertices, faces, V, F = _mesh_arrays(who, mesh, None)
+    vertices, faces, V, F = mesh_arrays(who, mesh, None)
     dev = vertices.device
     comp = topology.components
     C = int(comp.shape[0])
-    if tuple(topology.vertex_component.shape) != (V,) or tuple(topology.face_component.shape) != (F,) or comp.device != dev \
-            or (C == 0) != (V == 0):
-        raise ValueError(f"{who}: topology is not this mesh's (V = {V}, F = {F} on {dev})")
+    own_topology(who, topology, V, F, dev, ("components",))
     kept = (comp[:, 2] >= min_faces) & (topology.area >= float(min_area))
     if largest is not None and C > 0:
         key = torch.where(kept, comp[:, 2], torch.full_like(comp[:, 2], -1))
@@ -176,9 +148,7 @@ def clean_mesh(mesh: Mesh, topology: MeshTopology, *, min_faces: int = 1, min_ar
         face_index = torch.empty(F, **i32)
         counts = torch.empty(2, **i32)
         vc, fc = topology.vertex_component.contiguous(), topology.face_component.contiguous()
-        _lib.check(lib.colvo_mesh_clean_plan(_lib.ptr(vc), _lib.ptr(fc), _lib.ptr(kept8), V, F, C, _lib.ptr(scratch), _lib.ptr(vertex_map),
-                                             _lib.ptr(vertex_index), _lib.ptr(face_index), _lib.ptr(counts), stream),
-                   "colvo_mesh_clean_plan")
+        _lib.call("colvo_mesh_clean_plan", vc, fc, kept8, V, F, C, scratch, vertex_map, vertex_index, face_index, counts, stream)
         V2, F2 = (int(v) for v in counts.tolist())
         vertex_index, face_index = vertex_index[:V2], face_index[:F2]
     out_vertices = torch.empty(V2, 3, device=dev, dtype=torch.float32)
@@ -187,14 +157,7 @@ def clean_mesh(mesh: Mesh, topology: MeshTopology, *, min_faces: int = 1, min_ar
     out_cells = torch.empty(V2, 3, **i32)
     out_faces = torch.empty(F2, 3, **i32)
     if V2 + F2 > 0:
-        colors = None if mesh.colors is None else device_f32(who, "mesh.colors", mesh.colors, (V, 3))
-        normals = device_f32(who, "mesh.normals", mesh.normals, (V, 3))
-        cells = mesh.cells
-        if not isinstance(cells, torch.Tensor) or cells.dtype != torch.int32 or tuple(cells.shape) != (V, 3) or cells.device != dev:
-            raise ValueError(f"{who}: mesh.cells must be [V,3] int32 on the device of the vertices")
-        cells = cells.contiguous()
-        _lib.check(lib.colvo_mesh_clean_write(_lib.ptr(vertices), _lib.ptr(colors), _lib.ptr(normals), _lib.ptr(cells), _lib.ptr(faces),
-                                              V, F, _lib.ptr(vertex_map), _lib.ptr(vertex_index), _lib.ptr(face_index), V2, F2,
-                                              _lib.ptr(out_vertices), _lib.ptr(out_colors), _lib.ptr(out_normals), _lib.ptr(out_cells),
-                                              _lib.ptr(out_faces), stream), "colvo_mesh_clean_write")
+        colors, normals, cells = mesh_attributes(who, mesh, V, dev)
+        _lib.call("colvo_mesh_clean_write", vertices, colors, normals, cells, faces, V, F, vertex_map, vertex_index, face_index, V2, F2,
+                  out_vertices, out_colors, out_normals, out_cells, out_faces, stream)
     return CleanedMesh(Mesh(out_vertices, out_faces, out_colors, out_normals, out_cells, mesh.n_open), vertex_index, face_index, kept)

@@ -385,3 +385,21 @@ def test_exact_data_stays_in_the_exact_regime_at_the_inference_shapes():
     assert n == 6 * 20 + 4 * 7
     last = dict(X.layers("pose", 1, 256, 320))["conv7"]
     assert (last.Ho, last.Wo) == (2, 3)
+
+
+def test_call_passes_pointers_and_raises_under_the_entry_points_name(lib):
+    """_lib.call: tensors go as their addresses and None as NULL, the status is checked under the name that was called.  The native
+    half uses colvo_mesh_topology_components, which refuses a scratch address that is not 16-byte aligned before its first HIP call."""
+    import types
+    import unittest.mock as mock
+    from coivo_amd import _lib
+    t = torch.zeros(5)
+    seen = []
+    stub = types.SimpleNamespace(colvo_x=lambda *a: seen.append(a) or 0, colvo_y=lambda *a: 7, colvo_last_error=lambda: b"why")
+    with mock.patch.object(_lib, "load", lambda: stub):
+        assert _lib.call("colvo_x", t, None, 3, 0.5, "s") is None
+        assert seen == [(t.data_ptr(), 0, 3, 0.5, "s")]
+        with pytest.raises(RuntimeError, match=r"colvo_y failed \(code 7\): why"):
+            _lib.call("colvo_y", t)
+    with pytest.raises(RuntimeError, match="colvo_mesh_topology_components failed .*scratch must be 16-byte aligned"):
+        _lib.call("colvo_mesh_topology_components", 0x1000, 4, 2, 0x1008, 0x2000, 0x3000, 0x4000, None)

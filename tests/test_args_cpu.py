@@ -115,3 +115,76 @@ def test_voxel_grid_normalises():
     (None, None, 1e39, "voxel_size"), (None, None, "x", "voxel_size")])
 def test_voxel_grid_refuses(origin, dims, vs, name):
     _refused(lambda: A.voxel_grid(WHO, origin, dims, vs), name)
+
+
+# ---- clouds, reach, Sim(3) --------------------------------------------------------------------------------------------- #
+@pytest.mark.parametrize("t", [torch.zeros(4, 3), torch.zeros(4, 3, dtype=torch.float64), torch.zeros(4, 2), None],
+                         ids=["cpu", "dtype", "last_dim", "none"])
+def test_cloud_refuses(t):
+    _refused(lambda: A.cloud(WHO, "query", t), "query")
+
+
+def test_reach_returns_float32_values():
+    assert A.reach(WHO, 0.08, (0.02, 0.08)) == (A.f32(0.08), (A.f32(0.02), A.f32(0.08))) and A.reach(WHO, 1, ()) == (1.0, ())
+    _refused(lambda: A.reach(WHO, -1.0, ()), "max_dist")
+    _refused(lambda: A.reach(WHO, 0.1, (0.2,)), "thresholds")
+    _refused(lambda: A.reach(WHO, 0.1, [0.01] * (A.MAX_THRESHOLDS + 1)), "thresholds")
+
+
+def test_sim3_gives_host_float64_and_refuses_the_rest():
+    R, t, s = A.sim3(WHO, "init", (torch.eye(3), [1, 2, 3], torch.tensor([2.0])))
+    assert R.dtype == t.dtype == torch.float64 and tuple(R.shape) == (3, 3) and t.tolist() == [1.0, 2.0, 3.0] and s == 2.0
+    assert isinstance(s, float)
+    bad_R = torch.eye(3).clone()
+    bad_R[1, 1] = math.nan
+    for bad in ((torch.eye(4), torch.zeros(3), 1.0), (torch.eye(3), torch.zeros(4), 1.0), (torch.eye(3), torch.zeros(3), [1.0, 2.0]),
+                (bad_R, torch.zeros(3), 1.0), (torch.eye(3), torch.zeros(3), math.inf), (torch.eye(3), torch.zeros(3)), 5, None,
+                (torch.eye(3), "x", 1.0)):
+        _refused(lambda: A.sim3(WHO, "init", bad), "init")
+
+
+def test_finite_nonneg64_does_not_round():
+    assert A.finite_nonneg64(WHO, "damping", 1e-50) == 1e-50 and A.finite_nonneg64(WHO, "damping", 0) == 0.0
+    for bad in (-1e-300, math.nan, math.inf, "x", None):
+        _refused(lambda: A.finite_nonneg64(WHO, "damping", bad), "damping")
+
+
+# ---- meshes ------------------------------------------------------------------------------------------------------------ #
+def test_mesh_arrays_refuses():
+    v, f = torch.zeros(4, 3), torch.zeros(2, 3, dtype=torch.int32)
+    _refused(lambda: A.mesh_arrays(WHO, v, f), "vertices")                                        # on the CPU
+    _refused(lambda: A.mesh_arrays(WHO, v.double(), f), "vertices")
+    _refused(lambda: A.mesh_arrays(WHO, torch.zeros(4, 2), f), "vertices")
+    _refused(lambda: A.mesh_arrays(WHO, v, f.long()), "faces")
+    _refused(lambda: A.mesh_arrays(WHO, v, torch.zeros(2, 4, dtype=torch.int32)), "faces")
+    mesh = A.Mesh(v, f, None, v, torch.zeros(4, 3, dtype=torch.int32), 0)
+    _refused(lambda: A.mesh_arrays(WHO, mesh, f), "faces")                                        # with a Mesh give no faces
+    _refused(lambda: A.mesh_arrays(WHO, mesh, None), "vertices")
+
+
+def test_mesh_attributes_refuses_cells_of_the_wrong_dtype_or_shape():
+    import unittest.mock as mock
+    v = torch.zeros(4, 3)
+    with mock.patch.object(A, "device_f32", lambda who, name, t, shape: t):                       # (no device here)
+        for cells in (torch.zeros(4, 3, dtype=torch.int64), torch.zeros(3, 3, dtype=torch.int32), torch.zeros(4, dtype=torch.int32), None):
+            _refused(lambda: A.mesh_attributes(WHO, A.Mesh(v, None, None, v, cells, 0), 4, v.device), "mesh.cells")
+        colors, normals, cells = A.mesh_attributes(WHO, A.Mesh(v, None, None, v, torch.zeros(4, 3, dtype=torch.int32), 0), 4, v.device)
+        assert colors is None and normals is v and cells.is_contiguous()
+
+
+def test_own_topology_checks_the_tables_the_caller_reads():
+    from types import SimpleNamespace
+    dev = torch.device("cpu")
+    i32 = lambda *s: torch.zeros(*s, dtype=torch.int32)
+    topo = SimpleNamespace(vertex_component=i32(4), face_component=i32(2), vertex_loop=i32(4),
+                           components=torch.zeros(1, 8, dtype=torch.int64), loops=torch.zeros(1, 4, dtype=torch.int64))
+    A.own_topology(WHO, topo, 4, 2, dev, ("components",))
+    A.own_topology(WHO, topo, 4, 2, dev, ("loops",))
+    for V, F in ((5, 2), (4, 3)):
+        for tables in (("components",), ("loops",)):
+            _refused(lambda: A.own_topology(WHO, topo, V, F, dev, tables), "topology")
+    topo.loops = topo.loops.to(torch.int32)                                                       # clean_mesh does not read the loops
+    A.own_topology(WHO, topo, 4, 2, dev, ("components",))
+    _refused(lambda: A.own_topology(WHO, topo, 4, 2, dev, ("loops",)), "topology")
+    topo.vertex_component = i32(3)                                                                # fill_holes does not read the components
+    _refused(lambda: A.own_topology(WHO, topo, 4, 2, dev, ("components",)), "topology")

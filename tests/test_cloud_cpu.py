@@ -131,7 +131,7 @@ def test_cloud_entry_points_validate_their_arguments(lib):
 
 
 def test_python_functions_refuse_what_the_kernels_cannot_take():
-    from coivo_amd import evaluate as E
+    from coivo_amd import _args, evaluate as E
     ok = torch.zeros(4, 3)
     for bad in (ok, ok.double(), torch.zeros(4, 2), torch.zeros(3), torch.zeros(2, 4, 3), [[0.0, 0.0, 0.0]]):
         with pytest.raises(ValueError, match="float32 CUDA tensor of shape"):
@@ -143,21 +143,21 @@ def test_python_functions_refuse_what_the_kernels_cannot_take():
         with pytest.raises(ValueError, match="float32 CUDA tensor of shape"):
             E.reconstruction_metrics(bad, torch.eye(4)[None], torch.zeros(1, 1, 8, 8), torch.eye(3)[None], torch.eye(4)[None],
                                      voxel_size=0.1)
-    assert E._chk_reach("x", 0.08, (0.02, 0.04, 0.08)) == (E._f32(0.08), (E._f32(0.02), E._f32(0.04), E._f32(0.08)))
-    assert E._chk_reach("x", 1, ()) == (1.0, ())
+    assert _args.reach("x", 0.08, (0.02, 0.04, 0.08)) == (_args.f32(0.08), (_args.f32(0.02), _args.f32(0.04), _args.f32(0.08)))
+    assert _args.reach("x", 1, ()) == (1.0, ())
     for md in (0.0, -1.0, math.inf, math.nan, 1e-30, 1e30, 1e300, "a", None):
         with pytest.raises(ValueError, match="max_dist"):
-            E._chk_reach("x", md, ())
+            _args.reach("x", md, ())
     for th in ((0.02, 0.01), (0.0,), (-0.1,), (0.2,), (math.nan,), tuple([0.01] * 9), ("a",)):
         with pytest.raises(ValueError, match="thresholds"):
-            E._chk_reach("x", 0.1, th)
+            _args.reach("x", 0.1, th)
 
 
 def test_measures_from_hand_made_statistics():
-    from coivo_amd import evaluate as E
-    md = E._f32(0.08)
+    from coivo_amd import _args, evaluate as E
+    md = _args.f32(0.08)
     s = float(np.float32(2 ** 20) / np.float32(0.08))
-    assert E._f32(1048576.0 / md) == s                  # the Python side's scale is the float32 quotient
+    assert _args.f32(1048576.0 / md) == s                  # the Python side's scale is the float32 quotient
     pred = [10, 8, 2, 5, 0, 0, 0, 0, 0, 0, 3 * 2 ** 20, 123]
     gt = [20, 20, 5, 20, 0, 0, 0, 0, 0, 0, 5 * 2 ** 20, 456]
     m = E.metrics_from_stats(pred, gt, md, 2)

@@ -305,7 +305,7 @@ def test_cloud_metrics_with_a_transform_equal_the_replica_on_its_pinned_transfor
 
 # ---- end to end ------------------------------------------------------------------------------------------------------------- #
 def test_reconstruction_metrics_end_to_end():
-    from coivo_amd import evaluate as E, inference as I
+    from coivo_amd import _args, evaluate as E, inference as I
     from tests import fuse_ref
     depths, _, K, M = fuse_ref.scene(6, 32, 40, 5)
     vs = 0.1
@@ -318,11 +318,11 @@ def test_reconstruction_metrics_end_to_end():
     assert m.accuracy == 0.0 and m.completeness == 0.0 and m.chamfer == 0.0
     assert m.precision == (1.0, 1.0) and m.recall == (1.0, 1.0) and m.fscore == (1.0, 1.0)
     assert m.n_pred == m.n_gt == m.n_pred_reached == m.n_gt_reached == gt.points.shape[0]
-    assert m.pred_to_gt.max_dist == I._f32(4 * I._f32(vs)) and m.pred_to_gt.thresholds == (I._f32(vs), I._f32(2 * I._f32(vs)))
+    assert m.pred_to_gt.max_dist == _args.f32(4 * _args.f32(vs)) and m.pred_to_gt.thresholds == (_args.f32(vs), _args.f32(2 * _args.f32(vs)))
     # depths 3 % too deep, no alignment
     pred = I.fuse_point_cloud((d * 1.03).contiguous(), Kt, Mt, voxel_size=vs)
     m = E.reconstruction_metrics(pred, traj, d, Kt, traj, voxel_size=vs, align="none")
-    want = R.metrics(pred.points.cpu().numpy(), gt.points.cpu().numpy(), I._f32(4 * I._f32(vs)), (I._f32(vs), I._f32(2 * I._f32(vs))))
+    want = R.metrics(pred.points.cpu().numpy(), gt.points.cpu().numpy(), _args.f32(4 * _args.f32(vs)), (_args.f32(vs), _args.f32(2 * _args.f32(vs))))
     _assert_metrics(m, want)
     assert 0.0 < m.accuracy < 0.4 and 0.0 < m.fscore[0] < 1.0
     # the prediction in another Sim(3) frame: trajectory and cloud moved by the same map
@@ -337,7 +337,7 @@ def test_reconstruction_metrics_end_to_end():
     m = E.reconstruction_metrics(moved.to(dev()), moved_traj, d, Kt, traj, voxel_size=vs)
     A = E.align_trajectory(moved_traj, traj, "sim3")
     assert abs(A[2] - s) < 1e-9
-    want = R.metrics(moved.numpy(), gt.points.cpu().numpy(), I._f32(4 * I._f32(vs)), (I._f32(vs), I._f32(2 * I._f32(vs))),
+    want = R.metrics(moved.numpy(), gt.points.cpu().numpy(), _args.f32(4 * _args.f32(vs)), (_args.f32(vs), _args.f32(2 * _args.f32(vs))),
                      transform_=(A[0].numpy(), A[1].numpy(), A[2]))
     _assert_metrics(m, want)
     assert 0.0 < m.accuracy < 0.4

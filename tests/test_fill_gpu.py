@@ -242,7 +242,7 @@ def test_render_and_point_to_surface_take_the_filled_mesh():
 
 
 def test_surface_reconstruction_metrics_fills_the_ground_truth_mesh():
-    from coivo_amd import evaluate as E, inference as I
+    from coivo_amd import _args, evaluate as E, inference as I
     scene = _scene("tube2")
     depths, K, M, kw = scene[1]
     pred = _gpu_mesh(scene)
@@ -254,7 +254,7 @@ def test_surface_reconstruction_metrics_fills_the_ground_truth_mesh():
     gt = I.extract_mesh(I.fuse_tsdf(_t(depths), _t(K), _t(M), voxel_size=kw["voxel_size"], max_depth=T.TUBE_MAX_DEPTH), min_obs=2)
     assert torch.equal(gt.faces, pred.faces)
     fill = I.fill_holes(gt, I.mesh_topology(gt, unit=kw["voxel_size"]), max_edges=12)
-    vs = I._f32(kw["voxel_size"])
+    vs = _args.f32(kw["voxel_size"])
     _same(got, E.surface_metrics(pred, fill.mesh, max_dist=4.0 * vs, thresholds=(vs, 2.0 * vs)))
     plain = E.surface_reconstruction_metrics(*args, **common)
     assert got.n_gt == plain.n_gt + int(fill.new_vertex_loop.shape[0]) > plain.n_gt and got.n_pred == plain.n_pred

@@ -52,9 +52,9 @@ def test_isinstance_holds_across_modules():
 
 @pytest.mark.parametrize("first", ["localize", "evaluate", "inference", "render", "fusion"])
 def test_module_can_be_imported_first(first):
-    """A fresh interpreter: no import order has papered over a cycle."""
+    """A fresh interpreter: no import order has papered over a cycle (localize takes align_trajectory from trajectory, not evaluate)."""
     code = (f"import coivo_amd.{first} as m, sys; import coivo_amd.inference as I, coivo_amd.localize as L, coivo_amd.evaluate as E; "
-            "assert I.localize is L and L.evaluate is E and E.inference is I; print('ok')")
+            "assert I.localize is L and L.align_trajectory is E.align_trajectory and E.inference is I; print('ok')")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=120, cwd=root)
     assert r.returncode == 0 and r.stdout.strip() == "ok", r.stderr

@@ -191,7 +191,7 @@ def test_kernels_use_no_scratch(lib, tmp_path):
 
 
 def test_python_wrappers_refuse_bad_arguments_before_any_native_call():
-    from coivo_amd import evaluate as E
+    from coivo_amd import evaluate as E, registration
     assert E.Registration._fields == ("mode", "metric", "iterations", "max_dist", "damping", "min_pairs")
     assert tuple(E.Registration()) == ("sim3", "plane", 20, None, 1e-9, 64)
     assert E.RegistrationResult._fields == ("R", "t", "s", "history", "status", "normal_matrix")
@@ -217,12 +217,12 @@ def test_python_wrappers_refuse_bad_arguments_before_any_native_call():
         with pytest.raises(ValueError, match=word):                                # (the policy is looked at before the clouds)
             E.register_clouds(ok, ok, max_dist=0.1, **kw)
         with pytest.raises(ValueError, match=word):
-            E._chk_registration("x", E.Registration(**kw))
+            registration.check_registration("x", E.Registration(**kw))
     for md in (0.0, -1.0, math.inf, math.nan, 1e-30, "a"):
         with pytest.raises(ValueError, match="max_dist"):
-            E._chk_registration("x", E.Registration(max_dist=md))
+            registration.check_registration("x", E.Registration(max_dist=md))
     with pytest.raises(ValueError, match="Registration"):
-        E._chk_registration("x", dict(mode="sim3"))
+        registration.check_registration("x", dict(mode="sim3"))
     with pytest.raises(ValueError, match="Registration"):
         E.cloud_metrics(ok, ok, max_dist=0.1, thresholds=(0.05,), register="sim3")
     with pytest.raises(ValueError):

@@ -210,7 +210,7 @@ def test_freeze_and_revert_return_the_input_to_the_bit(name):
 
 # ---- 6. the reconstruction score ------------------------------------------------------------------------------------------ #
 def test_reconstruction_metrics_registers_when_asked():
-    from coivo_amd import evaluate as E, inference as I
+    from coivo_amd import _args, evaluate as E, inference as I
     sc = G.fused_scene()
     d, K, M = _t(sc["depths"]), _t(sc["K"]), _t(sc["M"])
     traj = torch.from_numpy(sc["M"]).double()
@@ -220,7 +220,7 @@ def test_reconstruction_metrics_registers_when_asked():
     none = E.reconstruction_metrics(pred, traj, d, K, traj, voxel_size=vs, register=None)
     A = E.align_trajectory(traj, traj, "sim3")
     gt = I.fuse_point_cloud(d, K, M, voxel_size=vs)
-    direct = E.cloud_metrics(pred, gt.points, max_dist=4.0 * I._f32(vs), thresholds=(I._f32(vs), 2.0 * I._f32(vs)), transform=A)
+    direct = E.cloud_metrics(pred, gt.points, max_dist=4.0 * _args.f32(vs), thresholds=(_args.f32(vs), 2.0 * _args.f32(vs)), transform=A)
     for m in (plain, none):
         assert m.registration is None and len(m) == 12
         assert tuple(m[:10]) == tuple(direct[:10])
@@ -241,7 +241,7 @@ def test_reconstruction_metrics_registers_when_asked():
     print("|transform - replica|", diff, "status", want["status"])
     assert want["status"] == G.OK and diff <= 1e-6
     # the measures are those of the refined transform
-    again = E.cloud_metrics(pred, gt.points, max_dist=4.0 * I._f32(vs), thresholds=(I._f32(vs), 2.0 * I._f32(vs)), transform=(R, t, s))
+    again = E.cloud_metrics(pred, gt.points, max_dist=4.0 * _args.f32(vs), thresholds=(_args.f32(vs), 2.0 * _args.f32(vs)), transform=(R, t, s))
     assert tuple(again[:10]) == tuple(reg[:10])
 
 

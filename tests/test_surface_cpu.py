@@ -318,12 +318,12 @@ def _patch(k, z=0.0):
 
 
 def test_measures_from_the_replica_statistics():
-    from coivo_amd import evaluate as E
+    from coivo_amd import _args, evaluate as E
     assert E.SURFACE_STATS == S.STATS and E.SURFACE_STATS[:12] == E.CLOUD_STATS
     v, faces = _patch(6)
     md, th = 0.25, (0.05, 0.125)
     same = S.nearest(v, v, faces, md, th)
-    m = E.metrics_from_stats(same["stats"][:12], same["stats"][:12], E._f32(md), 2)
+    m = E.metrics_from_stats(same["stats"][:12], same["stats"][:12], _args.f32(md), 2)
     assert m["accuracy"] == 0.0 and m["completeness"] == 0.0 and m["chamfer"] == 0.0
     assert m["precision"] == (1.0, 1.0) and m["recall"] == (1.0, 1.0) and m["fscore"] == (1.0, 1.0)
     assert m["n_pred"] == m["n_pred_reached"] == len(v)
@@ -333,7 +333,7 @@ def test_measures_from_the_replica_statistics():
     assert (a["dist"] == 0.0625).all() and (a["side"] == 1).all() and (b["side"] == -1).all()
     assert a["stats"][10] == len(v) * 2 ** 18 and a["stats"][12] == len(v) and b["stats"][13] == len(v)
     assert a["stats"][14] == len(v)                                          # (an edge candidate at the same d2 never replaces the plane one)
-    m = E.metrics_from_stats(a["stats"][:12], b["stats"][:12], E._f32(md), 2)
+    m = E.metrics_from_stats(a["stats"][:12], b["stats"][:12], _args.f32(md), 2)
     assert m["accuracy"] == 0.0625 and m["completeness"] == 0.0625 and m["precision"] == (0.0, 1.0) and m["recall"] == (0.0, 1.0)
     assert m["fscore"] == (0.0, 1.0)
     r = S.metrics((up, faces), (v, faces), md, th)

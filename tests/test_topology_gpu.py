@@ -268,7 +268,7 @@ def test_degenerate_inputs_give_empty_well_formed_results():
 
 # ---- 9. the whole pipeline ------------------------------------------------------------------------------------------------------------- #
 def test_reconstruct_sequence_returns_the_topology_and_cleans():
-    from coivo_amd import inference as I, nn as hnn, synth
+    from coivo_amd import _args, inference as I, nn as hnn, synth
     from oracle import colvo_spec as S
     dn_o, pn_o = S.make_models(31)
     dn, pn = hnn.DepthNet(), hnn.PoseNet()
@@ -283,7 +283,7 @@ def test_reconstruct_sequence_returns_the_topology_and_cleans():
                       colors=frames.float().contiguous(), stride=2, max_depth=0.5)
     raw = I.extract_mesh(vol, min_obs=2)
     _same(plain.mesh, raw)
-    assert isinstance(plain.topology, I.MeshTopology) and plain.topology.unit == I._f32(0.005)
+    assert isinstance(plain.topology, I.MeshTopology) and plain.topology.unit == _args.f32(0.005)
     _same(plain.topology, I.mesh_topology(raw, unit=0.005))
     rec = I.reconstruct_sequence(dn, pn, frames, K, mesh=I.Meshing(0.02, 2, min_faces=4), render=I.Render(mesh=True), **kw)
     assert len(rec) == 5 and isinstance(rec.topology, I.MeshTopology) and rec.mesh.faces.shape[0] > 0

@@ -29,7 +29,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from bench_fuse import H, W, MAX_DEPTH, make, time_us  # noqa: E402
-from coivo_amd import _lib, build, evaluate as E, inference as I  # noqa: E402
+from coivo_amd import _args, _lib, build, cloud_eval, evaluate as E, inference as I  # noqa: E402
 
 
 class Search:
@@ -81,7 +81,7 @@ def main():
     gt = I.fuse_point_cloud(depths, K, M, voxel_size=a.voxel, max_depth=MAX_DEPTH).points
     pred = I.fuse_point_cloud(pred_depths, K, M, voxel_size=a.voxel, max_depth=MAX_DEPTH).points
     stitched = I.stitch_point_cloud(pred_depths, K, M, stride=1, max_depth=MAX_DEPTH)
-    md, th = E._chk_reach("bench_cloud", a.max_dist, (a.max_dist / 4, a.max_dist / 2))
+    md, th = _args.reach("bench_cloud", a.max_dist, (a.max_dist / 4, a.max_dist / 2))
     out = dict(bench="cloud_metrics", N=N, H=H, W=W, voxel=a.voxel, max_dist=md, thresholds=list(th), n_gt=gt.shape[0],
                n_pred=pred.shape[0], n_stitched=stitched.shape[0], iters=a.iters, warmup=a.warmup, query_form="lane per query")
     print(json.dumps({k: out[k] for k in ("n_gt", "n_pred", "n_stitched", "max_dist")}), flush=True)
@@ -100,7 +100,7 @@ def main():
         row["examined_per_query"] = round(st[11] / max(st[0], 1), 2)
         row["query_points_per_s"] = rate(row["query_us"], q.shape[0])
         row["build_points_per_s"] = rate(row["build_us"], r.shape[0])
-        row["mean_distance"] = E._mean_distance(st, md)
+        row["mean_distance"] = cloud_eval.mean_truncated_distance(st, md)
         rows[name] = row
         print(f"{name:15s}: {q.shape[0]:9d} queries, {r.shape[0]:9d} refs: build {row['build_us']:9.1f} us  query {row['query_us']:10.1f} us  "
               f"| {row['query_points_per_s'] / 1e9:6.3f} G queries/s, {row['examined_per_query']:7.2f} records examined per query, "

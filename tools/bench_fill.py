@@ -22,7 +22,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from coivo_amd import _lib, build, holes, inference as I  # noqa: E402
+from coivo_amd import _args, _lib, build, holes, inference as I  # noqa: E402
 from bench_fuse import H, MAX_DEPTH, W, make, time_us  # noqa: E402
 
 
@@ -95,7 +95,7 @@ def main():
     dev = torch.device("cuda:0")
     depths, colors, K, M = make(a.frames, dev)
     origin, dims = I.fusion_grid(K, M, H, W, a.voxel, MAX_DEPTH)
-    unit = I._f32(a.voxel)
+    unit = _args.f32(a.voxel)
     volume = I.fuse_tsdf(depths, K, M, voxel_size=a.voxel, colors=colors, max_depth=MAX_DEPTH, origin=origin, dims=dims)
     mesh = I.extract_mesh(volume, min_obs=a.min_obs)
     topo = I.mesh_topology(mesh, unit=unit)

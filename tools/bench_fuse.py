@@ -25,7 +25,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from coivo_amd import _lib, build, inference as I, synth  # noqa: E402
+from coivo_amd import _args, _lib, build, inference as I, synth  # noqa: E402
 
 H, W = 256, 320
 MAX_DEPTH = 4.5
@@ -174,7 +174,7 @@ def main():
     N = a.frames
     depths, colors, K, M = make(N, dev)
     origin, dims = I.fusion_grid(K, M, H, W, a.voxel, MAX_DEPTH)
-    vs = I._f32(a.voxel)
+    vs = _args.f32(a.voxel)
     ph = Phases(depths, colors, K, M, origin, dims, vs, a.min_obs)
     inside = ph.n_input - ph.n_outside
     out = dict(bench="fuse_point_cloud", N=N, H=H, W=W, stride=1, voxel=a.voxel, min_obs=a.min_obs, dims=list(dims),

@@ -31,7 +31,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from bench_fuse import H, W, MAX_DEPTH, make  # noqa: E402
-from coivo_amd import _lib, build, evaluate as E, inference as I  # noqa: E402
+from coivo_amd import _args, _lib, build, evaluate as E, inference as I  # noqa: E402
 
 
 def alternate_us(fns, iters, warmup):
@@ -90,7 +90,7 @@ def main():
     normals = I.cloud_normals(gt_fused, depths, K, M, stride=1, max_depth=MAX_DEPTH).normals
     pred = I.fuse_point_cloud(pred_depths, K, M, voxel_size=a.voxel, max_depth=MAX_DEPTH).points
     del pred_depths
-    md, _ = E._chk_reach("bench_register", a.max_dist, ())
+    md, _ = _args.reach("bench_register", a.max_dist, ())
     with_normal = int(((normals != 0).any(dim=1)).sum())
     out = dict(bench="register_clouds", N=N, H=H, W=W, voxel=a.voxel, max_dist=md, n_gt=gt.shape[0], n_pred=pred.shape[0],
                n_gt_with_normal=with_normal, iters=a.iters, warmup=a.warmup, mode="sim3", metric="plane")

@@ -29,7 +29,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from bench_cloud import Search  # noqa: E402
 from bench_fuse import H, W, MAX_DEPTH, make, time_us  # noqa: E402
-from coivo_amd import _lib, build, evaluate as E, inference as I  # noqa: E402
+from coivo_amd import _args, _lib, build, cloud_eval, evaluate as E, inference as I, surface_eval  # noqa: E402
 
 
 class Index:
@@ -92,12 +92,12 @@ def main():
 
     def surface(d):
         raw = I.extract_mesh(I.fuse_tsdf(d, K, M, voxel_size=a.voxel, max_depth=MAX_DEPTH), min_obs=2)
-        return raw, E._cleaned(raw)
+        return raw, surface_eval.cleaned(raw)
 
     gt_raw, gt = surface(depths)
     pred_raw, pred = surface(pred_depths)
     del depths, pred_depths
-    md, th = E._chk_reach("bench_surface", a.max_dist, (a.max_dist / 4, a.max_dist / 2))
+    md, th = _args.reach("bench_surface", a.max_dist, (a.max_dist / 4, a.max_dist / 2))
     out = dict(bench="surface_metrics", N=N, H=H, W=W, voxel=a.voxel, max_dist=md, thresholds=list(th),
                gt=dict(V=gt_raw.vertices.shape[0], F=gt_raw.faces.shape[0], V_clean=gt.vertices.shape[0], F_clean=gt.faces.shape[0]),
                pred=dict(V=pred_raw.vertices.shape[0], F=pred_raw.faces.shape[0], V_clean=pred.vertices.shape[0],
@@ -122,7 +122,7 @@ def main():
             row["pairs_per_face"] = round(st[17] / max(s.F, 1), 3)
             row["examined_per_query"] = round(st[11] / max(st[0], 1), 2)
             row["oversize"] = st[18]
-            row["mean_distance"] = E._mean_distance(st, md)
+            row["mean_distance"] = cloud_eval.mean_truncated_distance(st, md)
             rows[name + ("_copied" if copy else "")] = row
             print(f"{name:11s} records of {s.record_bytes:2d} B: {q.shape[0]:8d} queries, {s.F:8d} faces, {s.pairs:8d} pairs ({row['pairs_per_face']:.3f} a "
                   f"face), {st[18]} oversize: plan {row['plan_us']:8.1f} us  fill {row['fill_us']:8.1f} us  query {row['query_us']:9.1f} us, "
@@ -132,7 +132,7 @@ def main():
         row = dict(build_us=round(time_us(c.build, a.iters, a.warmup), 1), query_us=round(time_us(c.query, a.iters, a.warmup), 1))
         cst = c.stats.tolist()
         row["examined_per_query"] = round(cst[11] / max(cst[0], 1), 2)
-        row["mean_distance"] = E._mean_distance(cst, md)
+        row["mean_distance"] = cloud_eval.mean_truncated_distance(cst, md)
         rows[name + "_vertices"] = row
         print(f"{name:11s} to the vertices (nearest_neighbors): build {row['build_us']:8.1f} us  query {row['query_us']:8.1f} us, "
               f"{row['examined_per_query']:6.2f} points per query, mean distance {row['mean_distance']:.5f}", flush=True)

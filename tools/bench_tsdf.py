@@ -22,7 +22,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from coivo_amd import _lib, build, inference as I  # noqa: E402
+from coivo_amd import _args, _lib, build, inference as I  # noqa: E402
 from bench_fuse import H, MAX_DEPTH, W, make, time_us  # noqa: E402
 
 T = 4
@@ -140,7 +140,7 @@ def main():
     N = a.frames
     depths, colors, K, M = make(N, dev)
     origin, dims = I.fusion_grid(K, M, H, W, a.voxel, MAX_DEPTH)
-    vs = I._f32(a.voxel)
+    vs = _args.f32(a.voxel)
     ph = Phases(depths, colors, K, M, origin, dims, vs, a.min_obs)
     surv = ph.survivors.float()
     out = dict(bench="fuse_tsdf", N=N, H=H, W=W, stride=1, voxel=a.voxel, T=T, min_obs=a.min_obs, dims=list(dims),
